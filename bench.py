@@ -13,8 +13,8 @@ A "step" is one pass of the hot path over one of the synthetic vectors: the stre
 kernel and -- for N > 1 -- the int64 all-reduce of the three 576-byte digit sets (main + low + high) plus the re-finalize, all issued by
 libexblas.so (exblas_exsum_accumulate_dev + exblas_allreduce_finish_dev: ncclAllReduce on a HIP stream, no
 torch.distributed in the step).  --rotate (default 4) DISTINCT vectors are cycled through, so no step can be served by
-the 256 MiB Infinity Cache from the previous one.  The same-buffer variant (every step re-reads one vector) is measured
-beside it and reported under roofline.same_buffer.
+the 256 MiB Infinity Cache from the previous one.  With --full the same-buffer variant (every step re-reads one vector)
+is measured beside it and reported under roofline.same_buffer.
 
 Scaling (BASELINE config 3; reference: ONE vector scattered over the ranks, limbs reduced, root rounds --
 src/cpu/blas/blas1/ExSUM.cpp:33-63,142-152):
@@ -27,9 +27,19 @@ src/cpu/blas/blas1/ExSUM.cpp:33-63,142-152):
   * --scaling weak makes the weak figure the headline (n_total = N * 2^log2n).
 
 Prints ONE JSON line on rank 0 (see README / task contract), with `roofline` for the dominant kernel (k_exsum resp.
-k_exdot: algorithmic 8 resp. 16 B/element over the HIP-event time of that kernel alone) and `cpu_baseline` (N == 1
-only: the reference's own compiled FPE+superaccumulator core from oracle/_ref when it can be loaded, else our C port,
-on the host cores).
+k_exdot: algorithmic 8 resp. 16 B/element over the HIP-event time of that kernel alone, sampled inside the timed steps).
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write --dump-outputs if given,
+print the line.  --full adds everything else: the same-buffer variant and the read probes (roofline.same_buffer,
+measured_read_probe_GBs), the weak-scaling leg beside a strong one, `cpu_baseline` (N == 1 only: the reference's own
+compiled FPE+superaccumulator core from oracle/_ref when it can be loaded, else our C port, on the host cores) and the
+CPU bit check (`bit_exact_vs_cpu`), the ExDOT leg and the ExGEMV / ExGEMM / ExTRSV and host-API line items.  The
+--no-* / --skip-* options below thin out a --full run.
+
+--dump-outputs DIR writes, on rank 0, the record the LAST timed step produced (the step reads rotating vector
+(warmup + steps - 1) mod --rotate): DIR/result.npy = [rounded result, reference-mode rounding] and
+DIR/canon_limbs.npy = the 41 canonical 52-bit limbs of the exact sum, both float64 (every limb is an integer below
+2^53: exact).  The inputs are a function of the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -76,6 +86,11 @@ def parse():
                          "per-kernel averages of a rocprofv3 --stats run)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "hbm_traffic.json"),
                     help="per-launch HBM bytes from a separate rocprofv3 --pmc pass, if present")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: same-buffer variant, read probes, weak leg, CPU baseline and bit "
+                         "check, ExDOT, BLAS2/3 and host-API items (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the record of the last timed step as DIR/result.npy and DIR/canon_limbs.npy (float64)")
     return ap.parse_args()
 
 
@@ -145,6 +160,9 @@ def timed_steps(ex, torch, dist, comm, op, buffers, fpe, ee, steps, warmup, worl
             one_step()
         drain()
         torch.cuda.synchronize()
+    # the prewarm ran as many steps as fit its time: the count restarts after it, so which buffer a later step reads
+    # depends on the arguments only (the last timed step reads buffer (warmup + steps - 1) mod nbuf)
+    state["i"] = 0
     for _ in range(warmup):
         one_step()
     drain()
@@ -519,6 +537,17 @@ def record_ids(rec):
             "limbs_crc": "0x%08x" % (zlib.crc32(np.ascontiguousarray(rec.canon, dtype="<i8").tobytes()) & 0xffffffff)}
 
 
+def dump_outputs(path, rec):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 arrays"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    limbs = np.asarray(rec.canon, dtype=np.int64)
+    as_f64 = limbs.astype(np.float64)
+    assert (as_f64.astype(np.int64) == limbs).all(), "a canonical limb does not fit a double exactly"
+    np.save(os.path.join(path, "result.npy"), np.array([rec.exact, rec.refmode], dtype=np.float64))
+    np.save(os.path.join(path, "canon_limbs.npy"), as_f64)
+
+
 def cpu_parity_only(op, host_arrays, fpe, ee, rec_gpu):
     """ONE run of the CPU core on the full vector(s) (all host threads): the bit check of an N > 1 run and of the ExDOT
     leg; not a timing."""
@@ -680,6 +709,7 @@ def main():
         if world > 1:
             roof["note"] = ("per GPU: the algorithmic bytes of the rank's shard / the slowest rank's mean kernel time; "
                             "traffic counters are collected at N = 1 only")
+        last = ex.read_record(rec)
         result = None
         if same_buffer:
             rec1 = ex.new_record_buffer()
@@ -693,6 +723,11 @@ def main():
                                            "Infinity Cache"}
             # the record of the LAST rotating step belongs to buffer (steps-1) mod rotate; buffer 0's result is rec1
             result = ex.read_record(rec1)
+        else:
+            # buffer 0's result (what `result` reports) from one untimed step of the same path
+            rec1 = ex.new_record_buffer()
+            timed_steps(ex, torch, dist, comm, op, bufs[:1], args.fpe, ee, 1, 0, world, rec1)
+            result = ex.read_record(rec1)
         if probes:
             probe_rot, probe_same = probe_read(ex, torch, bufs, op == "exdot", n_local)
             roof["measured_read_probe_GBs"] = probe_rot
@@ -701,31 +736,34 @@ def main():
                                   "kernel_ms is the dispatch's own duration: a ratio within 1 % of 1 means equal")
             if same_buffer:
                 roof["same_buffer"]["measured_read_probe_GBs"] = probe_same
-        return bufs, dt, roof, result, n_total
+        return bufs, dt, roof, result, n_total, last
+
+    cpu_check = args.full and not args.no_cpu_baseline
 
     def leg(op, want_cpu_timing):
-        """the headline measurement of one op in the selected scaling mode (+ the weak figure beside a strong one,
-        + the CPU bit check); returns (JSON pieces, device vector 0 for the host-API item)"""
+        """the headline measurement of one op in the selected scaling mode (--full: + the same-buffer variant and the
+        probes, the weak figure beside a strong one, the CPU bit check); returns (JSON pieces, device vector 0 for the
+        host-API item, record of the last timed step)"""
         mode = "strong" if strong else "weak"
-        bufs, dt, roof, result, n_total = run_op(op, mode)
+        bufs, dt, roof, result, n_total, last = run_op(op, mode, same_buffer=args.full, probes=args.full)
         o = {"value": n_total * args.steps / dt / 1e9, "unit": "Gelem/s", "ms_per_step": dt / args.steps * 1e3,
              "scaling": "strong" if strong else "weak", "n_total": n_total, "roofline": roof,
              "result": result.exact}
         o.update(record_ids(result))
         keep = bufs[0][0] if world == 1 else None
         host0 = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_check:
             host0 = [t.cpu().numpy() for t in bufs[0]]
         del bufs
         torch.cuda.empty_cache()
-        if strong and not args.no_weak_leg:
-            wb, wdt, wroof, _, wn = run_op(op, "weak", same_buffer=False, probes=False)
+        if args.full and strong and not args.no_weak_leg:
+            wb, wdt, wroof, _, wn, _ = run_op(op, "weak", same_buffer=False, probes=False)
             o["weak"] = {"value": wn * args.steps / wdt / 1e9, "unit": "Gelem/s", "ms_per_step": wdt / args.steps * 1e3,
                          "scaling": "weak", "elements_per_gpu": n, "n_total": wn, "kernel_ms": wroof["kernel_ms"],
                          "frac_hbm_peak_per_gpu": wroof["frac"]}
             del wb
             torch.cuda.empty_cache()
-        if not args.no_cpu_baseline and rank == 0:
+        if cpu_check and rank == 0:
             if world > 1:
                 host0 = full_host_vectors(op, n_total)
             if want_cpu_timing and world == 1:
@@ -739,9 +777,11 @@ def main():
         host0 = None
         if world > 1:
             dist.barrier()      # the other ranks wait for rank 0's CPU run
-        return o, keep
+        return o, keep, last
 
-    head, keep = leg(args.op, True)
+    head, keep, head_last = leg(args.op, True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head_last)
 
     def emit(secondary, blas23, host_api, extra=None):
         """rank 0: assemble and print THE JSON line from what has been measured"""
@@ -820,9 +860,9 @@ def main():
     secondary = None
     blas23 = None
     host_api = None
-    if not args.no_secondary and args.op == "exsum":
+    if args.full and not args.no_secondary and args.op == "exsum":
         # ExDOT on the same shape (BASELINE config 3), reported beside the headline number
-        secondary, _ = leg("exdot", False)
+        secondary, _, _ = leg("exdot", False)
         secondary["metric"] = "ExDOT fp64 Gelem/s"
         # BASELINE configs 4 and 5 on the same box (kernel-chain time by HIP events; parity is covered by tests/)
         if not args.skip_blas23:

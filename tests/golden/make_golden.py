@@ -2,12 +2,15 @@
 
 Run in the build container (needs /root/reference for `make -C oracle ref`):
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --ref-core     # ref_core_golden.npz + reftest_symbols.json only
 Every case stores DATA only: the raw little-endian float64 input, the 41 normalised limbs, the
 double under both rounding modes and the MPFR double.  Inputs come from the reference's own
 generators (src/common/common.cpp via oracle/_ref, glibc rand() seeded per case), from our
 counter-based generators, and from hand-picked edge values.
 """
+import json
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -91,5 +94,71 @@ def main():
     print("wrote", len(names), "exdot cases;", "exsum cases:", len(exsum_cases()))
 
 
+# the (fpe, early_exit) variants and thread counts tests/test_oracle.py runs the compiled core with
+REF_VARIANTS = [(0, False), (2, False), (3, False), (4, False), (8, False), (4, True), (6, True), (8, True)]
+REF_THREADS = (1, 3)
+REF_LOGNORMAL_SEEDS = {2.0: 5, 50.0: 6}
+REFTEST_OPS = ("exsum", "exdot", "exgemv", "exgemm", "extrsv")
+
+
+def ref_core():
+    """What the compiled reference core returns, for the tests that must also run where it cannot be built:
+    ill_cond(1e32) n = 2^12, seeds 1..40 from the reference's own generator (reproduced bit for bit by
+    O.gen_rand, whose output is pinned by `ill_cond_bits_xor`): limbs and Round() of every variant and thread count;
+    lognormal n = 2^20 from our counter-based generator (BASELINE config 1): limbs and Round() per variant.
+    And the C++ symbols the reference's GPU test programs (oracle/_ref/reftest_*) import from the library."""
+    assert O.ref() is not None, "needs oracle/_ref"
+    seeds = np.arange(1, 41)
+    ill_limbs, ill_round, ill_plain, ill_xor = [], [], [], []
+    for seed in seeds:
+        a = O.ref_gen("ill_cond", 1 << 12, int(seed), 1e32)
+        assert (a.view(np.int64) == O.gen_rand("ill_cond", 1 << 12, int(seed), 1e32).view(np.int64)).all()
+        ill_xor.append(np.bitwise_xor.reduce(a.view(np.int64)))
+        rows = []
+        for fpe, ee in REF_VARIANTS:
+            row = []
+            for nt in REF_THREADS:
+                r, l = O.ref_exsum(a, fpe, ee, nthreads=nt, limbs=True)
+                if not ill_limbs or len(ill_limbs) < seed:
+                    ill_limbs.append(l)
+                assert (l == ill_limbs[seed - 1]).all()
+                row.append(r)
+            rows.append(row)
+        ill_round.append(rows)
+        ill_plain.append(O.ref_exsum(a, 0))
+    ln_limbs, ln_round = [], []
+    for sd, seed in REF_LOGNORMAL_SEEDS.items():
+        a = O.gen("lognormal", 1 << 20, seed, 0.0, sd)
+        rows, l0 = [], None
+        for fpe, ee in REF_VARIANTS:
+            r, l = O.ref_exsum(a, fpe, ee, nthreads=4, limbs=True)
+            l0 = l if l0 is None else l0
+            assert (l == l0).all()
+            rows.append(r)
+        ln_limbs.append(l0)
+        ln_round.append(rows)
+    np.savez_compressed(os.path.join(HERE, "ref_core_golden.npz"), variants=np.array(REF_VARIANTS, dtype=np.int64),
+                        threads=np.array(REF_THREADS, dtype=np.int64), ill_cond_seeds=seeds,
+                        ill_cond_bits_xor=np.array(ill_xor, dtype=np.int64),
+                        ill_cond_limbs=np.array(ill_limbs, dtype=np.int64), ill_cond_round=np.array(ill_round),
+                        ill_cond_round_plain=np.array(ill_plain),
+                        lognormal_stddev=np.array(list(REF_LOGNORMAL_SEEDS)),
+                        lognormal_seed=np.array(list(REF_LOGNORMAL_SEEDS.values()), dtype=np.int64),
+                        lognormal_limbs=np.array(ln_limbs, dtype=np.int64), lognormal_round=np.array(ln_round))
+    syms = {}
+    for op in REFTEST_OPS:
+        exe = os.path.join(ROOT, "oracle", "_ref", f"reftest_{op}")
+        und = subprocess.run(["nm", "-D", "--undefined-only", exe], capture_output=True, text=True, check=True).stdout
+        und = sorted({ln.split()[-1] for ln in und.splitlines() if ln.strip()})
+        syms[op] = [s for s in und if s.startswith("_Z") and ("init_" in s or s.startswith(f"_Z{len(op)}{op}"))]
+    with open(os.path.join(HERE, "reftest_symbols.json"), "w") as fh:
+        json.dump(syms, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("wrote ref_core_golden.npz and reftest_symbols.json")
+
+
 if __name__ == "__main__":
-    main()
+    if "--ref-core" in sys.argv:
+        ref_core()
+    else:
+        main()

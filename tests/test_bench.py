@@ -52,7 +52,7 @@ def test_strong_scaling_bits_identical_across_rank_counts():
     limbs_crc for ExSUM and ExDOT, each checked against the CPU core on the FULL vector by rank 0, n_gpus = the ranks
     the communicator saw."""
     common = ["--log2n", "21", "--steps", "4", "--warmup", "1", "--prewarm-ms", "0", "--rotate", "2", "--no-host-api",
-              "--skip-blas23"]
+              "--skip-blas23", "--full"]
     lines = {}
     for n in (1, 2, 3):
         r = _run(["--gpus", str(n)] + common, {"EXBLAS_BENCH_BACKEND": "gloo"} if n > 1 else None)
@@ -80,9 +80,40 @@ def test_blas23_watchdog_keeps_the_headline():
     """N > 1: the BLAS2/3 items post collectives; if they do not finish in --blas23-timeout seconds rank 0 still prints the
     line (headline + ExDOT, bit checks included) and every rank leaves.  Forced here with a timeout no ExGEMV can meet."""
     r = _run(["--gpus", "2", "--log2n", "21", "--steps", "4", "--warmup", "1", "--prewarm-ms", "0", "--rotate", "2",
-              "--no-host-api", "--blas23-timeout", "0.05"], {"EXBLAS_BENCH_BACKEND": "gloo"})
+              "--no-host-api", "--blas23-timeout", "0.05", "--full"], {"EXBLAS_BENCH_BACKEND": "gloo"})
     js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(js) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
     ln = json.loads(js[0])
     assert ln["n_gpus"] == 2 and ln["bit_exact_vs_cpu"] is True and ln["exdot"]["bit_exact_vs_cpu"] is True
     assert ln["blas23_timed_out_after_s"] == 0.05 and "exgemm" not in ln
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps and reports the headline only (the --full items are absent);
+    --dump-outputs writes the record of the last timed step, which read rotating vector (warmup + steps - 1) mod --rotate
+    whatever the clock ramp-up ran: equal to the CPU core on that vector, and `result` to the CPU core on vector 0."""
+    import numpy as np
+    from oracle import pyoracle as O
+    steps, warmup, rotate, log2n = 8, 3, 3, 21
+    r = _run(["--gpus", "1", "--log2n", str(log2n), "--steps", str(steps), "--warmup", str(warmup), "--prewarm-ms", "50",
+              "--rotate", str(rotate), "--dump-outputs", str(tmp_path)])
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(js) == 1, r.stdout[-1500:]
+    ln = json.loads(js[0])
+    assert ln["steps"] == steps and ln["unit"] == "Gelem/s" and ln["higher_is_better"] is True and ln["dtype"] == "f64"
+    assert ln["ms_per_step"] > 0 and ln["value"] > 0 and ln["metric"].startswith("ExSUM fp64 Gelem/s")
+    for k in ("exdot", "exgemv", "exgemm", "extrsv", "host_api", "cpu_baseline", "bit_exact_vs_cpu"):
+        assert k not in ln, k
+    assert "same_buffer" not in ln["roofline"] and "measured_read_probe_GBs" not in ln["roofline"]
+    n = 1 << log2n
+    same = lambda a, b: np.float64(a).view(np.int64) == np.float64(b).view(np.int64)  # noqa: E731
+    r0 = O.exsum_omp(O.gen("ill_cond", n, 1, 1e32, 0.0), 8, True, 4)
+    assert same(ln["result"], r0)
+    want, limbs = O.exsum_omp(O.gen("ill_cond", n, 1 + 2 * ((warmup + steps - 1) % rotate), 1e32, 0.0), 8, True, 4, limbs=True)
+    res = np.load(tmp_path / "result.npy")
+    canon = np.load(tmp_path / "canon_limbs.npy")
+    assert res.dtype == np.float64 and canon.dtype == np.float64 and canon.shape == (41,)
+    assert same(res[0], want) and same(res[1], O.round_limbs(limbs, O.ROUND_REFERENCE))
+    assert (canon.astype(np.int64) == limbs).all()

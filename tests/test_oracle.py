@@ -70,9 +70,26 @@ def test_strided_and_offset(oracle):
 
 
 def test_compiled_reference_agrees(oracle):
-    """oracle == the reference's own compiled arithmetic core, limb for limb, for every variant."""
+    """oracle == the reference's own compiled arithmetic core, limb for limb, for every variant: against the core's
+    results recorded in tests/golden/ref_core_golden.npz (make_golden.py --ref-core; the inputs are the reference's
+    generator, which oracle.gen_rand restates bit for bit) and, where oracle/_ref is built, against the core itself."""
+    g = load_golden("ref_core_golden.npz")
+    variants = [(int(f), bool(e)) for f, e in g["variants"]]
+    assert variants == FPE_VARIANTS_SUM and len(g["ill_cond_seeds"]) == 40
+    ndiff = 0
+    for i, seed in enumerate(g["ill_cond_seeds"]):
+        a = oracle.gen_rand("ill_cond", 1 << 12, int(seed), 1e32)
+        assert np.bitwise_xor.reduce(a.view(np.int64)) == g["ill_cond_bits_xor"][i], seed
+        r0, l0 = oracle.exsum(a, 0, limbs=True)
+        assert (g["ill_cond_limbs"][i] == l0).all(), seed
+        for v, (fpe, ee) in enumerate(variants):
+            for t, nt in enumerate(g["threads"]):
+                assert same_double(g["ill_cond_round"][i, v, t], oracle.exsum(a, 0, mode=oracle.ROUND_REFERENCE)), \
+                    (seed, fpe, ee, nt)
+        ndiff += g["ill_cond_round_plain"][i] != r0
+    assert 0 < ndiff < 40
     if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+        return
     ndiff = 0
     for seed in range(1, 41):
         a = oracle.ref_gen("ill_cond", 1 << 12, seed, 1e32)
@@ -154,10 +171,30 @@ def test_gemv_gemm_oracle_vs_mpfr(oracle):
 def test_baseline_config1_plumbing(oracle):
     """BASELINE.json configs[0]: ExSUM n = 2^20 fp64 log-normal (the reference's CTest cases `20 2 0 n` and
     `20 50 0 n`, src/cpu/blas/blas1/CMakeLists.txt:28-35), CPU reference path vs MPFR -- no GPU involved.
-    Inputs come from the reference's own init_lognormal (std::random_device seeded, so every run is a new draw)."""
-    if oracle.ref() is None or oracle.mpfr() is None:
-        pytest.skip("needs oracle/_ref and libmpfr_oracle.so")
+    Recorded: the compiled core's limbs and Round() of every variant on fixed draws of our counter-based generator
+    (tests/golden/ref_core_golden.npz).  Live, where oracle/_ref is built: inputs from the reference's own
+    init_lognormal (std::random_device seeded, so every run is a new draw)."""
+    if oracle.mpfr() is None:
+        pytest.skip("libmpfr_oracle.so not built")
     n = 1 << 20
+    g = load_golden("ref_core_golden.npz")
+    variants = [(int(f), bool(e)) for f, e in g["variants"]]
+    assert variants == FPE_VARIANTS_SUM and sorted(g["lognormal_stddev"]) == [2.0, 50.0]
+    for j, (stddev, seed) in enumerate(zip(g["lognormal_stddev"], g["lognormal_seed"])):
+        a = oracle.gen("lognormal", n, int(seed), 0.0, float(stddev))
+        want = oracle.mpfr_exsum(a)
+        r0, l0 = oracle.exsum(a, 0, limbs=True)
+        assert same_double(r0, want)
+        lr = g["lognormal_limbs"][j]
+        assert (lr == l0).all(), stddev
+        assert same_double(oracle.round_limbs(lr), want)
+        for v, (fpe, ee) in enumerate(variants):
+            rr = g["lognormal_round"][j, v]
+            assert abs(rr - want) <= 1e-16 * abs(want) + 0.0 or abs(rr - want) / abs(want) <= 2.3e-16
+            r, l = oracle.exsum(a, fpe, ee, limbs=True)
+            assert (l == l0).all() and same_double(r, want), (stddev, fpe, ee)
+    if oracle.ref() is None:
+        return
     for stddev in (2.0, 50.0):
         a = oracle.ref_gen("lognormal", n, 0, 0.0, stddev)
         want = oracle.mpfr_exsum(a)

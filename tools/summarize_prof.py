@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Condense gpurun_out/{prof,pmc_fetch,pmc_write} (rocprofv3 CSV) into tracked files under profiles/.
+"""Condense $CI_OUT/{prof,pmc_fetch,pmc_write} (rocprofv3 CSV of tools/gpu_ci.sh; default ci_out/) into tracked files
+under profiles/.
 
 usage: tools/summarize_prof.py <round-tag>      e.g. r01
 Writes profiles/<tag>_kernel_stats.csv (the rocprofv3 --kernel-trace --stats summary, verbatim),
@@ -23,8 +24,8 @@ os.makedirs(out, exist_ok=True)
 
 
 def one(pattern):
-    g = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", pattern)), key=os.path.getmtime)
-    return g[-1] if g else None  # newest: gpurun merges every call's files into the same local directory
+    g = sorted(glob.glob(os.path.join(ROOT, os.environ.get("CI_OUT", "ci_out"), pattern)), key=os.path.getmtime)
+    return g[-1] if g else None  # newest: runs copied back from several boxes may share the directory
 
 
 ks = one("prof/*/*_kernel_stats.csv")
