@@ -42,6 +42,8 @@ C_ABI_SYMBOLS = [
     "exblas_ctx_create", "exblas_ctx_destroy", "exblas_exsum_ctx", "exblas_exdot_ctx", "exblas_exsum_accumulate_ctx",
     "exblas_exdot_accumulate_ctx", "exblas_finish_ctx", "exblas_exgemv_ctx", "exblas_extrsv_ctx", "exblas_exgemm_ctx",
     "exblas_reserve_workspace_ctx", "exblas_workspace_bytes_ctx", "exblas_last_gemm_info_ctx",
+    "exblas_exspmv_csr_dev", "exblas_exspmv_csr_ctx", "exblas_exspmv_csr", "exblas_set_spmv_path",
+    "exblas_last_spmv_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -161,6 +163,12 @@ def load_library():
                                             i32, vp]
     L.exblas_exgemm_sharded_dev.argtypes = [vp, C.c_char, C.c_char, i32, i32, i32, dbl, vp, i32, vp, i32, i32, dbl,
                                             vp, i32, i32, i32, i32, vp]
+    L.exblas_exspmv_csr_dev.argtypes = [i32, i32, i32, vp, vp, vp, dbl, vp, dbl, vp, i32, i32, vp]
+    L.exblas_exspmv_csr_ctx.argtypes = [vp] + L.exblas_exspmv_csr_dev.argtypes
+    L.exblas_exspmv_csr.argtypes = [i32, i32, i32, vp, vp, vp, dbl, vp, dbl, vp, i32, i32]
+    L.exblas_set_spmv_path.argtypes = [i32]
+    L.exblas_set_spmv_path.restype = None
+    L.exblas_last_spmv_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -332,6 +340,86 @@ def exgemm_dev(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe
     return c
 
 
+def _csr_parts(A):
+    """(crow, col, val, (m, n)) of a torch.sparse_csr_tensor or of a (crow, col, val, shape) tuple."""
+    if isinstance(A, (tuple, list)):
+        if len(A) != 4:
+            raise ValueError("exspmv: A must be a sparse CSR tensor or a (crow, col, val, shape) tuple")
+        crow, col, val, shape = A
+    else:
+        torch = _torch()
+        if getattr(A, "layout", None) != torch.sparse_csr:
+            raise TypeError("exspmv: A must be a torch.sparse_csr_tensor or a (crow, col, val, shape) tuple")
+        crow, col, val, shape = A.crow_indices(), A.col_indices(), A.values(), tuple(A.shape)
+    if len(shape) != 2:
+        raise ValueError(f"exspmv: A must be 2-D, got shape {tuple(shape)}")
+    m, n = int(shape[0]), int(shape[1])
+    if m < 0 or n < 0 or m > 0x7fffffff or n > 0x7fffffff:
+        raise ValueError(f"exspmv: unsupported shape {tuple(shape)}")
+    return crow, col, val, m, n
+
+
+def _spmv_check(A, x, y):
+    """Validates a device ExSpMV call before anything is launched; returns (crow, col, val, m, n, index_bits, y)."""
+    torch = _torch()
+    crow, col, val, m, n = _csr_parts(A)
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"exspmv: {name} must be a torch tensor")
+    if val.dtype != torch.float64 or x.dtype != torch.float64:
+        raise TypeError("exspmv: values and x must be float64")
+    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
+        raise TypeError("exspmv: row pointers and column indices must both be int32 or both int64")
+    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1 or x.dim() != 1:
+        raise ValueError("exspmv: crow, col, val and x must be 1-D")
+    if crow.numel() != m + 1:
+        raise ValueError(f"exspmv: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
+    if col.numel() != val.numel():
+        raise ValueError("exspmv: col and val differ in length")
+    if x.numel() < n:
+        raise ValueError(f"exspmv: x has {x.numel()} entries, fewer than n = {n}")
+    if y is not None:
+        if not isinstance(y, torch.Tensor) or y.dtype != torch.float64 or y.dim() != 1 or y.numel() != m:
+            raise ValueError(f"exspmv: y must be a 1-D float64 tensor of m = {m} entries")
+        if not y.is_contiguous():
+            raise ValueError("exspmv: y must be contiguous")
+    _require_gpu()
+    dev = val.device
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)) + ((("y", y),) if y is not None else ()):
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"exspmv: {name} must be on the GPU, on the device of the values")
+    crow, col, val, x = crow.contiguous(), col.contiguous(), val.contiguous(), x.contiguous()
+    if y is None:
+        y = torch.zeros(m, dtype=torch.float64, device=dev)
+    return crow, col, val, x, m, n, (32 if crow.dtype == torch.int32 else 64), y
+
+
+def exspmv_dev(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+    """ExSpMV: y = Round(alpha A x + beta y) row by row, exact and reproducible, stream-ordered on the current stream.
+    A: torch.sparse_csr_tensor (float64 values, int32 or int64 indices) or (crow, col, val, (m, n)) on the GPU; x a
+    float64 vector of at least n entries; y (m entries) is updated in place, or allocated (zeros) when None."""
+    torch = _torch()
+    crow, col, val, x, m, n, bits, y = _spmv_check(A, x, y)
+    _check(load_library().exblas_exspmv_csr_dev(m, n, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()),
+                                                C.c_void_p(val.data_ptr()), float(alpha), C.c_void_p(x.data_ptr()),
+                                                float(beta), C.c_void_p(y.data_ptr()), int(fpe), int(bool(early_exit)),
+                                                _stream_ptr(torch)), "exspmv_dev")
+    return y
+
+
+def set_spmv_path(mode):
+    """Test hook: 0 automatic, 1 accumulator finish for every row, 2 in-register rounding wherever certified (no row
+    split), 3 every row split at a small chunk.  Same bits on every path."""
+    load_library().exblas_set_spmv_path(int(mode))
+
+
+def last_spmv_info():
+    """(rows rounded in registers, rows rounded from their accumulator, rows split, chunks) of the last ExSpMV."""
+    out = (C.c_int64 * 4)()
+    _check(load_library().exblas_last_spmv_info(out), "last_spmv_info")
+    return tuple(int(v) for v in out)
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Methods mirror the ``*_dev``
@@ -409,6 +497,16 @@ class Context:
         if rc != -1:
             _check(rc, "extrsv_ctx")
         return rc
+
+    def exspmv(self, A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+        torch = _torch()
+        crow, col, val, x, m, n, bits, y = _spmv_check(A, x, y)
+        _check(load_library().exblas_exspmv_csr_ctx(self.handle, m, n, bits, C.c_void_p(crow.data_ptr()),
+                                                    C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
+                                                    float(alpha), C.c_void_p(x.data_ptr()), float(beta),
+                                                    C.c_void_p(y.data_ptr()), int(fpe), int(bool(early_exit)),
+                                                    _stream_ptr(torch)), "exspmv_ctx")
+        return y
 
     def workspace_bytes(self):
         return load_library().exblas_workspace_bytes_ctx(self.handle)
@@ -514,6 +612,38 @@ def exgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe, ea
     return load_library().exblas_exgemm(transa.encode(), transb.encode(), m, n, k, alpha, C.c_void_p(a_.ctypes.data),
                                         lda, C.c_void_p(b_.ctypes.data), ldb, beta, C.c_void_p(c.ctypes.data), ldc,
                                         fpe, int(bool(early_exit)))
+
+
+def exspmv(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+    """ExSpMV on host arrays: A = (row_ptr, col_idx, val, (m, n)) as numpy arrays (int32 or int64 indices of one width,
+    float64 values), x float64 of at least n entries; returns y (a new float64 array; the y passed in is not changed)."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError("exspmv: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
+    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
+    if len(shape) != 2:
+        raise ValueError("exspmv: shape must be (m, n)")
+    m, n = int(shape[0]), int(shape[1])
+    x = np.asarray(x)
+    if val.dtype != np.float64 or x.dtype != np.float64:
+        raise TypeError("exspmv: values and x must be float64")
+    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
+        raise TypeError("exspmv: row pointers and column indices must both be int32 or both int64")
+    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or x.ndim != 1:
+        raise ValueError("exspmv: row_ptr, col_idx, val and x must be 1-D")
+    if crow.size != m + 1 or col.size != val.size or x.size < n:
+        raise ValueError("exspmv: inconsistent sizes of row_ptr / col_idx / val / x")
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError("exspmv: row_ptr entries must lie in [0, nnz]")
+    y = np.zeros(m) if y is None else np.array(y, dtype=np.float64, copy=True)
+    if y.ndim != 1 or y.size != m:
+        raise ValueError(f"exspmv: y must have m = {m} entries")
+    _require_gpu()
+    crow, col, val, x = (np.ascontiguousarray(a) for a in (crow, col, val, x))
+    bits = 32 if crow.dtype == np.int32 else 64
+    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    _check(load_library().exblas_exspmv_csr(m, n, bits, p(crow), p(col), p(val), float(alpha), p(x), float(beta),
+                                            p(y), int(fpe), int(bool(early_exit))), "exspmv")
+    return y
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

@@ -37,6 +37,9 @@ struct Ctx {
     int gemm_max_slices = 0; // 0 = default (16): digits per operand the int8 path reserves workspace for
     int gemm_max_moduli = 0; // 0 = default (39): moduli the residue path reserves workspace for
     int gemm_ws_moduli = 0;  // moduli the last residue-path call actually reserved for (fewer after an out-of-memory retry)
+    int spmv_path = 0;       // exblas_set_spmv_path: 0 automatic, 1 accumulator finish for every row, 2 in-register
+                             // rounding wherever certified (no row split), 3 every row split at a small chunk
+    const long long *spmv_info_dev = nullptr;  // header of the last ExSpMV call's workspace (exblas_last_spmv_info)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -98,6 +101,11 @@ hipError_t exgemv_dispatch(Ctx &c, char transa, int m, int n, double alpha, cons
 hipError_t exgemm_dispatch(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a,
                            int lda, const double *b, int ldb, double beta, double *cmat, int ldc, int fpe,
                            int early_exit, int round_mode, hipStream_t st, const GemmChunks *chunks = nullptr);
+
+// spmv.hip
+hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
+                           const double *val, double alpha, const double *x, double beta, double *y, int fpe,
+                           int early_exit, int round_mode, hipStream_t st);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

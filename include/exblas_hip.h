@@ -206,6 +206,31 @@ int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_
  * (superaccumulator) path instead of the register expansion -- near-ties, heavy cancellation, huge/tiny/non-finite
  * values.  Synchronises the device; valid until the next exgemv/exgemm/extrsv call; -1 when unknown. */
 int exblas_extrsv_last_slow_rows(void);
+/* ExSpMV: exact, reproducible y = alpha A x + beta y for an m x n CSR matrix A on device pointers.  row_ptr[m+1] and
+ * col_idx[nnz] are int32 (index_bits 32) or int64 (64), both the same width; val, x, y contiguous fp64.  Row i, with its
+ * stored entries p in [row_ptr[i], row_ptr[i+1]), is exactly what ExGEMV 'N' computes for the 1 x k_i matrix of those
+ * values against the gathered x:
+ *     y_i = Round( sum_p val[p] * fl(alpha * x[col_idx[p]])  (+)  beta * y_i )
+ * in both rounding modes (exblas_set_round_mode), with ExGEMV's rules: alpha is folded into x by a rounded multiply;
+ * beta = 0 ignores y (NaN included), beta = 1 adds y exactly, any other beta adds the error-free product; ExGEMV's
+ * product domain and non-finite rules.  The order of a row's entries does not matter and duplicate columns each
+ * count; an empty row (or row_ptr[i+1] <= row_ptr[i]) gives Round(0 (+) beta y_i), +0.0 for beta = 0.  A column index
+ * outside [0, n) is never dereferenced: that row's result is NaN.  row_ptr entries must lie in [0, nnz].  The bits do
+ * not depend on fpe (>= 2, or 0), early_exit, the internal path, the grid, the index width or the row order.  fpe == 1
+ * is the plain, non-reproducible fp64 CSR SpMV.  Stream-ordered launches only (classification on the device, the
+ * context workspace): capturable into a hipGraph after exblas_reserve_workspace or one call of the same m.
+ * Returns 0 or a hipError_t; invalid m, n, index_bits or fpe < 0 give hipErrorInvalidValue. */
+int exblas_exspmv_csr_dev(int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                          const double *d_val, double alpha, const double *d_x, double beta, double *d_y, int fpe,
+                          int early_exit, void *stream);
+/* Test hook for ExSpMV (same bits on every path): 0 automatic, 1 every row rounded from its integer accumulator,
+ * 2 rows rounded in registers wherever the rounding test certifies it (no row is split), 3 every row split into
+ * chunks of 16 entries across waves. */
+void exblas_set_spmv_path(int mode);
+/* The most recent ExSpMV on this device: out[0] rows rounded in registers, out[1] rows rounded from their integer
+ * accumulator (fallback), out[2] rows split across workgroups, out[3] chunks of those rows (all 0 for fpe == 1).
+ * Synchronises the device; valid until the next call that uses the workspace; -1 when unknown. */
+int exblas_last_spmv_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -251,6 +276,9 @@ int exblas_extrsv_ctx(exblas_ctx_t *ctx, char uplo, char transa, char diag, int 
 int exblas_exgemm_ctx(exblas_ctx_t *ctx, char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc,
                       int fpe, int early_exit, void *stream);
+int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const void *d_row_ptr,
+                          const void *d_col_idx, const double *d_val, double alpha, const double *d_x, double beta,
+                          double *d_y, int fpe, int early_exit, void *stream);
 int exblas_reserve_workspace_ctx(exblas_ctx_t *ctx, size_t bytes);
 size_t exblas_workspace_bytes_ctx(exblas_ctx_t *ctx);
 int exblas_last_gemm_info_ctx(exblas_ctx_t *ctx, int *out8);
@@ -369,6 +397,10 @@ int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a,
                   int lda, const double *b, int ldb, double beta, double *c, int ldc, int fpe,
                   int early_exit);
+/* exblas_exspmv_csr_dev on host arrays (row_ptr, col_idx, val, x, y; y updated in place): staged through the device,
+ * synchronous.  Returns 0 or hipErrorInvalidValue (also for a negative row_ptr entry). */
+int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                      double alpha, const double *x, double beta, double *y, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
