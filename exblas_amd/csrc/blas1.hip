@@ -24,6 +24,7 @@ namespace exb {
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
+constexpr int U = 4;   // double2 loads per lane and stream in one tile of k_exsum / k_exdot
 
 // blas1 sinks everything into the wave's LDS accumulator column
 template <int N, bool EE, int COPIES, int CNT, int ZM = 0>
@@ -66,10 +67,10 @@ __device__ __forceinline__ void block_epilogue(long long *s_acc, unsigned flags,
 // ---------------------------------------------------------------------------------------------
 // ExSUM, contiguous input
 // ---------------------------------------------------------------------------------------------
-template <int N, bool EE, int COPIES, int U, bool NT, bool PF, int ZM = 0>
+template <int N, bool EE, int COPIES>
 __global__ void __launch_bounds__(BLOCK) k_exsum(const double *__restrict__ a, long long n,
                                                  long long *__restrict__ gacc,
-                                                 unsigned *__restrict__ gflags, int ngroups, int chunked)
+                                                 unsigned *__restrict__ gflags, int ngroups)
 {
     __shared__ long long s_acc[WAVES * NL * COPIES];
     auto zero_lds = [&]() {   // (after the first tile's loads are in flight, see k_exdot)
@@ -92,65 +93,41 @@ __global__ void __launch_bounds__(BLOCK) k_exsum(const double *__restrict__ a, l
     LdsSink<COPIES> sinkm{col, flags};
     Bypass bypass;
 
-    if constexpr (!PF) {
-        zero_lds();
-        for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-            const d2_t *p = v + t * TILE + threadIdx.x;
-            d2_t r[U];
+    // register double-buffering: the next tile's loads are in flight while this one is absorbed.  Tile t goes to
+    // workgroup t mod grid: the grid sweeps one compact window of addresses.
+    long long t = blockIdx.x;
+    if (t < ntiles) {
+        // two explicit register sets, filled alternately with unconditional loads (past the end: the last tile
+        // again) -- see k_exdot: no per-trip copies between the sets, both in flight
+        d2_t r0[U], r1[U];
+        auto fill = [&](long long tile, d2_t (&r)[U]) {
+            const d2_t *p = v + (tile < ntiles ? tile : ntiles - 1) * TILE + threadIdx.x;
 #pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = ld2<NT>(p + u * BLOCK);
+            for (int u = 0; u < U; ++u) r[u] = ld2(p + u * BLOCK);
+        };
+        auto absorb = [&](d2_t (&r)[U]) {
             double x[2 * U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 x[2 * u] = r[u].x;
                 x[2 * u + 1] = r[u].y;
             }
-            fpe_absorb_adaptive<N, EE, 2 * U, LdsSink<COPIES>, ZM>(fpe, x, sinkm, bypass);
+            fpe_absorb_adaptive<N, EE, 2 * U, LdsSink<COPIES>>(fpe, x, sinkm, bypass);
+        };
+        fill(t, r0);
+        zero_lds();
+        for (;;) {
+            fill(t + gridDim.x, r1);
+            absorb(r0);
+            t += gridDim.x;
+            if (t >= ntiles) break;
+            fill(t + gridDim.x, r0);
+            absorb(r1);
+            t += gridDim.x;
+            if (t >= ntiles) break;
         }
     } else {
-        // register double-buffering: the next tile's loads are in flight while this one is absorbed.
-        // Tile -> workgroup map: strided (tile t to workgroup t mod grid: the grid sweeps one compact window
-        // of addresses) or chunked (each workgroup streams its own contiguous range).
-        long long t = blockIdx.x, tstride = gridDim.x, tend = ntiles;
-        if (chunked) {
-            const long long per = (ntiles + gridDim.x - 1) / gridDim.x;
-            t = blockIdx.x * per;
-            tstride = 1;
-            tend = min(ntiles, t + per);
-        }
-        if (t < tend) {
-            // two explicit register sets, filled alternately with unconditional loads (past the end: the last tile
-            // again) -- see k_exdot: no per-trip copies between the sets, both in flight
-            d2_t r0[U], r1[U];
-            auto fill = [&](long long tile, d2_t (&r)[U]) {
-                const d2_t *p = v + (tile < tend ? tile : tend - 1) * TILE + threadIdx.x;
-#pragma unroll
-                for (int u = 0; u < U; ++u) r[u] = ld2<NT>(p + u * BLOCK);
-            };
-            auto absorb = [&](d2_t (&r)[U]) {
-                double x[2 * U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    x[2 * u] = r[u].x;
-                    x[2 * u + 1] = r[u].y;
-                }
-                fpe_absorb_adaptive<N, EE, 2 * U, LdsSink<COPIES>, ZM>(fpe, x, sinkm, bypass);
-            };
-            fill(t, r0);
-            zero_lds();
-            for (;;) {
-                fill(t + tstride, r1);
-                absorb(r0);
-                t += tstride;
-                if (t >= tend) break;
-                fill(t + tstride, r0);
-                absorb(r1);
-                t += tstride;
-                if (t >= tend) break;
-            }
-        } else {
-            zero_lds();
-        }
+        zero_lds();
     }
     // remainder vectors, grid-strided one double2 at a time
     for (long long i = ntiles * TILE + (long long)blockIdx.x * BLOCK + threadIdx.x; i < nv;
@@ -199,8 +176,8 @@ __global__ void __launch_bounds__(BLOCK) k_exsum_strided(const double *__restric
 // ExDOT: TwoProductFMA front-end (ExDOT.Superacc.cl:25-29, :244-253); the rounding error of the
 // product enters the expansion at slot max(N-3,0) like ExDOT.FPE.cl:254
 // ---------------------------------------------------------------------------------------------
-template <int N, bool EE, int COPIES, int U, bool NT, bool PF, int WPS = 1, bool HALVES = false, int ZM = 0>
-__global__ void __launch_bounds__(BLOCK, WPS) k_exdot(const double *__restrict__ a, const double *__restrict__ b,
+template <int N, bool EE, int COPIES, int ZM>
+__global__ void __launch_bounds__(BLOCK) k_exdot(const double *__restrict__ a, const double *__restrict__ b,
                                                  long long n, long long *__restrict__ gacc,
                                                  unsigned *__restrict__ gflags, int ngroups)
 {
@@ -226,100 +203,50 @@ __global__ void __launch_bounds__(BLOCK, WPS) k_exdot(const double *__restrict__
     Bypass bypass;
     constexpr long long TILE = (long long)BLOCK * U;
     const long long ntiles = nv / TILE;
-    if constexpr (!PF) {
-        zero_lds();
-        for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-            const long long base = t * TILE + threadIdx.x;
-            d2_t ra[U], rb[U];
+    long long t = blockIdx.x;
+    d2_t ra[U], rb[U];
+    if (t < ntiles) {
+        const long long base = t * TILE + threadIdx.x;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ra[u] = ld2(va + base + u * BLOCK);
+            rb[u] = ld2(vb + base + u * BLOCK);
+        }
+    }
+    zero_lds();
+    if (t < ntiles) {
+        // Two explicit register sets, filled alternately; the loads are unconditional (past the end they
+        // fetch the last tile again), so the compiler has no reason to copy one set into the other each
+        // trip (16 v_mov_b64 per tile with a conditional reload) and both sets stay in flight.
+        d2_t rc[U], rd[U];
+        auto fill = [&](long long tile, d2_t (&pa)[U], d2_t (&pb)[U]) {
+            const long long base = (tile < ntiles ? tile : ntiles - 1) * TILE + threadIdx.x;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                ra[u] = ld2<NT>(va + base + u * BLOCK);
-                rb[u] = ld2<NT>(vb + base + u * BLOCK);
+                pa[u] = ld2(va + base + u * BLOCK);
+                pb[u] = ld2(vb + base + u * BLOCK);
             }
+        };
+        auto absorb = [&](d2_t (&pa)[U], d2_t (&pb)[U]) {
             double x[2 * U], e[2 * U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                x[2 * u] = two_prod(ra[u].x, rb[u].x, e[2 * u]);
-                x[2 * u + 1] = two_prod(ra[u].y, rb[u].y, e[2 * u + 1]);
+                x[2 * u] = two_prod(pa[u].x, pb[u].x, e[2 * u]);
+                x[2 * u + 1] = two_prod(pa[u].y, pb[u].y, e[2 * u + 1]);
             }
-            if (!prod_range_divert<2 * U>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j & 1 ? ra[j >> 1].y : ra[j >> 1].x; },
-                                              [&](int j) { return j & 1 ? rb[j >> 1].y : rb[j >> 1].x; }))
-                fpe_absorb_prod_adaptive<N, EE, 2 * U, LdsSink<COPIES>, 0, false>(fpe, x, e, sink, bypass);
-        }
-    } else {
-        long long t = blockIdx.x;
-        d2_t ra[U], rb[U];
-        if (t < ntiles) {
-            const long long base = t * TILE + threadIdx.x;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ra[u] = ld2<NT>(va + base + u * BLOCK);
-                rb[u] = ld2<NT>(vb + base + u * BLOCK);
-            }
-        }
-        zero_lds();
-        if constexpr (HALVES) {
-            while (t < ntiles) {
-                const long long tn = t + gridDim.x;
-                // two half-tiles: the registers of a half are re-loaded (next tile) as soon as its products are
-                // formed, so only U products + U errors are live at a time (fewer VGPRs -> more waves per SIMD)
-                constexpr int H = U / 2;
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    double x[2 * H], e[2 * H];
-#pragma unroll
-                    for (int u = 0; u < H; ++u) {
-                        x[2 * u] = two_prod(ra[h * H + u].x, rb[h * H + u].x, e[2 * u]);
-                        x[2 * u + 1] = two_prod(ra[h * H + u].y, rb[h * H + u].y, e[2 * u + 1]);
-                    }
-                    const bool diverted = prod_range_divert<2 * H>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j & 1 ? ra[h * H + (j >> 1)].y : ra[h * H + (j >> 1)].x; },
-                        [&](int j) { return j & 1 ? rb[h * H + (j >> 1)].y : rb[h * H + (j >> 1)].x; });
-                    if (tn < ntiles) {
-                        const long long base = tn * TILE + threadIdx.x;
-#pragma unroll
-                        for (int u = 0; u < H; ++u) {
-                            ra[h * H + u] = ld2<NT>(va + base + (h * H + u) * BLOCK);
-                            rb[h * H + u] = ld2<NT>(vb + base + (h * H + u) * BLOCK);
-                        }
-                    }
-                    if (!diverted) fpe_absorb_prod_adaptive<N, EE, 2 * H, LdsSink<COPIES>, 0, false>(fpe, x, e, sink, bypass);
-                }
-                t = tn;
-            }
-        } else if (t < ntiles) {
-            // Two explicit register sets, filled alternately; the loads are unconditional (past the end they
-            // fetch the last tile again), so the compiler has no reason to copy one set into the other each
-            // trip (16 v_mov_b64 per tile with a conditional reload) and both sets stay in flight.
-            d2_t rc[U], rd[U];
-            auto fill = [&](long long tile, d2_t (&pa)[U], d2_t (&pb)[U]) {
-                const long long base = (tile < ntiles ? tile : ntiles - 1) * TILE + threadIdx.x;
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    pa[u] = ld2<NT>(va + base + u * BLOCK);
-                    pb[u] = ld2<NT>(vb + base + u * BLOCK);
-                }
-            };
-            auto absorb = [&](d2_t (&pa)[U], d2_t (&pb)[U]) {
-                double x[2 * U], e[2 * U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    x[2 * u] = two_prod(pa[u].x, pb[u].x, e[2 * u]);
-                    x[2 * u + 1] = two_prod(pa[u].y, pb[u].y, e[2 * u + 1]);
-                }
-                if (!prod_range_divert<2 * U>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j & 1 ? pa[j >> 1].y : pa[j >> 1].x; },
-                                                  [&](int j) { return j & 1 ? pb[j >> 1].y : pb[j >> 1].x; }))
-                    fpe_absorb_prod_adaptive<N, EE, 2 * U, LdsSink<COPIES>, ZM, false>(fpe, x, e, sink, bypass);
-            };
-            for (;;) {
-                fill(t + gridDim.x, rc, rd);
-                absorb(ra, rb);
-                t += gridDim.x;
-                if (t >= ntiles) break;
-                fill(t + gridDim.x, ra, rb);
-                absorb(rc, rd);
-                t += gridDim.x;
-                if (t >= ntiles) break;
-            }
+            if (!prod_range_divert<2 * U>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j & 1 ? pa[j >> 1].y : pa[j >> 1].x; },
+                                              [&](int j) { return j & 1 ? pb[j >> 1].y : pb[j >> 1].x; }))
+                fpe_absorb_prod_adaptive<N, EE, 2 * U, LdsSink<COPIES>, ZM, false>(fpe, x, e, sink, bypass);
+        };
+        for (;;) {
+            fill(t + gridDim.x, rc, rd);
+            absorb(ra, rb);
+            t += gridDim.x;
+            if (t >= ntiles) break;
+            fill(t + gridDim.x, ra, rb);
+            absorb(rc, rd);
+            t += gridDim.x;
+            if (t >= ntiles) break;
         }
     }
     for (long long i = ntiles * TILE + (long long)blockIdx.x * BLOCK + threadIdx.x; i < nv;
@@ -593,7 +520,7 @@ static inline int grid_for(const Ctx &c, long long work_items, long long per_blo
     return (int)want;
 }
 
-template <int N, bool EE, int COPIES, int U, bool NT, bool PF, int ZM = 0>
+template <int N, bool EE, int COPIES>
 static void run_exsum(Ctx &c, const double *a, long long n, hipStream_t st)
 {
     // resident blocks per CU: the HBM-bound kernels want few fat blocks; the variants that run the full N-level cascade
@@ -604,8 +531,7 @@ static void run_exsum(Ctx &c, const double *a, long long n, hipStream_t st)
     // an odd number of workgroups (one resident slot left idle): the tiles a workgroup has in flight are grid x 16 KiB
     // apart, and with an even grid they compete for the same HBM channels -- 865 against 855 Gelem/s at n = 2^28
     if (grid == c.num_cu * bpc && grid > 1 && !(grid & 1)) grid -= 1;
-    EXB_LAUNCH_STREAMING(c, (k_exsum<N, EE, COPIES, U, NT, PF, ZM>), grid, st, a, n, c.gacc, c.gflags, c.ngroups,
-                         c.variant == 9 ? 1 : 0);
+    EXB_LAUNCH_STREAMING(c, (k_exsum<N, EE, COPIES>), grid, st, a, n, c.gacc, c.gflags, c.ngroups);
 }
 
 #ifndef EXBLAS_SUM_COPIES
@@ -619,22 +545,7 @@ static hipError_t launch_exsum(Ctx &c, const double *a, long long n, long long i
 {
     constexpr int COPIES = (N == 0) ? 16 : EXBLAS_SUM_COPIES;
     if (inca == 1) {
-        if constexpr (N == 8 && EE) {
-            // tuning variants of the production kernel, selected with exblas_set_tuning() for A/B runs
-            switch (c.variant) {
-            case 1: run_exsum<N, EE, COPIES, 4, true, false>(c, a, n, st); break;
-            case 2: run_exsum<N, EE, COPIES, 8, true, false>(c, a, n, st); break;
-            case 3: run_exsum<N, EE, COPIES, 2, true, true>(c, a, n, st); break;
-            case 4: run_exsum<N, EE, COPIES, 4, false, true>(c, a, n, st); break;
-            case 5: run_exsum<N, EE, COPIES, 2, true, false>(c, a, n, st); break;
-            case 6: run_exsum<N, EE, COPIES, 8, true, true>(c, a, n, st); break;
-            case 7: run_exsum<N, EE, COPIES, 6, true, true>(c, a, n, st); break;
-            case 8: run_exsum<N, EE, COPIES, 4, true, true, 1>(c, a, n, st); break;
-            default: run_exsum<N, EE, COPIES, 4, true, true>(c, a, n, st); break;
-            }
-        } else {
-            run_exsum<N, EE, COPIES, 4, true, true>(c, a, n, st);
-        }
+        run_exsum<N, EE, COPIES>(c, a, n, st);
     } else {
         int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
         EXB_LAUNCH_STREAMING(c, (k_exsum_strided<N, EE, COPIES>), grid, st, a, n, inca, c.gacc, c.gflags, c.ngroups);
@@ -642,7 +553,7 @@ static hipError_t launch_exsum(Ctx &c, const double *a, long long n, long long i
     return hipGetLastError();
 }
 
-template <int N, bool EE, int COPIES, int U, bool NT, bool PF, int WPS = 1, bool HALVES = false, int ZM = 0>
+template <int N, bool EE, int COPIES>
 static void run_exdot(Ctx &c, const double *a, const double *b, long long n, hipStream_t st)
 {
     // Workgroups per CU: 48 at n = 2^28 (placement probe, round 2), but a workgroup should stream about five tiles or
@@ -658,7 +569,9 @@ static void run_exdot(Ctx &c, const double *a, const double *b, long long n, hip
     // (b - a = 16 KiB mod 32 KiB) to 0.667 ms (0 mod 32 KiB); odd: 0.625-0.635 ms for every placement
     // (tools/dot_align.py, profiles/r02_exdot_placement.log).
     if (grid > c.num_cu && !(grid & 1)) grid += 1;
-    EXB_LAUNCH_STREAMING(c, (k_exdot<N, EE, COPIES, U, NT, PF, WPS, HALVES, ZM>), grid, st, a, b, n, c.gacc, c.gflags,
+    // early-exit votes by one fp64 compare per residue (ZM = 1): median 0.658 ms against 0.699 by integer ORs at
+    // n = 2^28 (tools/tune.py, same box)
+    EXB_LAUNCH_STREAMING(c, (k_exdot<N, EE, COPIES, SKIP_ZERO_LEVELS<EE> ? 1 : 0>), grid, st, a, b, n, c.gacc, c.gflags,
                          c.ngroups);
 }
 
@@ -669,24 +582,7 @@ static hipError_t launch_exdot(Ctx &c, const double *a, long long inca, const do
     constexpr int COPIES = (N == 0) ? 16 : EXBLAS_DOT_COPIES;
     const bool vec = inca == 1 && incb == 1 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
     if (vec) {
-        if constexpr (N == 8 && EE) {
-            switch (c.variant) {
-            case 1: run_exdot<N, EE, COPIES, 2, true, false>(c, a, b, n, st); break;
-            case 2: run_exdot<N, EE, COPIES, 4, true, false>(c, a, b, n, st); break;
-            case 3: run_exdot<N, EE, COPIES, 1, true, true>(c, a, b, n, st); break;
-            case 4: run_exdot<N, EE, COPIES, 2, false, true>(c, a, b, n, st); break;
-            case 5: run_exdot<N, EE, COPIES, 1, true, false>(c, a, b, n, st); break;
-            case 6: run_exdot<N, EE, COPIES, 2, true, true>(c, a, b, n, st); break;
-            case 7: run_exdot<N, EE, COPIES, 3, true, true>(c, a, b, n, st); break;
-            case 8: run_exdot<N, EE, COPIES, 4, true, true, 1, true>(c, a, b, n, st); break;
-            case 9: run_exdot<N, EE, COPIES, 8, true, true, 1, true>(c, a, b, n, st); break;
-            case 10: run_exdot<N, EE, COPIES, 4, true, true>(c, a, b, n, st); break;  // votes by integer ORs (round 1)
-            // early-exit votes by one fp64 compare per residue: median 0.658 ms against 0.699 (tools/tune.py, same box)
-            default: run_exdot<N, EE, COPIES, 4, true, true, 1, false, 1>(c, a, b, n, st); break;
-            }
-        } else {
-            run_exdot<N, EE, COPIES, 4, true, true, 1, false, SKIP_ZERO_LEVELS<EE> ? 1 : 0>(c, a, b, n, st);
-        }
+        run_exdot<N, EE, COPIES>(c, a, b, n, st);
     } else {
         int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
         EXB_LAUNCH_STREAMING(c, (k_exdot_strided<N, EE, COPIES>), grid, st, a, inca, b, incb, n, c.gacc, c.gflags,

@@ -17,10 +17,6 @@
 
 #include <algorithm>
 
-// tools/ only: a device buffer of 2 x (workgroups x 4) uint64 that k_gemvN_fpe_sx fills with per-wave start / end clocks
-// (100 MHz wall clock); nullptr (the default) = off.  Not part of the C ABI (not declared in include/).
-extern "C" void *exblas_debug_timeline = nullptr;
-
 namespace exb {
 
 constexpr int GV_BLOCK = 256;
@@ -29,14 +25,16 @@ constexpr int GV_KC = 1024;  // columns of x staged in LDS at a time (8 KiB)
 constexpr int GV_TICKET_STRIDE = 4096 + 256;  // bytes between two ticket counters of k_gemvN_fpe_sx
 
 // ---------------------------------------------------------------------------------------------
-// 'N', expansion path: two rows per lane
+// 'N', expansion path: two rows per lane, x staged in LDS.  For the matrices k_gemvN_fpe_sx cannot stream with 16-byte
+// loads (odd m or lda, or a misaligned A).
 // ---------------------------------------------------------------------------------------------
-template <int N, bool EE, bool VEC, int U = 4>
+template <int N, bool EE>
 __global__ void __launch_bounds__(GV_BLOCK) k_gemvN_fpe(int m, int n, double alpha, const double *__restrict__ a,
                                                         long long lda, const double *__restrict__ x, long long incx,
                                                         int kper, double *__restrict__ part,
                                                         long long *__restrict__ ws)
 {
+    constexpr int U = 4;   // columns per step
     __shared__ double xs[GV_KC];
     const int tid = threadIdx.x;
     const long long r0 = ((long long)blockIdx.x * GV_BLOCK + tid) * 2;
@@ -60,14 +58,8 @@ __global__ void __launch_bounds__(GV_BLOCK) k_gemvN_fpe(int m, int n, double alp
                 double ax[U], ay[U];
 #pragma unroll
                 for (int j = 0; j < U; ++j) {
-                    if constexpr (VEC) {
-                        const d2_t r = ld2<true>((const d2_t *)(col + lda * (k + j)));
-                        ax[j] = r.x;
-                        ay[j] = r.y;
-                    } else {
-                        ax[j] = col[lda * (k + j)];
-                        ay[j] = v1 ? col[lda * (k + j) + 1] : 0.0;
-                    }
+                    ax[j] = col[lda * (k + j)];
+                    ay[j] = v1 ? col[lda * (k + j) + 1] : 0.0;
                 }
                 double p[U], e[U];
 #pragma unroll
@@ -111,36 +103,26 @@ __global__ void __launch_bounds__(256) k_scale_x(int n, double alpha, const doub
 // vector is read with scalar loads (one s_load_dwordx16 per 8 columns) and enters the TwoProd as an SGPR operand -- no
 // LDS staging of x, no workgroup barriers, no fragment registers for it.  The early-exit vote is one fp64 compare
 // per residue (the lane masks are OR-ed by the scalar unit).  Otherwise as k_gemvN_fpe (two rows per lane).
-template <int N, bool EE, int U = 8, bool TL = false>
+template <int N, bool EE>
 __global__ void __launch_bounds__(GV_BLOCK, 4) k_gemvN_fpe_sx(int m, int n, const double *__restrict__ a, long long lda,
-                                                           const double *__restrict__ xa, int kper,
-                                                           double *__restrict__ part, long long *__restrict__ ws, int il,
-                                                           int *__restrict__ tickets,
-                                                           unsigned long long *__restrict__ timeline)
+                                                           const double *__restrict__ xa, double *__restrict__ part,
+                                                           long long *__restrict__ ws, int *__restrict__ tickets)
 {
+    constexpr int U = 8;   // columns per group
     const int tid = threadIdx.x;
-    // TL: tools only (exblas_debug_timeline; a separate instantiation, the production kernels carry no trace of it):
-    // start / end clock of every wave
-    if (TL && (tid & 63) == 0)
-        timeline[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * GV_WAVES + (tid >> 6)) * 2] = wall_clock64();
     const long long r0 = ((long long)blockIdx.x * GV_BLOCK + tid) * 2;
     const int ks = blockIdx.y, KS = gridDim.y;
-    const int k0 = ks * kper, k1 = min(n, k0 + kper);
     const bool v0 = r0 < m;
     double f0[N], f1[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) f0[i] = f1[i] = 0.0;
     GlobalSink s0{ws + (v0 ? r0 : 0) * SET_WORDS}, s1{ws + (v0 ? r0 + 1 : 0) * SET_WORDS};
     if (v0) {
-        // il = 1: the k splits take the groups of U columns round-robin (split ks: groups ks, ks + KS, ...) instead of
-        // one contiguous range each (+1-2 %).  il = 2: in addition a group is every SECOND column of a block of 2U (even
-        // ones, then odd ones), so the loads a wave has in flight are 2 lda apart -- the 256 KiB column stride of
-        // lda = 32768 is the one that costs 9 % (tools/gemv_lda.py), 512 KiB does not.  il = 3 (production): the groups
-        // of il = 2, handed out dynamically.
-        static_assert(U == 8, "column groups are blocks of 16");
-        const int cs = il >= 2 ? 2 : 1;                          // column step inside a group
-        const int nfull = il >= 2 ? (n / (2 * U)) * 2 * U : (n / U) * U;  // columns covered by whole groups
-        auto group_k = [&](int gg) { return il >= 2 ? (gg >> 1) * 2 * U + (gg & 1) : gg * U; };
+        // A group is every SECOND column of a block of 2U (even ones, then odd ones), so the loads a wave has in flight
+        // are 2 lda apart -- the 256 KiB column stride of lda = 32768 is the one that costs 9 % (tools/gemv_lda.py),
+        // 512 KiB does not.
+        const int nfull = (n / (2 * U)) * 2 * U;  // columns covered by whole groups
+        auto group_k = [&](int gg) { return (gg >> 1) * 2 * U + (gg & 1); };
         // one counter per 128 rows, GV_TICKET_STRIDE bytes apart: device-scope atomics execute at the memory side, and 256
         // counters in one 1 KiB line made every draw of the whole chip queue at ONE channel (1.74 ms against 1.46 static)
         int *ctr = tickets + (size_t)(blockIdx.x * GV_WAVES + (tid >> 6)) * (GV_TICKET_STRIDE / sizeof(int));
@@ -156,10 +138,10 @@ __global__ void __launch_bounds__(GV_BLOCK, 4) k_gemvN_fpe_sx(int m, int n, cons
             double ax[U], ay[U], xs[U];
 #pragma unroll
             for (int j = 0; j < U; ++j) {
-                const d2_t r = ld2<true>((const d2_t *)(col + lda * (cs * j)));
+                const d2_t r = ld2((const d2_t *)(col + lda * (2 * j)));
                 ax[j] = r.x;
                 ay[j] = r.y;
-                xs[j] = xa[k + cs * j];  // uniform address: scalar load
+                xs[j] = xa[k + 2 * j];  // uniform address: scalar load
             }
             if (draw_after_loads) drawn = draw();  // behind the loads in the (in-order) return queue: it cannot hold them up
             double p[U], e[U];
@@ -170,54 +152,32 @@ __global__ void __launch_bounds__(GV_BLOCK, 4) k_gemvN_fpe_sx(int m, int n, cons
             for (int j = 0; j < U; ++j) p[j] = two_prod(ay[j], xs[j], e[j]);
             fpe_absorb_prod<N, EE, U, GlobalSink, 1>(f1, p, e, s1);
         };
-        if (il == 3) {
-            // DYNAMIC: the KS waves that own the same 128 rows (one per k split) draw column groups from a shared counter.
-            // The four workgroups resident on a CU do not run at the same pace -- the instruction arbiter favours the
-            // oldest: at 32768^2 with static ranges they finished at 1010 / 1081 / 1238 / 1412 us (tools/gemv_timeline.py),
-            // the CU draining from four waves per SIMD to one over the last 30 % of the kernel.  Every row segment has
-            // waves of all four ages, so with a shared counter they all run dry together.  The sum is exact, so which
-            // wave adds which columns cannot change a bit.  A ticket is TB groups (32 KiB of matrix per wave); tickets
-            // are drawn TWO ahead and the atomic is issued behind the loads of a group, so its (long, device-scope)
-            // latency has a whole ticket's compute time to pass and never sits in front of a load in the return queue.
-            constexpr int TB = 2;
-            const int ntick = (nfull / U + TB - 1) / TB, ngroups = nfull / U;
-            int t0 = __builtin_amdgcn_readfirstlane(draw());
-            int t1v = draw();
-            while (t0 < ntick) {
-                const int g = t0 * TB;
-                do_group(g, true);                       // draws the ticket after next into `drawn`
-                if (g + 1 < ngroups) do_group(g + 1, false);
-                t0 = __builtin_amdgcn_readfirstlane(t1v);
-                t1v = drawn;
-            }
-        } else if (il) {
-            for (int g = ks; g < nfull / U; g += KS) do_group(g, false);
+        // DYNAMIC: the KS waves that own the same 128 rows (one per k split) draw column groups from a shared counter.
+        // The four workgroups resident on a CU do not run at the same pace -- the instruction arbiter favours the
+        // oldest: at 32768^2 with static ranges they finished at 1010 / 1081 / 1238 / 1412 us
+        // (profiles/r03_gemv_timeline.log), the CU draining from four waves per SIMD to one over the last 30 % of the
+        // kernel.  Every row segment has waves of all four ages, so with a shared counter they all run dry together.
+        // The sum is exact, so which wave adds which columns cannot change a bit.  A ticket is TB groups (32 KiB of
+        // matrix per wave); tickets are drawn TWO ahead and the atomic is issued behind the loads of a group, so its
+        // (long, device-scope) latency has a whole ticket's compute time to pass and never sits in front of a load in
+        // the return queue.
+        constexpr int TB = 2;
+        const int ntick = (nfull / U + TB - 1) / TB, ngroups = nfull / U;
+        int t0 = __builtin_amdgcn_readfirstlane(draw());
+        int t1v = draw();
+        while (t0 < ntick) {
+            const int g = t0 * TB;
+            do_group(g, true);                       // draws the ticket after next into `drawn`
+            if (g + 1 < ngroups) do_group(g + 1, false);
+            t0 = __builtin_amdgcn_readfirstlane(t1v);
+            t1v = drawn;
         }
-        // what the groups do not cover: il == 0: this split's whole range; otherwise the last columns, split 0's job
-        int k = il ? nfull : k0;
-        const int kend = il ? (ks == 0 ? n : 0) : k1;
+        // the last columns, which the groups do not cover: split 0's job
+        int k = nfull;
+        const int kend = ks == 0 ? n : 0;
         const double *col = a + r0 + lda * k;
-        if (!il) {
-            for (; k + U <= kend; k += U, col += lda * U) {
-                double ax[U], ay[U], xs[U];
-#pragma unroll
-                for (int j = 0; j < U; ++j) {
-                    const d2_t r = ld2<true>((const d2_t *)(col + lda * j));
-                    ax[j] = r.x;
-                    ay[j] = r.y;
-                    xs[j] = xa[k + j];
-                }
-                double p[U], e[U];
-#pragma unroll
-                for (int j = 0; j < U; ++j) p[j] = two_prod(ax[j], xs[j], e[j]);
-                fpe_absorb_prod<N, EE, U, GlobalSink, 1>(f0, p, e, s0);
-#pragma unroll
-                for (int j = 0; j < U; ++j) p[j] = two_prod(ay[j], xs[j], e[j]);
-                fpe_absorb_prod<N, EE, U, GlobalSink, 1>(f1, p, e, s1);
-            }
-        }
         for (; k < kend; ++k, col += lda) {
-            const d2_t r = ld2<true>((const d2_t *)col);
+            const d2_t r = ld2((const d2_t *)col);
             const double xv = xa[k];
             double p[1], e[1];
             p[0] = two_prod(r.x, xv, e[0]);
@@ -232,8 +192,6 @@ __global__ void __launch_bounds__(GV_BLOCK, 4) k_gemvN_fpe_sx(int m, int n, cons
 #pragma unroll
         for (int i = 0; i < N; ++i) o[i] = f1[i];
     }
-    if (TL && (tid & 63) == 0)
-        timeline[(((size_t)blockIdx.y * gridDim.x + blockIdx.x) * GV_WAVES + (tid >> 6)) * 2 + 1] = wall_clock64();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -348,12 +306,15 @@ __global__ void __launch_bounds__(GV_BLOCK) k_gemv_finish(int rows, int nvals, c
 // 'T': y_j = Round(sum_i A(i,j) * fl(alpha*x_i) (+) beta*y_j); column j is contiguous -> ExDOT per workgroup
 // ---------------------------------------------------------------------------------------------
 // x: the pre-scaled contiguous vector x' = fl(alpha * x) (k_scale_x), so the kernel carries neither the multiply nor incx
-template <int N, bool EE, int COPIES, int U = 2, int ZM = 0, int MINW = 1>
-__global__ void __launch_bounds__(GV_BLOCK, MINW) k_gemvT(int m, const double *__restrict__ a, long long lda,
+template <int N, bool EE, int COPIES>
+__global__ void __launch_bounds__(GV_BLOCK) k_gemvT(int m, const double *__restrict__ a, long long lda,
                                                     const double *__restrict__ x, double beta,
-                                                    double *__restrict__ y, long long incy, int round_mode,
-                                                    int stagger, long long *__restrict__ ws)
+                                                    double *__restrict__ y, long long incy, int round_mode)
 {
+    // A/B on MI355X (tools/tune_gemv.py, 32768^2): 4 loads per stream in flight + staggered sweeps 5.3 TB/s; 2 loads
+    // 5.0; no stagger 4.9; a wave-per-column form (no workgroup barriers) and a persistent form were slower.  Early-exit
+    // votes by fp64 compares (ZM = 1): 1.58-1.61 ms against 1.64-1.66 by integer ORs.
+    constexpr int U = 4, ZM = 1;
     __shared__ long long s_acc[GV_WAVES * NL * COPIES];
     __shared__ long long merged[NL];
     __shared__ unsigned s_flags;
@@ -377,7 +338,7 @@ __global__ void __launch_bounds__(GV_BLOCK, MINW) k_gemvT(int m, const double *_
         // Every column of a power-of-two lda starts on the same HBM channel; since the sum is order-free, each
         // workgroup starts its sweep at a different tile (and wraps) so that concurrent columns spread over the
         // channels instead of marching through them in lockstep.
-        const long long t0 = stagger ? (j * 37) % (ntiles > 0 ? ntiles : 1) : 0;
+        const long long t0 = (j * 37) % (ntiles > 0 ? ntiles : 1);
         // a wave owns U KiB of the tile and each of its loads covers 1 KiB of it: the U loads of a lane are 1 KiB apart,
         // i.e. ONE address register pair + immediate offsets (they were 4 KiB apart, beyond the 12-bit offset: a 64-bit
         // add per load)
@@ -391,7 +352,7 @@ __global__ void __launch_bounds__(GV_BLOCK, MINW) k_gemvT(int m, const double *_
                 const long long base = t * tile + lane_off;
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    qa[u] = ld2<true>(va + base + u * 64);
+                    qa[u] = ld2(va + base + u * 64);
                     qx[u] = vx[base + u * 64];  // x is re-read by every workgroup: keep it cacheable
                 }
             };
@@ -441,7 +402,7 @@ __global__ void __launch_bounds__(GV_BLOCK, MINW) k_gemvT(int m, const double *_
         fpe_absorb_prod<N, false, 1>(f, p, e, sink);
     }
     fpe_flush_sink<N>(f, sink);
-    if (ws == nullptr && tid == 0 && beta != 0.0) {
+    if (tid == 0 && beta != 0.0) {
         const double yv = y[j * incy];
         if (beta == 1.0) {
             sink.add(yv);
@@ -459,14 +420,7 @@ __global__ void __launch_bounds__(GV_BLOCK, MINW) k_gemvT(int m, const double *_
         for (int w = 0; w < GV_WAVES; ++w)
 #pragma unroll
             for (int c = 0; c < COPIES; ++c) sum += s_acc[(w * NL + l) * COPIES + c];
-        if (ws) ws[j * SET_WORDS + l] = sum;   // deferred (A/B variant): k_gemv_finish carries, adds beta * y and rounds
-        else merged[l] = sum;
-    }
-    if (ws) {
-        // A/B variant: the column's 68 limbs + 3 non-finite indicators go to memory and ONE k_gemv_finish launch rounds
-        // all n outputs (a wave per output, ~30 us at n = 32768)
-        if (tid < 3) ws[j * SET_WORDS + NL + tid] = (s_flags >> tid) & 1u;
-        return;
+        merged[l] = sum;
     }
     __syncthreads();
     if (wave == 0) {  // one wavefront carries, cuts and rounds (shuffles + ballots only)
@@ -508,7 +462,7 @@ static hipError_t gemvN_fpe(Ctx &c, int m, int n, double alpha, const double *a,
                             double beta, double *y, int incy, int round_mode, hipStream_t st)
 {
     const int gx = (m + 2 * GV_BLOCK - 1) / (2 * GV_BLOCK);
-    const int wg_target = c.num_cu * (c.variant == 3 ? 8 : (c.variant == 4 ? 16 : (c.variant == 5 ? 32 : 4)));  // 4/CU: 1.43 ms, 8: 1.47, 16: 1.5-1.6
+    const int wg_target = c.num_cu * 4;  // 4/CU: 1.43 ms, 8: 1.47, 16: 1.5-1.6
     int KS = (wg_target + gx - 1) / gx;
     const int max_ks = (n + 63) / 64;
     if (KS > max_ks) KS = max_ks;
@@ -532,34 +486,16 @@ static hipError_t gemvN_fpe(Ctx &c, int m, int n, double alpha, const double *a,
     if (e != hipSuccess) return e;
     const bool vec = (m % 2 == 0) && (lda % 2 == 0) && (((uintptr_t)a) & 15u) == 0;
     dim3 grid(gx, KS);
-    if (vec && c.variant != 1 && c.variant != 2 && c.variant != 6) {
-        // production: x from SGPRs (scalar loads of the pre-scaled vector), early-exit votes by fp64 compares.  Against
-        // the LDS-staged kernel below (variant 6) in one process: 1.40-1.45 ms against 1.41-1.48 at 32768^2
+    if (vec) {
+        // x from SGPRs (scalar loads of the pre-scaled vector), early-exit votes by fp64 compares.  Against an LDS-staged
+        // form with 16-byte loads, in one process: 1.40-1.45 ms against 1.41-1.48 at 32768^2
         hipLaunchKernelGGL(k_scale_x, dim3((n + 255) / 256), dim3(256), 0, st, n, alpha, x, (long long)incx, xa);
-        const int il = c.variant == 9 ? 0 : (c.variant == 10 ? 1 : (c.variant == 11 ? 2 : 3));
-        bool traced = false;
-        if constexpr (N == 8 && EE) {
-            if (exblas_debug_timeline) {
-                traced = true;
-                hipLaunchKernelGGL((k_gemvN_fpe_sx<N, EE, 8, true>), grid, dim3(GV_BLOCK), 0, st, m, n, a, (long long)lda, xa,
-                                   kper, part, ws, il, tickets, (unsigned long long *)exblas_debug_timeline);
-            }
-        }
-        if (!traced)
-            hipLaunchKernelGGL((k_gemvN_fpe_sx<N, EE, 8>), grid, dim3(GV_BLOCK), 0, st, m, n, a, (long long)lda, xa, kper, part,
-                               ws, il, tickets, (unsigned long long *)nullptr);
-    } else if (vec && c.variant == 1)
-        hipLaunchKernelGGL((k_gemvN_fpe<N, EE, true, 4>), grid, dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
+        hipLaunchKernelGGL((k_gemvN_fpe_sx<N, EE>), grid, dim3(GV_BLOCK), 0, st, m, n, a, (long long)lda, xa, part, ws,
+                           tickets);
+    } else {
+        hipLaunchKernelGGL((k_gemvN_fpe<N, EE>), grid, dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
                            (long long)incx, kper, part, ws);
-    else if (vec && N == 8 && EE && c.variant == 2)
-        hipLaunchKernelGGL((k_gemvN_fpe<N, EE, true, 2>), grid, dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
-                           (long long)incx, kper, part, ws);
-    else if (vec)  // (variant 6) x staged in LDS; 8 columns per step: 6.06 TB/s vs 5.78 with 4 (tools/tune_gemv.py, 32768^2)
-        hipLaunchKernelGGL((k_gemvN_fpe<N, EE, true, 8>), grid, dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
-                           (long long)incx, kper, part, ws);
-    else
-        hipLaunchKernelGGL((k_gemvN_fpe<N, EE, false>), grid, dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
-                           (long long)incx, kper, part, ws);
+    }
     hipLaunchKernelGGL(k_gemv_finish, dim3((m + GV_WAVES - 1) / GV_WAVES), dim3(GV_BLOCK), 0, st, m, KS * N, part, ws,
                        beta, y, (long long)incy, round_mode);
     return hipGetLastError();
@@ -593,35 +529,19 @@ static hipError_t gemvT(Ctx &c, int m, int n, double alpha, const double *a, int
                         double beta, double *y, int incy, int round_mode, hipStream_t st)
 {
     constexpr int COPIES = (N == 0) ? 16 : 8;
-    // A/B on MI355X (tools/tune_gemv.py, 32768^2): 4 loads per stream in flight + staggered sweeps 5.3 TB/s;
-    // 2 loads 5.0; no stagger 4.9; a wave-per-column form (no workgroup barriers) and a persistent form were slower
-    // Rounding inside the workgroup (production) or deferred to one k_gemv_finish launch over all n outputs (variant 12:
-    // the column's limbs go through memory).  Measured at 32768^2: 1.616 ms against 1.649 deferred -- the ~6 us single-wave
-    // carry + round chain at the end of a workgroup's 39 us life is covered by the other workgroups of the CU; the extra
-    // launch is not.
-    long long *ws = nullptr;
-    // x' = fl(alpha * x), contiguous, once (m doubles behind the deferred-finish area of the workspace)
-    const size_t ws_bytes = c.variant == 12 ? (size_t)n * SET_WORDS * sizeof(long long) : 0;
+    // Rounding inside the workgroup: the ~6 us single-wave carry + round chain at the end of a workgroup's 39 us life is
+    // covered by the other workgroups of the CU.  Deferring it to one k_gemv_finish launch over all n outputs (the
+    // column's limbs through memory) measured 1.649 ms against 1.616 at 32768^2.
     {
+        // x' = fl(alpha * x), contiguous, once
         hipError_t e;
-        char *base = (char *)workspace(c, ws_bytes + (size_t)m * sizeof(double), st, &e);
-        if (!base) return e;
-        if (ws_bytes) ws = (long long *)base;
-        double *xa = (double *)(base + ws_bytes);
+        double *xa = (double *)workspace(c, (size_t)m * sizeof(double), st, &e);
+        if (!xa) return e;
         hipLaunchKernelGGL(k_scale_x, dim3((m + 255) / 256), dim3(256), 0, st, m, alpha, x, (long long)incx, xa);
         x = xa;
     }
-#define GVT_LAUNCH(...)                                                                                                \
-    hipLaunchKernelGGL((k_gemvT<N, EE, COPIES, __VA_ARGS__>), dim3(n), dim3(GV_BLOCK), 0, st, m, a, (long long)lda, x, \
-                       beta, y, (long long)incy, round_mode, c.variant == 1 ? 0 : 1, ws)
-    if (c.variant == 1) GVT_LAUNCH(2);             // two loads per stream in flight, no stagger
-    else if (c.variant == 13) GVT_LAUNCH(4, 1, 4); // A/B: four waves per SIMD (the compiler must fit 128 registers: it spills)
-    else if (c.variant == 6) GVT_LAUNCH(4);        // A/B: early-exit votes by integer ORs of the residue words
-    else GVT_LAUNCH(4, 1);                         // early-exit votes by fp64 compares: 1.58-1.61 ms against 1.64-1.66 at 32768^2
-#undef GVT_LAUNCH
-    if (ws)
-        hipLaunchKernelGGL(k_gemv_finish, dim3((n + GV_WAVES - 1) / GV_WAVES), dim3(GV_BLOCK), 0, st, n, 0,
-                           (const double *)nullptr, ws, beta, y, (long long)incy, round_mode);
+    hipLaunchKernelGGL((k_gemvT<N, EE, COPIES>), dim3(n), dim3(GV_BLOCK), 0, st, m, a, (long long)lda, x, beta, y,
+                       (long long)incy, round_mode);
     return hipGetLastError();
 }
 
@@ -677,7 +597,7 @@ hipError_t exgemv_dispatch(Ctx &c, char transa, int m, int n, double alpha, cons
 extern "C" int exblas_debug_gemv_occupancy(void)
 {
     int nb = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, exb::k_gemvN_fpe_sx<8, true, 8, false>, exb::GV_BLOCK, 0) != hipSuccess)
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, exb::k_gemvN_fpe_sx<8, true>, exb::GV_BLOCK, 0) != hipSuccess)
         return -1;
     return nb;
 }

@@ -823,8 +823,6 @@ hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, in
     plan->R = (unsigned *)(base + o_r);
     plan->plane_a = plane_a; plan->plane_b = plane_b; plan->lcap = lcap; plan->m4 = cm4;
     plan->chunk_rows = chunk; plan->a = a; plan->lda = lda; plan->alpha = alpha; plan->ta = ta; plan->k = k;
-    // tuning variants 21..25: 1, 2, 3, 6 moduli per launch / all in one; default: by the number of tiles (exgemm_crt_rows)
-    plan->mods_per_launch = c.variant == 21 ? 1 : (c.variant == 22 ? 2 : (c.variant == 23 ? 3 : (c.variant == 24 ? 6 : (c.variant == 25 ? lcap : 0))));
     plan->num_cu = c.num_cu;
     plan->beta = beta; plan->c = cmat; plan->ldc = ldc; plan->round_mode = round_mode;
     c.gemm_info_dev = info;
@@ -849,11 +847,8 @@ hipError_t exgemm_crt_rows(const I8Plan &p, int row0, int row1, hipStream_t st)
         // they run in step; they start in step at the beginning of a launch and drift apart afterwards: about 12 rounds
         // of one workgroup per CU per launch (8192^3, whole-matrix launches: 15 GB through the fabric per call with 12
         // rounds, 30.5 GB with 72).  Launches for moduli the data does not need exit at once.
-        int per = p.mods_per_launch;
-        if (per <= 0) {
-            const long long tiles = (long long)by_cnt * bx_cnt;
-            per = (int)max(1ll, min((long long)p.lcap, (12ll * p.num_cu) / max(1ll, tiles)));
-        }
+        const long long tiles = (long long)by_cnt * bx_cnt;
+        const int per = (int)max(1ll, min((long long)p.lcap, (12ll * p.num_cu) / max(1ll, tiles)));
         for (int kc0 = 0; kc0 < p.KC; kc0 += CRT_KPASS)
             for (int mod0 = 0; mod0 < p.lcap; mod0 += per) {
                 const int nm = min(per, p.lcap - mod0);

@@ -91,14 +91,13 @@ static void init_ctx(Ctx &c, int device, int layer)
     c.ngroups = env_int("EXBLAS_NGROUPS", 32);
     c.grid_adj = env_int("EXBLAS_GRID_ADJ", 0);
     if (c.ngroups < 1) c.ngroups = 1;
-    c.variant = env_int("EXBLAS_VARIANT", 0);
     c.gemm_path = env_int("EXBLAS_GEMM_PATH", 0);
     if (layer > 0 && g_ctx[0][device].device >= 0) {  // knobs set through the API so far apply to every layer
         const Ctx &z = g_ctx[0][device];
         c.blocks_per_cu = z.blocks_per_cu; c.bpc_sum = z.bpc_sum; c.bpc_dot = z.bpc_dot; c.bpc_sa = z.bpc_sa;
         c.bpc_heavy = z.bpc_heavy;
         c.grid_adj = z.grid_adj;
-        c.ngroups = z.ngroups; c.variant = z.variant; c.gemm_path = z.gemm_path;
+        c.ngroups = z.ngroups; c.gemm_path = z.gemm_path;
         c.spmv_path = z.spmv_path;
         c.gemm_max_slices = z.gemm_max_slices;
         c.gemm_max_moduli = z.gemm_max_moduli;
@@ -349,6 +348,9 @@ void exblas_set_round_mode(int mode) { g_round_mode = mode ? 1 : 0; }
 
 int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant)
 {
+    // variant: kept in the signature for existing callers.  Refused before the device is touched: a stale A/B script
+    // fails instead of timing the one production kernel under a variant's name.
+    if (variant != -1 && variant != 0) return (int)hipErrorInvalidValue;
     ctx(-1);
     for_each_layer(current_device(), [&](Ctx &c) {
         std::lock_guard<std::mutex> lk(c.mu);
@@ -362,7 +364,6 @@ int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant)
             c.gacc = c.gacc_all + (size_t)c.slot * NL * c.ngroups;
             EXB_CHECK(hipDeviceSynchronize());
         }
-        if (variant >= 0) c.variant = variant;
     });
     return 0;
 }

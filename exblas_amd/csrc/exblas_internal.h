@@ -21,7 +21,6 @@ struct Ctx {
     int bpc_heavy = 4;       // ExSUM variants without early exit, N >= 5, in -DEXBLAS_FULL_CASCADE=1 builds only (VALU-latency-bound)
     int ngroups = 32;        // EXBLAS_NGROUPS: global group accumulators the blocks add into
     int grid_adj = 0;        // EXBLAS_GRID_ADJ: workgroups added to the grid of the streaming ExSUM / ExDOT kernels
-    int variant = 0;         // tuning variant of the production kernels (exblas_set_tuning)
     // when set, the NEXT streaming ExSUM / ExDOT launch carries this event as the completion signal of its own dispatch
     // packet (hipExtLaunchKernelGGL) and clears the field: no separate event packet follows the kernel in the queue
     // (comm.hip: pipelined_step)
@@ -122,7 +121,7 @@ struct I8Plan {
     bool crt = false;
     unsigned *R = nullptr;
     size_t plane_a = 0, plane_b = 0;
-    int lcap = 0, m4 = 0, mods_per_launch = 0, num_cu = 256;
+    int lcap = 0, m4 = 0, num_cu = 256;
     // residue path: A' is reduced row chunk by row chunk (PA / R hold one chunk)
     int chunk_rows = 0, lda = 0, ta = 0, k = 0;
     const double *a = nullptr;

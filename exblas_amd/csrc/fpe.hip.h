@@ -12,12 +12,8 @@ namespace exb {
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
-template <bool NT>
-__device__ __forceinline__ d2_t ld2(const d2_t *p)
-{
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
+// 16-byte streaming load, non-temporal: each element is read once
+__device__ __forceinline__ d2_t ld2(const d2_t *p) { return __builtin_nontemporal_load(p); }
 
 // biased exponent field of a double, and the guard threshold 2^1000 (see fpe_absorb_sink)
 __device__ __forceinline__ unsigned expo_field(double x) { return ((unsigned)__double2hiint(x) >> 20) & 0x7ffu; }
@@ -37,7 +33,7 @@ __device__ __forceinline__ bool any_nonzero(const double (&x)[CNT])
         for (int j = 0; j < CNT; ++j)
             bits |= ((unsigned)__double2hiint(x[j]) << 1) | (unsigned)__double2loint(x[j]);
         return bits != 0;
-    } else {  // fp64 compares (A/B variant)
+    } else {  // fp64 compares
         bool nz = false;
 #pragma unroll
         for (int j = 0; j < CNT; ++j) nz |= (x[j] != 0.0);

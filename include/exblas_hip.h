@@ -96,8 +96,10 @@ extern "C" {
 int exblas_hip_init(int device);
 int exblas_hip_device_count(void);
 const char *exblas_hip_version(void);
-/* Launch-geometry knobs for A/B measurements (<= 0 / < 0 leave a value unchanged): resident blocks per CU
- * of the streaming kernels, number of global group accumulators, kernel variant (0 = production). */
+/* Launch-geometry knobs for A/B measurements (<= 0 leaves a value unchanged): resident blocks per CU of the
+ * streaming kernels, number of global group accumulators.  variant must be -1 or 0 (the library builds one kernel
+ * per configuration; candidates are A/B'd as separate builds); any other value returns hipErrorInvalidValue and
+ * changes nothing. */
 int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant);
 /* ExGEMM implementation.  0 (default): error-free integer arithmetic on the int8 matrix cores
  * (v_mfma_i32_32x32x32_i8) for every (fpe, early_exit) variant and both rounding modes whenever the data qualifies --

@@ -3,6 +3,7 @@ import ctypes
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 
@@ -60,6 +61,16 @@ def test_no_gpu_means_loud_failure(lib):
     assert lib.exblas_hip_device_count() == 0
     with pytest.raises(RuntimeError):
         exblas_amd.exsum(4, [1.0, 2.0, 3.0, 4.0], 1, 0, 0)
+
+
+def test_set_tuning_refuses_a_kernel_variant():
+    """The library builds one kernel per configuration: exblas_set_tuning's third argument accepts only -1 and 0, and any
+    other value is refused with hipErrorInvalidValue before the device is touched.  A fresh child process: without a
+    device, any path that reaches the context ends the process."""
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); import exblas_amd; "
+            "print('ret', exblas_amd.load_library().exblas_set_tuning(-1, -1, 5))")
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ret 1"), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 
 
 def test_product_does_not_import_oracle():
