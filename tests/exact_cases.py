@@ -1,0 +1,462 @@
+"""Constructed ExGEMV / ExGEMM inputs whose exact results are known as Python integers, and the integer reference.
+
+Nothing here touches the GPU, the library or the oracle: operands are built as Python integers (``dtype=object``
+matrices) times powers of two, the exact result is ``ndarray.dot`` on those object arrays, and the expected double is
+``float(Fraction)`` (correctly rounded to nearest, ties to even, subnormals included).  Every constructor converts its
+operands to float64 and asserts that each one converts back to the integer it was built from.
+
+Output classes (``classify``), in units of the result's least significant integer bit:
+  ``zero``   the exact result is 0
+  ``exact``  the result is representable (at most 53 significant bits): nothing to round
+  ``tie``    exactly half a unit in the last place above a double (``tie_up``: round-to-even goes away from zero)
+  ``carry``  a tie whose 53 kept bits are all ones: it rounds up into the next binade
+  ``tie+1`` / ``tie-1``   one integer unit above / below a tie (in magnitude)
+  ``max``    the largest magnitude the case can produce (worst-case families only)
+  ``other``  anything else (never present in a planted case)
+"""
+import math
+from fractions import Fraction
+from types import SimpleNamespace
+
+import numpy as np
+
+
+# ---------------------------------------------------------------------------------------------
+# integer reference
+# ---------------------------------------------------------------------------------------------
+def round_nearest_even(v):
+    """exact integer or Fraction -> the nearest double (ties to even); beyond the double range -> +-inf"""
+    v = Fraction(v)
+    try:
+        return float(v)
+    except OverflowError:
+        return math.inf if v > 0 else -math.inf
+
+
+def obj(a):
+    """any integer array -> dtype=object array of Python ints (same shape)"""
+    a = np.asarray(a)
+    out = np.empty(a.shape, dtype=object)
+    out.ravel()[:] = [int(v) for v in a.ravel().tolist()]
+    return out
+
+
+def to_f64(ints, exp=0):
+    """integers (object array) times 2^exp (an int, or an int array that broadcasts) as float64 -- asserting that every
+    entry converts back to the integer it was built from (2^66 + 1 would silently round)"""
+    ints = np.asarray(ints, dtype=object)
+    flat = ints.ravel().tolist()
+    f = np.array([float(v) for v in flat], dtype=np.float64)
+    assert [int(x) for x in f.tolist()] == flat, "an operand is not representable as a double"
+    f = f.reshape(ints.shape)
+    e = np.broadcast_to(np.asarray(exp, dtype=np.int64), ints.shape)
+    out = np.ldexp(f, e)
+    assert np.isfinite(out).all() and (np.ldexp(out, -e) == f).all(), "an operand leaves the double range when scaled"
+    return out
+
+
+def gemm_exact(a_int, b_int):
+    """exact integer product of two object matrices"""
+    return np.asarray(a_int, dtype=object).dot(np.asarray(b_int, dtype=object))
+
+
+def gemv_exact(g_int, x_int, beta=0, y0_int=None):
+    """exact G x + beta y0 (G: outputs x inner, object ints; beta a Fraction or int) as an object vector of integers"""
+    y = np.asarray(g_int, dtype=object).dot(np.asarray(x_int, dtype=object))
+    if y0_int is not None and beta != 0:
+        t = [Fraction(beta) * int(v) + int(s) for v, s in zip(y0_int, y)]
+        assert all(v.denominator == 1 for v in t), "beta * y0 is not an integer in the result's units"
+        y = obj([int(v) for v in t])
+    return y
+
+
+def rounded(c_int, exp=0):
+    """float64 array of round_nearest_even(c_int * 2^exp), exp an int or a broadcasting int array"""
+    c_int = np.asarray(c_int, dtype=object)
+    e = np.broadcast_to(np.asarray(exp, dtype=np.int64), c_int.shape).ravel().tolist()
+    out = np.array([round_nearest_even(Fraction(int(v)) * Fraction(2) ** int(s)) for v, s in zip(c_int.ravel().tolist(), e)],
+                   dtype=np.float64)
+    return out.reshape(c_int.shape)
+
+
+def span_bits(ints, axis):
+    """the largest number of bits a vector of the matrix spans, from its highest set bit down to its lowest (rows of the
+    matrix for axis = 1, columns for axis = 0): what ExGEMM's operand scan reports for A and for B"""
+    ints = np.asarray(ints, dtype=object)
+    best = 0
+    for vec in (ints if axis == 1 else ints.T):
+        mags = [abs(int(v)) for v in vec if int(v)]
+        if mags:
+            best = max(best, max(v.bit_length() for v in mags) - min((v & -v).bit_length() - 1 for v in mags))
+    return best
+
+
+def classify(v):
+    """class of one exact integer result (module docstring) and whether round-to-even moves its magnitude up"""
+    v = int(v)
+    if v == 0:
+        return "zero", False
+    a = abs(v)
+    sh = a.bit_length() - 53
+    if sh <= 0 or a & ((1 << sh) - 1) == 0:
+        return "exact", False
+    r, half, mant = a & ((1 << sh) - 1), 1 << (sh - 1), a >> sh
+    if r == half:
+        return ("carry" if mant == (1 << 53) - 1 else "tie"), bool(mant & 1)
+    if r == half + 1:
+        return "tie+1", True
+    if r == half - 1:
+        return "tie-1", False
+    return "other", r > half
+
+
+def classify_all(c_int):
+    c_int = np.asarray(c_int, dtype=object)
+    pairs = [classify(v) for v in c_int.ravel().tolist()]
+    cls = np.array([p[0] for p in pairs], dtype=object).reshape(c_int.shape)
+    up = np.array([p[1] for p in pairs], dtype=bool).reshape(c_int.shape)
+    return cls, up
+
+
+def planted_mix(case):
+    """The condition every planted case meets by construction: at least 40 % exact ties and at least 40 % one unit off a
+    tie, ties that round up and ties that round down, near-ties above and below, a tie that carries into the next
+    binade, both signs, and no output outside the planted classes.  Returns the class counts."""
+    cls, up, c = case.classes.ravel(), case.tie_up.ravel(), case.c_int.ravel()
+    total = cls.size
+    count = {name: int((cls == name).sum()) for name in ("tie", "carry", "tie+1", "tie-1", "exact", "zero", "other")}
+    ties = (cls == "tie") | (cls == "carry")
+    near = (cls == "tie+1") | (cls == "tie-1")
+    neg = np.array([int(v) < 0 for v in c.tolist()])
+    assert count["other"] == 0, count
+    assert 10 * int(ties.sum()) >= 4 * total and 10 * int(near.sum()) >= 4 * total, count
+    assert (ties & up).any() and (ties & ~up).any(), "ties in both directions"
+    assert count["tie+1"] and count["tie-1"] and count["carry"], count
+    for sel in (ties, near):
+        assert (sel & neg).any() and (sel & ~neg).any(), "both signs"
+    return count
+
+
+# ---------------------------------------------------------------------------------------------
+# the residue path's moduli: 256, 255, 253, 251, 247, ... (greedy, pairwise coprime, counting down from 256)
+# ---------------------------------------------------------------------------------------------
+CRT_LMAX = 39
+
+
+def crt_moduli(count=CRT_LMAX):
+    ps, c = [], 256
+    while len(ps) < count:
+        if all(math.gcd(c, q) == 1 for q in ps):
+            ps.append(c)
+        c -= 1
+    return ps
+
+
+def crt_bits(count=CRT_LMAX):
+    """bits[L] = floor(log2(p_0 ... p_{L-1})) for L = 0 .. count"""
+    bits, prod = [0], 1
+    for p in crt_moduli(count):
+        prod *= p
+        bits.append(prod.bit_length() - 1)
+    return bits
+
+
+def crt_need(bits_a, bits_b, k):
+    return bits_a + bits_b + max(0, (k - 1).bit_length()) + 2
+
+
+def crt_moduli_needed(bits_a, bits_b, k):
+    """the smallest L with bits[L] >= bits_a + bits_b + ceil(log2 k) + 2"""
+    need = crt_need(bits_a, bits_b, k)
+    ps, prod, c = [], 1, 256
+    while prod.bit_length() - 1 < need:
+        if all(math.gcd(c, q) == 1 for q in ps):
+            ps.append(c)
+            prod *= c
+        c -= 1
+    return len(ps)
+
+
+# ---------------------------------------------------------------------------------------------
+# planted ties
+# ---------------------------------------------------------------------------------------------
+LAYOUTS = ("tail", "split", "head")
+D_PATTERN = (0, 1, 0, -1)
+
+
+def _k_order(k, layout):
+    """positions along k, as a list of canonical indices (0 lead, 1 its duplicate, 2 .. k-3 random, k-2 H, k-1 d)"""
+    lead, dup, h, d = 0, 1, k - 2, k - 1
+    rnd = list(range(2, k - 2))
+    half = len(rnd) // 2
+    if layout == "tail":
+        return [lead, dup] + rnd + [h, d]
+    if layout == "split":          # H first, the leading products in the middle, the deciding unit last
+        return [h] + rnd[:half] + [lead, dup] + rnd[half:] + [d]
+    if layout == "head":           # the deciding unit first, H last
+        return [d] + rnd[:half] + [lead, dup] + rnd[half:] + [h]
+    raise ValueError(layout)
+
+
+def planted_gemm(m, n, k, S, seed=0, layout="tail", ea=0, eb=0):
+    """A (m x k) and B (k x n) with
+
+        A = s_i * [ 2^S * (1, 0, u_i2 .. u_i,k-3) , 1 , 1 ]            u, v small random integers in [-8, 8]
+        B = t_j * [ 3 * 2^18 ; 3 * 2^18 ; v_2j .. v_k-3,j ; h_j H ; d_j ]     H = 2^(S - 34), h_j in {1, 3}, d_j in {0, +1, 0, -1}
+
+    so that C_ij = s_i t_j (2^S P_ij + h_j H + d_j) with P_ij of exactly 20 bits: H is half a unit in the last place,
+    h_j = 3 makes the kept mantissa odd (the tie rounds away from zero), d_j = +-1 moves the sum one integer unit off the
+    tie, S - 34 bits below the rounding position.  Carry columns (j % 16 in 12, 13, 15) hold 2^20 - 1 in the leading
+    rows, zeros for v and 2^S - H in the H row: all 53 kept bits are ones and the tie carries into the next binade.
+    With m >= 16, row 3 is +-2^S * 5 against the two equal leading rows of B (large products that cancel to exactly
+    zero) and row m - 2 has no 2^S part (results of a few bits: nothing to round).  `layout` moves the leading, H and d
+    positions along k; `ea`, `eb` scale A and B by powers of two."""
+    assert k >= 5 and n >= 16 and S >= 54
+    rng = np.random.default_rng([seed, m, n, k, S])
+    U, V = obj(rng.integers(-8, 9, (m, k))), obj(rng.integers(-8, 9, (k, n)))
+    H = 1 << (S - 34)
+    A, B = np.empty((m, k), dtype=object), np.empty((k, n), dtype=object)
+    s = [-1 if i % 3 == 1 else 1 for i in range(m)]
+    t = [-1 if j % 7 in (2, 5) else 1 for j in range(n)]
+    zero_row, exact_row = (3, m - 2) if m >= 16 else (-1, -1)
+    for i in range(m):
+        if i == zero_row:
+            A[i, :] = 0
+            A[i, 0], A[i, 1] = 5 << S, -(5 << S)
+        elif i == exact_row:
+            A[i, :] = U[i, :] * s[i]
+            A[i, 0] = A[i, 1] = A[i, k - 2] = 0
+            A[i, k - 1] = s[i]
+        else:
+            A[i, :] = U[i, :] * (s[i] << S)
+            A[i, 0], A[i, 1], A[i, k - 2], A[i, k - 1] = s[i] << S, 0, s[i], s[i]
+    for j in range(n):
+        d = D_PATTERN[j % 4]
+        if j % 16 in (12, 13, 15):
+            B[:, j] = 0
+            B[0, j] = B[1, j] = t[j] * ((1 << 20) - 1)
+            B[k - 2, j] = t[j] * ((1 << S) - H)
+        else:
+            B[:, j] = V[:, j] * t[j]
+            B[0, j] = B[1, j] = t[j] * (3 << 18)
+            B[k - 2, j] = t[j] * H * (3 if (j // 4) % 2 else 1)
+        B[k - 1, j] = t[j] * d
+    order = _k_order(k, layout)
+    A, B = A[:, order], B[order, :]
+    c_int = gemm_exact(A, B)
+    cls, up = classify_all(c_int)
+    pos = {name: order.index(idx) for name, idx in (("lead", 0), ("dup", 1), ("H", k - 2), ("d", k - 1))}
+    return SimpleNamespace(m=m, n=n, k=k, S=S, layout=layout, a_int=A, b_int=B, ea=ea, eb=eb, a=to_f64(A, ea), b=to_f64(B, eb),
+                           c_int=c_int, c_exp=ea + eb, classes=cls, tie_up=up, want=rounded(c_int, ea + eb), pos=pos,
+                           bits_a=span_bits(A, 1), bits_b=span_bits(B, 0))
+
+
+def gemm_operand(mat, trans, pad, fill=3.0):
+    """row-major storage of op(X) = mat for ExGEMM: 'N' stores mat, 'T' stores its transpose; `pad` extra columns of
+    `fill` per stored row.  Returns (flat array, leading dimension)."""
+    st = np.ascontiguousarray(mat.T if trans == "T" else mat, dtype=np.float64)
+    ld = st.shape[1] + pad
+    out = np.full((st.shape[0], ld), fill, dtype=np.float64)
+    out[:, :st.shape[1]] = st
+    return out.reshape(-1), ld
+
+
+def planted_gemv(outputs, inner, S, seed=0, layout="tail", plant=None, beta=0):
+    """The columns of planted_gemm's B as the rows of a matrix G (outputs x inner) and one ordinary row of its A as x:
+    y_j = t_j (2^S P_j + h_j H + d_j), the same classes per output.  `plant` = 'H' or 'd' takes that term out of the
+    inner product and plants it in y: beta = 1 with y0_j = the term; beta = -3/4 with y0_j = -4 term (beta y0 = 3 term)
+    and -2 term left in the inner product.  With beta = 0, y0 holds finite values that must be ignored."""
+    g = planted_gemm(1, outputs, inner, S, seed=seed, layout=layout)
+    G, x = g.b_int.T.copy(), g.a_int[0].copy()
+    beta = Fraction(beta)
+    y0 = obj(np.zeros(outputs, dtype=np.int64))
+    if plant is not None:
+        assert beta in (1, Fraction(-3, 4))
+        p = g.pos[plant]
+        term = G[:, p] * x[p]
+        if beta == 1:
+            y0, x[p] = term, 0
+        else:
+            y0, x[p] = term * -4, x[p] * -2
+    else:
+        assert beta == 0
+    y_int = gemv_exact(G, x, beta, y0)
+    assert (y_int == g.c_int[0]).all()
+    y0f = to_f64(y0) if beta != 0 else np.full(outputs, 12345.678)
+    return SimpleNamespace(outputs=outputs, inner=inner, S=S, layout=layout, plant=plant, beta=float(beta), g_int=G, x_int=x,
+                           y0_int=y0, g=to_f64(G), x=to_f64(x), y0=y0f, c_int=y_int, c_exp=0, classes=g.classes[0],
+                           tie_up=g.tie_up[0], want=g.want[0], pos=g.pos)
+
+
+def gemv_operands(g, x, y0, trans, pad=0, offa=0, incx=1, offx=0, incy=1, offy=0, fill=3.0):
+    """ExGEMV's arguments for y = G x: column-major A with A = G ('N': m outputs, n inner) or A = G^T ('T': m inner, n
+    outputs), lda = m + pad, strided / offset x and y.  Returns (m, n, a, lda, x, y)."""
+    G = np.asarray(g, dtype=np.float64)
+    outputs, inner = G.shape
+    m, n = (inner, outputs) if trans == "T" else (outputs, inner)
+    cols = G if trans == "T" else G.T                    # cols[c] = column c of A
+    lda = m + pad
+    a = np.full(offa + n * lda, fill, dtype=np.float64)
+    av = a[offa:].reshape(n, lda)
+    av[:, :m] = cols
+    xs = np.full(offx + (inner - 1) * incx + 1, fill, dtype=np.float64)
+    xs[offx::incx] = x
+    ys = np.full(offy + (outputs - 1) * incy + 1, fill, dtype=np.float64)
+    ys[offy::incy] = y0
+    return m, n, a, lda, xs, ys
+
+
+# ---------------------------------------------------------------------------------------------
+# worst-case magnitudes for the residue path
+# ---------------------------------------------------------------------------------------------
+_WORST_K = (1, 2, 3, 16, 17, 256, 257, 8192, 8193, 5, 1024, 1025, 64, 65)
+# the L whose M_L is barely above 2^bits[L] (M_L / 2^bits[L] = 1.03 .. 1.08) get a k that is exactly a power of two, so that
+# k 2^na 2^nb is exactly 2^(bits[L] - 2) and the largest sum comes as close to M_L / 4 as doubles allow
+_WORST_K_TIGHT = {11: 1024, 22: 8192, 27: 256, 28: 64, 29: 1024, 33: 4096}
+_WORST_K_TIGHT[13] = 1      # the largest L a single product reaches: 50 + 50 + 2 bits
+
+
+def _clog2(k):
+    return max(0, (k - 1).bit_length())
+
+
+def crt_worst_params(L):
+    """(na, nb, k) with na + nb + ceil(log2 k) + 2 == bits[L], na, nb <= 126: k from a list of powers of two and powers
+    of two plus one where the bits allow it.  k = 1 only serves na, nb <= 53 (a vector of one double spans 53 bits)."""
+    need = crt_bits()[L]
+    k = _WORST_K_TIGHT.get(L, _WORST_K[L % len(_WORST_K)])
+    while need - 2 - _clog2(k) < 2:
+        k = max(1, k // 4)
+    if k == 1 and need - 2 > 106:
+        k = 2
+    while need - 2 - _clog2(k) > 252:
+        k = 1 << (_clog2(k) + 1)
+    rest = need - 2 - _clog2(k)
+    na = min(126, (rest + 1) // 2)
+    nb = rest - na
+    assert 1 <= nb <= 126 and crt_need(na, nb, k) == need
+    return na, nb, k
+
+
+def _full_vector(nbits, k):
+    """k magnitudes that span exactly `nbits` bits and are as large as doubles allow: 2^nbits - 1 everywhere when that
+    is a double (nbits <= 53); else the top 53 bits set, (2^53 - 1) 2^(nbits - 53), except for the last entry (the last
+    two from k = 4 on, so that alternating signs still cancel in pairs), which holds 2^53 - 1 and pins the unit"""
+    if nbits <= 53:
+        return [(1 << nbits) - 1] * k
+    assert k >= 2
+    lows = 2 if k >= 4 else 1
+    return [((1 << 53) - 1) << (nbits - 53)] * (k - lows) + [(1 << 53) - 1] * lows
+
+
+def crt_worst_case(L, m=12, n=12):
+    """Operands at the largest magnitude (na, nb, k) = crt_worst_params(L) admits: every entry of a row of A is
+    +-(2^na - 1) 2^ra_i -- for na > 53, which no double holds, +-(2^53 - 1) 2^(na - 53) 2^ra_i with 2^53 - 1 in the last
+    position(s), _full_vector -- and likewise for the columns of B with nb, rb_j; ra, rb are per-row / per-column powers
+    of two.  Rows and columns by index mod 6: all plus, all minus, alternating from plus, alternating from minus, a
+    unit vector (a single +-1), all plus.  C then holds the largest sum (class ``max``), its negative, cancellation in
+    pairs (to 0 when k is even), single products and +-1."""
+    na, nb, k = crt_worst_params(L)
+    X, Y = _full_vector(na, k), _full_vector(nb, k)
+
+    def vec(kind, mags, unit):
+        if kind in (0, 5):
+            return list(mags)
+        if kind == 1:
+            return [-v for v in mags]
+        if kind in (2, 3):
+            return [v if (l + kind) % 2 == 0 else -v for l, v in enumerate(mags)]
+        return [unit] + [0] * (k - 1)
+
+    A, B = np.empty((m, k), dtype=object), np.empty((k, n), dtype=object)
+    for i in range(m):
+        A[i, :] = vec(i % 6, X, 1 if i % 12 < 6 else -1)
+    for j in range(n):
+        B[:, j] = vec(j % 6, Y, -1 if j % 12 < 6 else 1)
+    ra = np.array([(7 * i) % 23 - 11 for i in range(m)], dtype=np.int64)
+    rb = np.array([(5 * j) % 19 - 9 for j in range(n)], dtype=np.int64)
+    a = to_f64(A, ra[:, None])
+    b = to_f64(B, rb[None, :])
+    c_int = gemm_exact(A, B)
+    c_exp = ra[:, None] + rb[None, :]
+    cls, up = classify_all(c_int)
+    top = sum(x * y for x, y in zip(X, Y))
+    cls[np.array([[abs(int(v)) == top for v in row] for row in c_int])] = "max"
+    return SimpleNamespace(L=L, m=m, n=n, k=k, na=na, nb=nb, a_int=A, b_int=B, a=a, b=b, c_int=c_int, c_exp=c_exp,
+                           classes=cls, tie_up=up, want=rounded(c_int, c_exp), bits_a=span_bits(A, 1), bits_b=span_bits(B, 0), top=top)
+
+
+def crt_wrap_case(k, m=10, n=9, nbits=12, seed=0):
+    """Every entry = 128 (mod 256) in the integer units the residue path works in: the symmetric residue of p = 256 is
+    +128, which wraps to -128 as an int8, and with k = 8192 the int32 contraction of that modulus reaches exactly 2^27.
+    Row 0 of A and column 0 of B carry one odd entry each, which pins the unit of every vector to 2^0."""
+    rng = np.random.default_rng([seed, k])
+    top = 1 << (nbits - 1)
+    A = obj(top + 128 + 256 * rng.integers(0, top // 256, (m, k)))
+    B = obj(top + 128 + 256 * rng.integers(0, top // 256, (k, n)))
+    A *= obj(np.where(rng.random((m, 1)) < 0.4, -1, 1))
+    A[0, 0], B[0, 0] = top + 1, -(top + 1)
+    c_int = gemm_exact(A, B)
+    cls, up = classify_all(c_int)
+    return SimpleNamespace(m=m, n=n, k=k, na=nbits, nb=nbits, a_int=A, b_int=B, a=to_f64(A), b=to_f64(B), c_int=c_int,
+                           c_exp=0, classes=cls, tie_up=up, want=rounded(c_int), bits_a=span_bits(A, 1), bits_b=span_bits(B, 0))
+
+
+# ---------------------------------------------------------------------------------------------
+# ExGEMV result-range rows
+# ---------------------------------------------------------------------------------------------
+def range_rows_gemv(inner=12):
+    """Rows whose exact sums sit at the ends of the double range while every product is exact for TwoProd (a multiple
+    of 2^-1074 below 2^1024).  Six positions of x are in use, spread over [0, inner): three hold small integers times
+    2^-537 (G there: integers times 2^-537, products: multiples of 2^-1074), three hold 2^511 (G there: values times
+    2^512, products up to 2^1023).  y0 (for beta = 1) adds the last term of two of the rows.
+    Returns G, x, y0 (float64), the exact sums without and with y0 (Fractions), and row names."""
+    assert inner >= 6
+    lo = [0, inner // 2, inner - 1]                     # x = (1, 3, -2) * 2^-537
+    hi = [1, inner // 2 - 1, inner - 2]                 # x = 2^511
+    xl = (1, 3, -2)
+    T52 = 1 << 52
+    big = (1 << 53) - 1                                 # (2^53 - 1) * 2^(512 - 53) * 2^511 = 2^1023 - 2^970
+    rows = [   # name, G at lo (integers, times 2^-537), G at hi (integers, times 2^(512 - 53)), y0
+        ("subnormal 15 units", (5, 2, -2), (0, 0, 0), 0.0),
+        ("subnormal -2 units", (-4, 0, -1), (0, 0, 0), 0.0),
+        ("largest subnormal", (T52 - 7, 2, 0), (0, 0, 0), 0.0),
+        ("smallest normal", (T52 - 6, 2, 0), (0, 0, 0), 0.0),
+        ("4 x smallest normal", (T52, T52, 0), (0, 0, 0), 0.0),
+        ("one unit after cancellation", (T52, 1, T52 // 2 + 1), (0, 0, 0), 0.0),
+        ("partial sums overflow", (0, 0, 0), (T52 * 2, T52 * 2, -T52 * 2), 0.0),
+        ("DBL_MAX", (0, 0, 0), (T52 * 2, big - 1, 0), 0.0),
+        ("tie at the overflow threshold", (0, 0, 0), (T52 * 2, big - 1, 1), 0.0),
+        ("just below the overflow tie", (0, 0, 0), (T52 * 2, big - 1, 0), 2.0 ** 970 - 2.0 ** 918),
+        ("-DBL_MAX", (0, 0, 0), (-T52 * 2, -(big - 1), 0), 0.0),
+        ("negative tie at the overflow threshold", (0, 0, 0), (-T52 * 2, -(big - 1), 0), -(2.0 ** 970)),
+        ("huge products cancel, 3 units remain", (1, 0, -1), (T52 * 2, -T52 * 2, 0), 0.0),
+        ("huge products cancel to zero", (0, 0, 0), (big, -T52, -(big - T52)), 0.0),
+    ]
+    nr = len(rows)
+    Gi = np.zeros((nr, inner), dtype=object)
+    ge = np.zeros(inner, dtype=np.int64)
+    xi = np.zeros(inner, dtype=object)
+    xe = np.zeros(inner, dtype=np.int64)
+    for p, v in zip(lo, xl):
+        xi[p], xe[p], ge[p] = v, -537, -537
+    for p in hi:
+        xi[p], xe[p], ge[p] = 1, 511, 512 - 53
+    y0 = np.zeros(nr)
+    for r, (_, gl, gh, yv) in enumerate(rows):
+        for p, v in zip(lo, gl):
+            Gi[r, p] = v
+        for p, v in zip(hi, gh):
+            Gi[r, p] = v
+        y0[r] = yv
+    G, x = to_f64(Gi, ge[None, :]), to_f64(xi, xe)
+    sums = [sum(Fraction(int(Gi[r, t]) * int(xi[t])) * Fraction(2) ** int(ge[t] + xe[t]) for t in range(inner) if Gi[r, t])
+            for r in range(nr)]
+    with_y = [s + Fraction(float(v)) for s, v in zip(sums, y0)]
+    for r in range(nr):                                 # every product is exact for TwoProd
+        for t in range(inner):
+            p = Fraction(int(Gi[r, t]) * int(xi[t])) * Fraction(2) ** int(ge[t] + xe[t])
+            assert abs(p) < Fraction(2) ** 1024 and (p * Fraction(2) ** 1074).denominator == 1
+    return SimpleNamespace(inner=inner, names=[r[0] for r in rows], g=G, x=x, y0=y0, exact=sums, exact_with_y=with_y,
+                           want=np.array([round_nearest_even(s) for s in sums]),
+                           want_with_y=np.array([round_nearest_even(s) for s in with_y]))

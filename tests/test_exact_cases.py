@@ -1,0 +1,148 @@
+"""CPU tests of the constructed ExGEMV / ExGEMM cases (tests/exact_cases.py): the constructions meet their own
+conditions, and the oracle (and MPFR where built) returns the integer reference's bits on every output.  The integer
+reference shares no code with the library or the oracle; where the two disagree the oracle is wrong."""
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import exact_cases as X
+
+PLANTED_GEMM = [(40, 48, 35, 54, "tail"), (40, 48, 300, 100, "split"), (40, 48, 9000, 118, "head"),
+                (37, 50, 9000, 54, "split"), (13, 21, 300, 118, "tail"), (16, 16, 5, 100, "head")]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def test_round_nearest_even_and_classes():
+    assert X.round_nearest_even(2**53 + 1) == 2.0**53 and X.round_nearest_even(2**53 + 3) == 2.0**53 + 4
+    assert X.round_nearest_even(Fraction(3, 2**1075)) == 2 * 5e-324 and X.round_nearest_even(Fraction(1, 2**1075)) == 0.0
+    assert X.round_nearest_even(2**1024 - 2**971) == np.finfo(np.float64).max
+    assert X.round_nearest_even(2**1024 - 2**970) == np.inf and X.round_nearest_even(-(2**1024)) == -np.inf
+    assert X.classify(0)[0] == "zero" and X.classify(-(2**53 - 1) << 70)[0] == "exact"
+    assert X.classify((2**52 << 1) + 1) == ("tie", False) and X.classify(-((2**52 + 1) << 4) - 8) == ("tie", True)
+    assert X.classify(((2**53 - 1) << 4) + 8) == ("carry", True)
+    assert X.classify((2**52 << 4) + 9)[0] == "tie+1" and X.classify((2**52 << 4) + 7)[0] == "tie-1"
+    assert X.classify((2**52 << 4) + 3)[0] == "other"
+    with pytest.raises(AssertionError):
+        X.to_f64(X.obj([2**66 + 1]))                       # would silently round
+    with pytest.raises(AssertionError):
+        X.to_f64(X.obj([3]), -1075)                        # leaves the double range
+
+
+def test_moduli_table_and_worst_case_parameters():
+    bits = X.crt_bits()
+    assert X.crt_moduli(5) == [256, 255, 253, 251, 247] and len(bits) == X.CRT_LMAX + 1 == 40
+    assert bits[1:5] == [8, 15, 23, 31] and bits[39] == 285
+    assert bits[1:] == [8, 15, 23, 31, 39, 47, 55, 63, 71, 79, 87, 94, 102, 110, 117, 125, 132, 140, 147, 155, 162, 170,
+                        177, 184, 191, 198, 206, 213, 220, 226, 233, 240, 247, 253, 260, 266, 273, 279, 285]
+    ks = set()
+    for L in range(2, 37):
+        na, nb, k = X.crt_worst_params(L)
+        assert X.crt_need(na, nb, k) == bits[L] and X.crt_moduli_needed(na, nb, k) == L
+        assert 1 <= nb <= na <= 126 and (k > 1 or na <= 53)
+        ks.add(k)
+    assert {1, 2, 3, 16, 17, 8192, 8193} <= ks            # powers of two, one more, and the k-pass boundary
+
+
+@pytest.mark.parametrize("m,n,k,S,layout", PLANTED_GEMM)
+def test_planted_gemm_vs_oracle(oracle, m, n, k, S, layout):
+    c = X.planted_gemm(m, n, k, S, seed=1, layout=layout)
+    count = X.planted_mix(c)
+    assert (np.array([int(v) for v in c.a.ravel()], dtype=object) == c.a_int.ravel()).all()
+    assert (np.array([int(v) for v in c.b.ravel()], dtype=object) == c.b_int.ravel()).all()
+    if m >= 16:
+        assert count["zero"] >= n and count["exact"] > 0
+    assert (c.bits_a, c.bits_b) == (S + 4, S)              # 122 bits at S = 118: inside the 126 the int8 paths accept
+    # H and the deciding unit sit where the layout says (different k passes from k > 8192 on)
+    assert {"tail": c.pos["H"] == k - 2 and c.pos["d"] == k - 1, "split": c.pos["H"] == 0 and c.pos["d"] == k - 1,
+            "head": c.pos["d"] == 0 and c.pos["H"] == k - 1}[layout]
+    plain = c.a @ c.b                                       # what the suite's random data never shows: fp64 is wrong here
+    assert (plain != c.want).sum() > m * n // 8
+    for ta, tb in (("N", "N"), ("T", "T")):
+        a, lda = X.gemm_operand(c.a, ta, 1)
+        b, ldb = X.gemm_operand(c.b, tb, 2)
+        got = oracle.exgemm(ta, tb, m, n, k, 1.0, a, lda, b, ldb, 0.0, np.zeros(m * n), n, 0, mode=oracle.ROUND_EXACT)
+        bad = _bits(got) != _bits(c.want.reshape(-1))
+        assert not bad.any(), (ta, tb, c.classes.reshape(-1)[bad][:8], got[bad][:4], c.want.reshape(-1)[bad][:4])
+    if oracle.mpfr() is not None:
+        dots = oracle.mpfr_exgemm_dots(m, n, k, c.a.reshape(-1), k, c.b.reshape(-1), n)
+        assert (_bits(dots) == _bits(c.want)).all()
+
+
+@pytest.mark.parametrize("outputs,inner,S,layout,plant,beta", [
+    (40, 3001, 54, "split", None, 0), (48, 300, 100, "tail", "H", 1), (33, 3001, 118, "head", "d", 1),
+    (40, 35, 118, "split", "H", -0.75), (64, 2900, 54, "tail", "d", -0.75)])
+def test_planted_gemv_vs_oracle(oracle, outputs, inner, S, layout, plant, beta):
+    c = X.planted_gemv(outputs, inner, S, seed=2, layout=layout, plant=plant, beta=beta)
+    X.planted_mix(c)
+    assert [int(v) for v in c.g.ravel()] == c.g_int.ravel().tolist() and [int(v) for v in c.x] == c.x_int.tolist()
+    if plant:
+        assert [int(v) for v in c.y0] == c.y0_int.tolist() and (c.y0 != 0).sum() >= outputs // 3
+    for trans in ("N", "T"):
+        m, n, a, lda, xs, ys = X.gemv_operands(c.g, c.x, c.y0, trans, pad=3, offa=2, incx=2, offx=1, incy=3, offy=2)
+        got = oracle.exgemv(trans, m, n, 1.0, a, lda, xs, c.beta, ys, 0, incx=2, incy=3, offa=2, offx=1, offy=2,
+                            mode=oracle.ROUND_EXACT)
+        assert (_bits(got[2::3]) == _bits(c.want)).all(), (trans, c.classes[_bits(got[2::3]) != _bits(c.want)][:8])
+        if oracle.mpfr() is not None:
+            m, n, a, lda, xs, ys = X.gemv_operands(c.g, c.x, c.y0, trans)
+            assert (_bits(oracle.mpfr_exgemv(trans, m, n, 1.0, a, lda, xs, c.beta, ys)) == _bits(c.want)).all(), trans
+
+
+def test_crt_worst_cases_vs_oracle(oracle):
+    seen = set()
+    for L in range(2, 37):
+        c = X.crt_worst_case(L)
+        assert X.crt_need(c.na, c.nb, c.k) == X.crt_bits()[L]
+        # the operands really span na and nb bits, and every base-256 digit of the full entries is 255
+        assert (c.bits_a, c.bits_b) == (c.na, c.nb)
+        M = 1
+        for p in X.crt_moduli(L):
+            M *= p
+        assert 4 * c.top < M and (c.classes == "max").sum() >= 4
+        assert {int(v) for v in c.c_int.ravel()} >= {c.top, -c.top, 1, -1}
+        seen |= set(c.classes.ravel())
+        want = c.want.reshape(-1)
+        got = oracle.exgemm("N", "N", c.m, c.n, c.k, 1.0, c.a.reshape(-1), c.k, c.b.reshape(-1), c.n, 0.0,
+                            np.zeros(c.m * c.n), c.n, 0, mode=oracle.ROUND_EXACT)
+        assert (_bits(got) == _bits(want)).all(), (L, c.classes.reshape(-1)[_bits(got) != _bits(want)][:8])
+        if oracle.mpfr() is not None:
+            dots = oracle.mpfr_exgemm_dots(c.m, c.n, c.k, c.a.reshape(-1), c.k, c.b.reshape(-1), c.n)
+            assert (_bits(dots) == _bits(c.want)).all(), L
+    assert {"max", "zero", "exact", "other"} <= seen
+
+
+@pytest.mark.parametrize("k", [8192, 8193])
+def test_crt_wrap_case_vs_oracle(oracle, k):
+    c = X.crt_wrap_case(k)
+    body = np.array([[int(v) % 256 for v in row] for row in c.a_int]), np.array([[int(v) % 256 for v in row] for row in c.b_int])
+    assert (body[0] == 128).sum() == c.m * k - 1 and (body[1] == 128).sum() == c.n * k - 1
+    assert (c.bits_a, c.bits_b) == (12, 12)
+    got = oracle.exgemm("N", "N", c.m, c.n, k, 1.0, c.a.reshape(-1), k, c.b.reshape(-1), c.n, 0.0, np.zeros(c.m * c.n),
+                        c.n, 0, mode=oracle.ROUND_EXACT)
+    assert (_bits(got) == _bits(c.want.reshape(-1))).all()
+
+
+@pytest.mark.parametrize("inner", [12, 3000])
+def test_range_rows_gemv_vs_oracle(oracle, inner):
+    r = X.range_rows_gemv(inner)
+    tiny, dmax = 5e-324, np.finfo(np.float64).max
+    by_name = dict(zip(r.names, zip(r.want, r.want_with_y)))
+    assert by_name["subnormal 15 units"][0] == 15 * tiny and by_name["subnormal -2 units"][0] == -2 * tiny
+    assert by_name["largest subnormal"][0] == (2**52 - 1) * tiny and by_name["smallest normal"][0] == 2.0**-1022
+    assert by_name["partial sums overflow"][0] == 2.0**1023 and by_name["DBL_MAX"][0] == dmax
+    assert by_name["tie at the overflow threshold"][0] == np.inf
+    assert by_name["just below the overflow tie"] == (dmax, dmax)
+    assert by_name["negative tie at the overflow threshold"] == (-dmax, -np.inf)
+    assert by_name["huge products cancel, 3 units remain"][0] == 3 * tiny
+    assert not np.isnan(r.want).any() and not np.isnan(r.want_with_y).any()
+    for trans in ("N", "T"):
+        for beta, want in ((0.0, r.want), (1.0, r.want_with_y)):
+            m, n, a, lda, xs, ys = X.gemv_operands(r.g, r.x, r.y0, trans, pad=1)
+            got = oracle.exgemv(trans, m, n, 1.0, a, lda, xs, beta, ys, 0, mode=oracle.ROUND_EXACT)
+            assert (_bits(got) == _bits(want)).all(), (trans, beta, [r.names[i] for i in np.nonzero(_bits(got) != _bits(want))[0]])
+            if oracle.mpfr() is not None:
+                m, n, a, lda, xs, ys = X.gemv_operands(r.g, r.x, r.y0, trans)
+                assert (_bits(oracle.mpfr_exgemv(trans, m, n, 1.0, a, lda, xs, beta, ys)) == _bits(want)).all(), (trans, beta)

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from exact_cases import crt_moduli_needed as _crt_moduli_needed
+
 pytestmark = pytest.mark.gpu
 
 GEMV_VARIANTS = [(0, False), (2, False), (3, False), (4, False), (8, False), (4, True), (6, True), (8, True)]
@@ -132,19 +134,6 @@ def gemm_info(lib):
     v = (C.c_int * 8)()
     assert lib.exblas_last_gemm_info(v) == 0
     return (v[0], v[1], v[2], v[3], v[4]) if v[0] == 4 else (v[0], v[1], v[2])
-
-
-# cumulative bits of the residue path's moduli 256, 255, 253, 251, 247, 241, ... (floor(log2(product of the first L)))
-def _crt_moduli_needed(bits_a, bits_b, k):
-    from math import gcd
-    need = bits_a + bits_b + max(0, (k - 1).bit_length()) + 2
-    ps, prod, c = [], 1, 256
-    while prod.bit_length() - 1 < need:
-        if all(gcd(c, q) == 1 for q in ps):
-            ps.append(c)
-            prod *= c
-        c -= 1
-    return len(ps)
 
 
 @pytest.mark.parametrize("m,n,k", [(64, 64, 512), (130, 75, 1100), (16, 200, 33), (200, 260, 150), (257, 300, 70)])
@@ -649,7 +638,8 @@ def test_exgemm_mfma_fallbacks(ex, oracle, path):
 
 def test_gemv_gemm_randomized_soak(ex):
     """tools/stress_blas23.py: 180 random shapes / transposes / alpha, beta / leading dimensions / strides / offsets /
-    variants / data families for ExGEMV and ExGEMM (scalar and MFMA paths): bits equal to the oracle"""
+    variants / data families for ExGEMV and ExGEMM (scalar and MFMA paths): bits equal to the oracle; then 18 planted-tie
+    cases (tests/exact_cases.py) judged by the Python integer reference"""
     import os
     import subprocess
     import sys
@@ -657,6 +647,7 @@ def test_gemv_gemm_randomized_soak(ex):
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_blas23.py"), "180", "11"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "0 mismatches" in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
+    assert "+ 18 planted, 0 mismatches" in r.stdout, r.stdout[-3000:]
 
 
 def test_exgemm_mixed_digit_counts(ex, oracle):
@@ -718,7 +709,8 @@ def test_exgemm_randomized_soak(ex):
     """tools/stress_gemm.py: 120 random ExGEMM cases -- shapes with ragged tiles and k across the 8192-per-pass
     boundary, transposes, leading dimensions, alpha/beta, independently chosen operand families (every digit count
     1..16 and pairing: unrolled bodies, generic body, multi-pass, scalar fallback), both rounding modes, occasional
-    subnormal / huge entries: bits equal to the oracle (a 700-case run of the same tool: 0 mismatches)"""
+    subnormal / huge entries: bits equal to the oracle (a 700-case run of the same tool: 0 mismatches); then 12 planted-tie
+    cases (tests/exact_cases.py) judged by the Python integer reference in the exact rounding mode"""
     import os
     import subprocess
     import sys
@@ -726,7 +718,9 @@ def test_exgemm_randomized_soak(ex):
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_gemm.py"), "120", "7"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "0 mismatches" in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
+    assert "+ 12 planted, 0 mismatches" in r.stdout, r.stdout[-3000:]
     # the same cases with the residue path forced at every shape (by default it serves min(m, n) >= 192 only)
     r = subprocess.run([sys.executable, os.path.join(root, "tools", "stress_gemm.py"), "120", "8"],
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, EXBLAS_GEMM_PATH="4"))
     assert r.returncode == 0 and "0 mismatches" in r.stdout, (r.stdout[-3000:], r.stderr[-2000:])
+    assert "+ 12 planted, 0 mismatches" in r.stdout, r.stdout[-3000:]

@@ -1,5 +1,8 @@
 """Randomised soak of ExGEMV / ExGEMM against the oracle: python tools/stress_blas23.py [iterations] [seed].
-Random shapes, transposes, alpha/beta, leading dimensions, strides and variants; bits must equal the oracle's."""
+Random shapes, transposes, alpha/beta, leading dimensions, strides and variants; bits must equal the oracle's.
+After those cases (unchanged by this: it draws from a generator of its own) a `planted` family: iterations / 10 cases
+(at least 4) of tests/exact_cases.py's planted ties for ExGEMV ('N' / 'T', the half unit or the deciding unit planted in
+y through beta = 1 or -0.75, strides, offsets) and ExGEMM, judged by the Python integer reference."""
 import os
 import sys
 import time
@@ -65,5 +68,47 @@ for it in range(iters):
         print(f"MISMATCH it={it} {desc} kind={kind} fpe={fpe} ee={ee}", flush=True)
     if it % 40 == 0:
         print(f"it {it}: {desc} kind={kind} fpe={fpe}{'ee' if ee else ''} [{time.time() - t0:.0f} s]", flush=True)
-print(f"done: {iters} cases, {bad} mismatches, {fast} gemm cases on the MFMA path, {time.time() - t0:.0f} s")
+# planted ties: every output an exact tie, one unit off a tie or a carry into the next binade
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+try:
+    import exact_cases as xc  # noqa: E402
+except ImportError:                                # a tree without tests/exact_cases.py: the cases above are the whole run
+    xc = None
+    print("planted family not run: tests/exact_cases.py is not in this tree", flush=True)
+prng = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x71e5])
+planted = max(4, iters // 10) if xc else 0
+for it in range(planted):
+    S, layout = int(prng.choice([54, 61, 84, 100, 118])), str(prng.choice(xc.LAYOUTS))
+    if it % 3 != 2:
+        outputs = int(prng.integers(16, 600))
+        inner = int(prng.integers(5, 400)) if prng.random() < 0.5 else int(prng.integers(2000, 4000))
+        plant, beta = [(None, 0), ("H", 1), ("d", 1), ("H", -0.75), ("d", -0.75)][int(prng.integers(0, 5))]
+        case = xc.planted_gemv(outputs, inner, S, seed=it, layout=layout, plant=plant, beta=beta)
+        trans = str(prng.choice(["N", "T"]))
+        incx, incy = int(prng.choice([1, 1, 2])), int(prng.choice([1, 1, 3]))
+        offa, offx, offy = int(prng.integers(0, 3)), int(prng.integers(0, 3)), int(prng.integers(0, 3))
+        m, n, a, lda, x, y = xc.gemv_operands(case.g, case.x, case.y0, trans, pad=int(prng.integers(0, 4)), offa=offa,
+                                              incx=incx, offx=offx, incy=incy, offy=offy)
+        fpe, ee = gv_variants[int(prng.integers(0, len(gv_variants)))]
+        want = y.copy()
+        want[offy::incy] = case.want
+        ex.exgemv(trans, m, n, 1.0, a, lda, offa, x, incx, offx, case.beta, y, incy, offy, fpe, ee)
+        ok = (bits(y) == bits(want)).all()
+        desc = f"gemv {trans} m={m} n={n} lda={lda} inc={incx},{incy} off={offa},{offx},{offy} S={S} {layout} plant={plant} b={beta}"
+    else:
+        m, n, k = int(prng.integers(1, 200)), int(prng.integers(16, 200)), int(prng.integers(5, 400))
+        ta, tb = str(prng.choice(["N", "T"])), str(prng.choice(["N", "T"]))
+        case = xc.planted_gemm(m, n, k, S, seed=it, layout=layout)
+        a, lda = xc.gemm_operand(case.a, ta, int(prng.integers(0, 3)))
+        b, ldb = xc.gemm_operand(case.b, tb, int(prng.integers(0, 3)))
+        fpe, ee = gm_variants[int(prng.integers(0, len(gm_variants)))]
+        c = np.zeros(m * n)
+        ex.exgemm(ta, tb, m, n, k, 1.0, a, lda, b, ldb, 0.0, c, n, fpe, ee)
+        fast += lib.exblas_last_gemm_slices() >= 2
+        ok = (bits(c) == bits(case.want.reshape(-1))).all()
+        desc = f"gemm {ta}{tb} m={m} n={n} k={k} ld={lda},{ldb} S={S} {layout} slices={lib.exblas_last_gemm_slices()}"
+    if not ok:
+        bad += 1
+        print(f"MISMATCH planted it={it} {desc} fpe={fpe} ee={ee}", flush=True)
+print(f"done: {iters} cases + {planted} planted, {bad} mismatches, {fast} gemm cases on the MFMA path, {time.time() - t0:.0f} s")
 sys.exit(1 if bad else 0)

@@ -3,7 +3,10 @@ EXBLAS_GEMM_PATH=4 in the environment forces the residue path (blas3_crt.hip) at
 Random shapes (ragged tiles, k across the 8192-per-pass boundary), transposes, leading dimensions, alpha/beta, operand
 families chosen independently for A and B (so every digit count 1..16 and every pairing occurs: unrolled bodies,
 generic body, multi-pass, scalar fallback), both rounding modes, now and then a non-finite or subnormal entry.
-Bits must equal the oracle's."""
+Bits must equal the oracle's.
+After those cases (unchanged by this: it draws from a generator of its own) a `planted` family: iterations / 10 cases
+(at least 4) of tests/exact_cases.py's planted ties with random shape, S, layout and transposes, judged by the Python
+integer reference (exact rounding) or the oracle (reference rounding)."""
 import ctypes as C
 import os
 import sys
@@ -79,7 +82,42 @@ for it in range(iters):
         print(f"MISMATCH it={it} {desc} ({int((bits(c) != bits(want)).sum())} entries)", flush=True)
     if it % 50 == 0:
         print(f"it {it}: {desc} [{time.time() - t0:.0f} s]", flush=True)
+# planted ties: every output an exact tie, one unit off a tie, a carry into the next binade, zero or a short exact value
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+try:
+    import exact_cases as xc  # noqa: E402
+except ImportError:                                # a tree without tests/exact_cases.py: the cases above are the whole run
+    xc = None
+    print("planted family not run: tests/exact_cases.py is not in this tree", flush=True)
+prng = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 1, 0x71e5])
+planted = max(4, iters // 10) if xc else 0
+for it in range(planted):
+    big_k = prng.random() < 0.15
+    m, n = int(prng.integers(1, 150)), int(prng.integers(16, 150))
+    k = int(prng.integers(8100, 9300)) if big_k else int(prng.integers(5, 700))
+    if big_k:
+        m, n = min(m, 40), min(n, 48)
+    S, layout = int(prng.choice([54, 61, 84, 100, 118])), str(prng.choice(xc.LAYOUTS))
+    ta, tb = str(prng.choice(["N", "T"])), str(prng.choice(["N", "T"]))
+    case = xc.planted_gemm(m, n, k, S, seed=it, layout=layout, ea=int(prng.integers(-60, 61)), eb=int(prng.integers(-60, 61)))
+    a, lda = xc.gemm_operand(case.a, ta, int(prng.integers(0, 3)))
+    b, ldb = xc.gemm_operand(case.b, tb, int(prng.integers(0, 3)))
+    mode = int(prng.integers(0, 2))
+    fpe, ee = variants[int(prng.integers(0, len(variants)))]
+    want = case.want.reshape(-1) if mode == 0 else o.exgemm(ta, tb, m, n, k, 1.0, a, lda, b, ldb, 0.0, np.zeros(m * n), n, 0, mode=1)
+    lib.exblas_set_round_mode(mode)
+    c = np.zeros(m * n)
+    ex.exgemm(ta, tb, m, n, k, 1.0, a, lda, b, ldb, 0.0, c, n, fpe, ee)
+    v = (C.c_int * 8)()
+    lib.exblas_last_gemm_info(v)
+    key = (v[0], v[1], v[2])
+    paths[key] = paths.get(key, 0) + 1
+    if not (bits(c) == bits(want)).all():
+        bad += 1
+        wrong = bits(c) != bits(want)
+        print(f"MISMATCH planted it={it} gemm {ta}{tb} m={m} n={n} k={k} S={S} {layout} mode={mode} fpe={fpe}{'ee' if ee else ''} "
+              f"path={key} ({int(wrong.sum())} entries: {sorted(set(case.classes.reshape(-1)[wrong].tolist()))})", flush=True)
 lib.exblas_set_round_mode(0)
 print("paths (impl, digits or bits of A, of B): count ->", dict(sorted(paths.items())))
-print(f"done: {iters} cases, {bad} mismatches, {time.time() - t0:.0f} s")
+print(f"done: {iters} cases + {planted} planted, {bad} mismatches, {time.time() - t0:.0f} s")
 sys.exit(1 if bad else 0)
