@@ -44,6 +44,8 @@ C_ABI_SYMBOLS = [
     "exblas_reserve_workspace_ctx", "exblas_workspace_bytes_ctx", "exblas_last_gemm_info_ctx",
     "exblas_exspmv_csr_dev", "exblas_exspmv_csr_ctx", "exblas_exspmv_csr", "exblas_set_spmv_path",
     "exblas_last_spmv_info",
+    "exblas_exspmm_csr_dev", "exblas_exspmm_csr_ctx", "exblas_exspmm_csr", "exblas_set_spmm_path",
+    "exblas_last_spmm_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -169,6 +171,12 @@ def load_library():
     L.exblas_set_spmv_path.argtypes = [i32]
     L.exblas_set_spmv_path.restype = None
     L.exblas_last_spmv_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exspmm_csr_dev.argtypes = [i32, i32, i32, i32, vp, vp, vp, dbl, vp, i64, dbl, vp, i64, i32, i32, vp]
+    L.exblas_exspmm_csr_ctx.argtypes = [vp] + L.exblas_exspmm_csr_dev.argtypes
+    L.exblas_exspmm_csr.argtypes = [i32, i32, i32, i32, vp, vp, vp, dbl, vp, i64, dbl, vp, i64, i32, i32]
+    L.exblas_set_spmm_path.argtypes = [i32]
+    L.exblas_set_spmm_path.restype = None
+    L.exblas_last_spmm_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -420,6 +428,82 @@ def last_spmv_info():
     return tuple(int(v) for v in out)
 
 
+def _spmm_check(A, X, Y):
+    """Validates a device ExSpMM call before anything is launched; returns (crow, col, val, X, m, n, k, index_bits, Y)."""
+    torch = _torch()
+    crow, col, val, m, n = _csr_parts(A)
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"exspmm: {name} must be a torch tensor")
+    if val.dtype != torch.float64 or X.dtype != torch.float64:
+        raise TypeError("exspmm: values and X must be float64")
+    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
+        raise TypeError("exspmm: row pointers and column indices must both be int32 or both int64")
+    if X.dim() == 1:
+        raise ValueError("exspmm: X must be 2-D (n x k); for one vector use exspmv_dev")
+    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1 or X.dim() != 2:
+        raise ValueError("exspmm: crow, col and val must be 1-D and X 2-D")
+    if crow.numel() != m + 1:
+        raise ValueError(f"exspmm: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
+    if col.numel() != val.numel():
+        raise ValueError("exspmm: col and val differ in length")
+    if X.shape[0] < n:
+        raise ValueError(f"exspmm: X has {X.shape[0]} rows, fewer than n = {n}")
+    k = int(X.shape[1])
+    if Y is not None:
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.dim() != 2 or tuple(Y.shape) != (m, k):
+            raise ValueError(f"exspmm: Y must be a 2-D float64 tensor of shape ({m}, {k})")
+        if m > 0 and k > 0 and (Y.stride(1) != 1 or (m > 1 and Y.stride(0) < k)):
+            raise ValueError("exspmm: Y is updated in place: it needs stride(1) == 1 and stride(0) >= k")
+    _require_gpu()
+    dev = val.device
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)) + ((("Y", Y),) if Y is not None else ()):
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"exspmm: {name} must be on the GPU, on the device of the values")
+    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
+    if k > 0 and X.shape[0] > 0 and (X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < k)):
+        X = X.contiguous()
+    if Y is None:
+        Y = torch.zeros((m, k), dtype=torch.float64, device=dev)
+    return crow, col, val, X, m, n, k, (32 if crow.dtype == torch.int32 else 64), Y
+
+
+def _ld(t, k):
+    """Leading dimension of a row-major 2-D tensor with unit column stride (a single row: k)."""
+    return max(int(t.stride(0)), k) if t.shape[0] > 1 else k
+
+
+def _spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha, beta, fpe, early_exit):
+    return (m, n, k, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
+            float(alpha), C.c_void_p(X.data_ptr()), _ld(X, k), float(beta), C.c_void_p(Y.data_ptr()), _ld(Y, k),
+            int(fpe), int(bool(early_exit)))
+
+
+def exspmm_dev(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+    """ExSpMM: Y = Round(alpha A X + beta Y) output by output, exact and reproducible, stream-ordered on the current
+    stream; column j is bit for bit exspmv_dev(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_dev; X a 2-D float64
+    tensor with at least n rows (row-major: a copy is made when X.stride(1) != 1, otherwise ldx = X.stride(0)); Y (m x k,
+    stride(1) == 1, stride(0) >= k) is updated in place, or allocated (zeros) when None."""
+    torch = _torch()
+    crow, col, val, X, m, n, k, bits, Y = _spmm_check(A, X, Y)
+    _check(load_library().exblas_exspmm_csr_dev(*_spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha, beta, fpe,
+                                                            early_exit), _stream_ptr(torch)), "exspmm_dev")
+    return Y
+
+
+def set_spmm_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from an integer accumulator, 2 in-register rounding wherever
+    certified (no row split), 3 every row split at a small chunk.  Same bits on every path."""
+    load_library().exblas_set_spmm_path(int(mode))
+
+
+def last_spmm_info():
+    """(outputs rounded in registers, outputs rounded from an accumulator, rows split, chunks) of the last ExSpMM."""
+    out = (C.c_int64 * 4)()
+    _check(load_library().exblas_last_spmm_info(out), "last_spmm_info")
+    return tuple(int(v) for v in out)
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Methods mirror the ``*_dev``
@@ -507,6 +591,14 @@ class Context:
                                                     C.c_void_p(y.data_ptr()), int(fpe), int(bool(early_exit)),
                                                     _stream_ptr(torch)), "exspmv_ctx")
         return y
+
+    def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+        torch = _torch()
+        crow, col, val, X, m, n, k, bits, Y = _spmm_check(A, X, Y)
+        _check(load_library().exblas_exspmm_csr_ctx(self.handle, *_spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha,
+                                                                             beta, fpe, early_exit),
+                                                    _stream_ptr(torch)), "exspmm_ctx")
+        return Y
 
     def workspace_bytes(self):
         return load_library().exblas_workspace_bytes_ctx(self.handle)
@@ -644,6 +736,41 @@ def exspmv(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
     _check(load_library().exblas_exspmv_csr(m, n, bits, p(crow), p(col), p(val), float(alpha), p(x), float(beta),
                                             p(y), int(fpe), int(bool(early_exit))), "exspmv")
     return y
+
+
+def exspmm(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+    """ExSpMM on host arrays: A = (row_ptr, col_idx, val, (m, n)) as numpy arrays (as for exspmv), X float64 of shape
+    (rows >= n, k); returns Y (a new m x k float64 array; the Y passed in is not changed)."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError("exspmm: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
+    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
+    if len(shape) != 2:
+        raise ValueError("exspmm: shape must be (m, n)")
+    m, n = int(shape[0]), int(shape[1])
+    X = np.asarray(X)
+    if val.dtype != np.float64 or X.dtype != np.float64:
+        raise TypeError("exspmm: values and X must be float64")
+    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
+        raise TypeError("exspmm: row pointers and column indices must both be int32 or both int64")
+    if X.ndim == 1:
+        raise ValueError("exspmm: X must be 2-D (n x k); for one vector use exspmv")
+    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or X.ndim != 2:
+        raise ValueError("exspmm: row_ptr, col_idx and val must be 1-D and X 2-D")
+    if crow.size != m + 1 or col.size != val.size or X.shape[0] < n:
+        raise ValueError("exspmm: inconsistent sizes of row_ptr / col_idx / val / X")
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError("exspmm: row_ptr entries must lie in [0, nnz]")
+    k = int(X.shape[1])
+    Y = np.zeros((m, k)) if Y is None else np.array(Y, dtype=np.float64, copy=True, order="C")
+    if Y.shape != (m, k):
+        raise ValueError(f"exspmm: Y must have shape ({m}, {k})")
+    _require_gpu()
+    crow, col, val, X = (np.ascontiguousarray(a) for a in (crow, col, val, X))
+    bits = 32 if crow.dtype == np.int32 else 64
+    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    _check(load_library().exblas_exspmm_csr(m, n, k, bits, p(crow), p(col), p(val), float(alpha), p(X), k, float(beta),
+                                            p(Y), k, int(fpe), int(bool(early_exit))), "exspmm")
+    return Y
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

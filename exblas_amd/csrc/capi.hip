@@ -99,6 +99,7 @@ static void init_ctx(Ctx &c, int device, int layer)
         c.grid_adj = z.grid_adj;
         c.ngroups = z.ngroups; c.gemm_path = z.gemm_path;
         c.spmv_path = z.spmv_path;
+        c.spmm_path = z.spmm_path;
         c.gemm_max_slices = z.gemm_max_slices;
         c.gemm_max_moduli = z.gemm_max_moduli;
     }
@@ -479,6 +480,31 @@ int exblas_last_spmv_info(int64_t *out4)
     return 0;
 }
 
+void exblas_set_spmm_path(int mode)
+{
+    ctx(-1);
+    for_each_layer(current_device(), [&](Ctx &c) {
+        std::lock_guard<std::mutex> lk(c.mu);
+        c.spmm_path = (mode >= 0 && mode <= 3) ? mode : 0;
+    });
+}
+
+// out[0] outputs rounded in registers, out[1] outputs rounded from an accumulator, out[2] rows split across workgroups,
+// out[3] chunks of the split rows; read from the device (synchronises)
+int exblas_last_spmm_info(int64_t *out4)
+{
+    if (!out4) return (int)hipErrorInvalidValue;
+    Ctx &c = ctx(-1, g_last_layer[current_device()]);
+    std::lock_guard<std::mutex> lk(c.mu);
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (!c.spmm_info_dev) return -1;
+    long long h[8];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(h, c.spmm_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
+    return 0;
+}
+
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
                                hipStream_t st)
@@ -525,6 +551,20 @@ static int exspmv_on(Ctx &c, int m, int n, int index_bits, const void *d_row_ptr
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exspmv_dispatch(c, m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe,
                                 early_exit, round_mode(), st);
+}
+
+static int exspmm_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                     const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
+                     int64_t ldy, int fpe, int early_exit, hipStream_t st)
+{
+    if (m < 0 || n < 0 || k < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
+    if (ldx < k || ldy < k) return (int)hipErrorInvalidValue;
+    if (m == 0 || k == 0) return 0;
+    if (!d_row_ptr || !d_y || (n > 0 && !d_x)) return (int)hipErrorInvalidValue;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exspmm_dispatch(c, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy,
+                                fpe, early_exit, round_mode(), st);
 }
 
 static int extrsv_on(Ctx &c, char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x,
@@ -605,6 +645,14 @@ int exblas_exspmv_csr_dev(int m, int n, int index_bits, const void *d_row_ptr, c
 {
     return exspmv_on(ctx(-1), m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe, early_exit,
                      (hipStream_t)stream);
+}
+
+int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                          const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
+                          int64_t ldy, int fpe, int early_exit, void *stream)
+{
+    return exspmm_on(ctx(-1), m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
+                     early_exit, (hipStream_t)stream);
 }
 
 int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x, int incx,
@@ -752,6 +800,15 @@ int exblas_exspmv_csr_ctx(exblas_ctx_t *h, int m, int n, int index_bits, const v
                      (hipStream_t)stream);
 }
 
+int exblas_exspmm_csr_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, const void *d_row_ptr,
+                          const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
+                          double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return exspmm_on(*cp, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
+                     early_exit, (hipStream_t)stream);
+}
+
 int exblas_extrsv_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x,
                       int incx, int fpe, int early_exit, void *stream)
 {
@@ -842,6 +899,7 @@ int exblas_release_workspace(void)
         c.ws_bytes = 0;
         c.gemm_info_dev = nullptr;  // it pointed into the workspace
         c.spmv_info_dev = nullptr;
+        c.spmm_info_dev = nullptr;
     });
     return (int)first;
 }
@@ -1232,6 +1290,52 @@ int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const v
                        (const double *)(d + b_rp + b_ci + b_val), beta, d_y, fpe, early_exit, c.stream);
     if (rc) die("exblas_exspmv_csr", (hipError_t)rc, __FILE__, __LINE__);
     EXB_CHECK(hipMemcpyAsync(y, d_y, (size_t)m * 8, hipMemcpyDeviceToHost, c.stream));
+    EXB_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
+}
+
+int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                      double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
+                      int early_exit)
+{
+    if (m < 0 || n < 0 || k < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
+    if (ldx < k || ldy < k) return (int)hipErrorInvalidValue;
+    if (m == 0 || k == 0) return 0;
+    if (!row_ptr || !y || (n > 0 && !x)) return (int)hipErrorInvalidValue;
+    // the entries the call reads: [0, max row_ptr); a negative row_ptr entry is refused
+    const size_t isz = index_bits / 8;
+    long long nnz = 0;
+    for (int i = 0; i <= m; ++i) {
+        const long long v = index_bits == 32 ? (long long)((const int32_t *)row_ptr)[i] : ((const int64_t *)row_ptr)[i];
+        if (v < 0) return (int)hipErrorInvalidValue;
+        if (v > nnz) nnz = v;
+    }
+    if (nnz > 0 && (!col_idx || !val)) return (int)hipErrorInvalidValue;
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    // whole rows of X and Y travel, padding included (the last row only up to its k-th entry)
+    const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)k : 0;
+    const size_t yspan = (size_t)(m - 1) * (size_t)ldy + (size_t)k;
+    const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
+                 b_val = align_up((size_t)nnz * 8), b_x = align_up(xspan * 8), b_y = align_up(yspan * 8);
+    char *d;
+    {
+        std::lock_guard<std::mutex> lk(c.mu);
+        d = (char *)stage_buf(c, 0, b_rp + b_ci + b_val + b_x + b_y);
+        EXB_CHECK(hipMemcpyAsync(d, row_ptr, (size_t)(m + 1) * isz, hipMemcpyHostToDevice, c.stream));
+        if (nnz > 0) {
+            EXB_CHECK(hipMemcpyAsync(d + b_rp, col_idx, (size_t)nnz * isz, hipMemcpyHostToDevice, c.stream));
+            EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci, val, (size_t)nnz * 8, hipMemcpyHostToDevice, c.stream));
+        }
+        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
+        EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val + b_x, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
+    }
+    double *d_y = (double *)(d + b_rp + b_ci + b_val + b_x);
+    int rc = exspmm_on(c, m, n, k, index_bits, d, d + b_rp, (const double *)(d + b_rp + b_ci), alpha,
+                       (const double *)(d + b_rp + b_ci + b_val), ldx, beta, d_y, ldy, fpe, early_exit, c.stream);
+    if (rc) die("exblas_exspmm_csr", (hipError_t)rc, __FILE__, __LINE__);
+    // the padding of Y comes back as it went
+    EXB_CHECK(hipMemcpyAsync(y, d_y, yspan * 8, hipMemcpyDeviceToHost, c.stream));
     EXB_CHECK(hipStreamSynchronize(c.stream));
     return 0;
 }

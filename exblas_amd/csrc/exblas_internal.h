@@ -39,6 +39,9 @@ struct Ctx {
     int spmv_path = 0;       // exblas_set_spmv_path: 0 automatic, 1 accumulator finish for every row, 2 in-register
                              // rounding wherever certified (no row split), 3 every row split at a small chunk
     const long long *spmv_info_dev = nullptr;  // header of the last ExSpMV call's workspace (exblas_last_spmv_info)
+    int spmm_path = 0;       // exblas_set_spmm_path: 0 automatic, 1 every output rounded from an integer accumulator,
+                             // 2 in-register rounding wherever certified (no row split), 3 every row split at a small chunk
+    const long long *spmm_info_dev = nullptr;  // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -105,6 +108,11 @@ hipError_t exgemm_dispatch(Ctx &c, char transa, char transb, int m, int n, int k
 hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
                            const double *val, double alpha, const double *x, double beta, double *y, int fpe,
                            int early_exit, int round_mode, hipStream_t st);
+
+// spmm.hip
+hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                           const double *val, double alpha, const double *x, long long ldx, double beta, double *y,
+                           long long ldy, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

@@ -19,24 +19,9 @@
 //                     row's global accumulator (order-free)
 //   k_spmv_long_finish one wave per long row: beta terms, finish_wave, store
 // fpe == 1 runs the same structure with plain fp64 sums (the non-reproducible baseline).
-#include "superacc.hip.h"
-#include "fpe.hip.h"
-#include "exblas_internal.h"
+#include "spmv_common.hip.h"
 
 namespace exb {
-
-constexpr int SP_BLOCK = 256;
-constexpr int SP_WAVES = SP_BLOCK / 64;
-constexpr int SP_N = 4;              // expansion size of every fpe >= 2 (and 0): the bits do not depend on it
-constexpr int SP_G_SHORT = 8;        // lanes per short row
-constexpr long long SP_SHORT_MAX = 64;     // entries of a short row (<= 8 per lane)
-constexpr long long SP_LONG_MIN = 16384;   // rows longer than this are split
-constexpr long long SP_CHUNK = 4096;       // entries per wave of a split row
-constexpr long long SP_CHUNK_SMALL = 16;   // path 3: split every row at this chunk
-constexpr long long SP_LCAP = 16384;       // long-row accumulator slots (beyond: the row runs as a medium row)
-constexpr unsigned SP_SPILL = 128u;        // row flag: something went to the row's integer accumulator
-constexpr int SP_HDR = 8;                  // header words: [0] medium rows [1] long rows [2] chunks, [4..7] info
-constexpr int SP_ACC_FLAGS = NL + 3;       // word of a long row's accumulator that holds its flags
 
 struct RowSink {
     long long *col;   // the row's 68 limbs in LDS
@@ -49,61 +34,6 @@ struct RowSink {
     __device__ __forceinline__ void note(unsigned bits) { flags |= bits | SP_SPILL; }
 };
 
-template <class I>
-__device__ __forceinline__ I ld_nt(const I *p) { return __builtin_nontemporal_load(p); }
-
-// fl(alpha * x[c]) for an in-range column; a column outside [0, n) is never read and makes the row NaN
-template <class I>
-__device__ __forceinline__ double gather_x(const double *__restrict__ x, I c, int n, double alpha, unsigned &flags)
-{
-    if ((unsigned long long)(long long)c < (unsigned long long)n) return alpha * x[c];
-    flags |= FLAG_NAN | SP_SPILL;
-    return 0.0;
-}
-
-// Certified round-to-nearest-even of the exact value of an expansion f (any N terms, finite, |f| < 2^1012).
-// Two error-free VecSum passes leave S = f0 + f1 + sum_{i>=2} f_i exactly; res + q = f0 + f1 exactly (TwoSum).  Then
-// |S - res| <= |q| + sum_{i>=2} |f_i|.  When that is below half the spacing of the doubles next to res (a quarter of
-// ulp(res) when |res| is a power of two: the spacing below it is halved), res is the unique nearest double, so
-// RN(S) = res: no tie is possible.  The bound on the tail is taken twice over (fp rounding of the |f_i| sum, and the
-// absolute error of subnormal partials, are far below that margin for |res| >= 2^-960).  Returns false whenever it
-// cannot decide (near-ties, ties, |res| < 2^-960 or >= 2^1020, a zero head over non-zero terms): the caller then rounds
-// the exact accumulator.  Sound, not complete.
-template <int N>
-__device__ __forceinline__ bool spmv_round_fast(double (&f)[N], double &out)
-{
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-        for (int i = N - 1; i >= 1; --i) {
-            double s;
-            f[i - 1] = two_sum(f[i - 1], f[i], s);
-            f[i] = s;
-        }
-    }
-    double q;
-    const double res = two_sum(f[0], f[1], q);
-    double tail = 0.0;
-    bool any = f[0] != 0.0 || f[1] != 0.0;
-#pragma unroll
-    for (int i = 2; i < N; ++i) {
-        tail += __builtin_fabs(f[i]);
-        any |= f[i] != 0.0;
-    }
-    if (!any) {
-        out = 0.0;   // the exact sum is zero: +0.0, as the accumulator rounds it
-        return true;
-    }
-    const unsigned ef = expo_field(res);
-    if (ef < 1023u - 960u || ef >= 1023u + 1020u) return false;
-    const bool pow2 = (((unsigned long long)__double_as_longlong(res)) & 0x000fffffffffffffull) == 0;
-    // half = ulp(res) / 2 = 2^(E - 53), a quarter ulp for a power of two
-    const double half = __longlong_as_double((long long)((unsigned long long)(ef - (pow2 ? 54u : 53u)) << 52));
-    if (!(tail <= half * 0x1p-32)) return false;
-    if (!(__builtin_fabs(q) < half - half * 0x1p-30)) return false;
-    out = res;
-    return true;
-}
 
 // ---------------------------------------------------------------------------------------------
 // classification
@@ -270,46 +200,8 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
 }
 
 // ---------------------------------------------------------------------------------------------
-// long rows: chunk bases, chunks, finish
+// long rows: chunks, finish (the chunk bases come from k_spmv_long_prep, spmv_common.hip.h)
 // ---------------------------------------------------------------------------------------------
-template <class I>
-__global__ void __launch_bounds__(1024) k_spmv_long_prep(const I *__restrict__ rp, const int *__restrict__ lrows,
-                                                         int lcap, long long chunk, long long *__restrict__ hdr,
-                                                         long long *__restrict__ lbase)
-{
-    __shared__ long long part[1024];
-    __shared__ long long carry;
-    const int tid = threadIdx.x;
-    const long long nl = min(hdr[1], (long long)lcap);
-    if (tid == 0) carry = 0;
-    __syncthreads();
-    for (long long b = 0; b < nl; b += 1024) {
-        const long long i = b + tid;
-        long long k = 0;
-        if (i < nl) {
-            const int r = lrows[i];
-            const long long len = max(0ll, (long long)rp[r + 1] - (long long)rp[r]);
-            k = (len + chunk - 1) / chunk;
-        }
-        part[tid] = k;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {   // inclusive Hillis-Steele scan
-            const long long t = tid >= o ? part[tid - o] : 0;
-            __syncthreads();
-            part[tid] += t;
-            __syncthreads();
-        }
-        if (i < nl) lbase[i] = carry + part[tid] - k;
-        __syncthreads();
-        if (tid == 0) carry += part[1023];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        lbase[nl] = carry;
-        hdr[2] = carry;
-    }
-}
-
 template <bool PLAIN, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restrict__ rp, const I *__restrict__ ci,
                                                        const double *__restrict__ val, double alpha,
@@ -425,7 +317,6 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__rest
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 template <bool PLAIN, class I>
 static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, const double *val, double alpha,

@@ -132,7 +132,10 @@ int exblas_reserve_workspace(size_t bytes);
 /* Bytes the *_dev layer's workspace holds right now on the current device (the parked blocks not included).  Footprint of
  * the residue path of exgemm: 39 bytes per entry of B, of a 2048-row chunk of A and of a 2048-row chunk of C --
  * 8192^3: 3.7 GiB, 16384^3: 12.2 GiB; the digit-slice path: 16 bytes per entry of A and B (+ 40 per entry of C when more
- * than one pass can be needed). */
+ * than one pass can be needed).  ExSpMM: 1024 + 4 m + 8 ceil(m / r) t + 12 L + 576 k L bytes (each term rounded up to 256),
+ * r = 64 / min(64, k rounded up to a power of two) rows per wave, t = ceil(k / 64) column tiles (one bitmap word per 64
+ * outputs), L = min(m, floor(32 MiB / (576 k))) accumulator slots for split rows: at most 32 MiB whatever k is; rows
+ * past L run whole. */
 size_t exblas_workspace_bytes(void);
 /* Frees the workspace blocks that later, larger calls replaced.  Synchronises the device; only call it when no graph
  * captured before the growth will be replayed again. */
@@ -233,6 +236,33 @@ void exblas_set_spmv_path(int mode);
  * accumulator (fallback), out[2] rows split across workgroups, out[3] chunks of those rows (all 0 for fpe == 1).
  * Synchronises the device; valid until the next call that uses the workspace; -1 when unknown. */
 int exblas_last_spmv_info(int64_t *out4);
+/* ExSpMM: exact, reproducible Y = alpha A X + beta Y for an m x n CSR matrix A (as for ExSpMV) and dense ROW-MAJOR blocks
+ * X (at least n rows, k columns, leading dimension ldx >= k) and Y (m x k, ldy >= k, updated in place) on device
+ * pointers.  Column j of Y is, bit for bit, what exblas_exspmv_csr_dev gives for (A, X[:, j], alpha, beta, Y[:, j]):
+ *     Y[i, j] = Round( sum_p val[p] * fl(alpha * X[col_idx[p], j])  (+)  beta * Y[i, j] )
+ * with everything said there: both rounding modes, alpha folded into X by a rounded multiply, beta = 0 ignores Y (NaN
+ * included), beta = 1 adds it exactly, any other beta adds the error-free product, ExGEMV's product domain and
+ * non-finite rules, empty rows, duplicate columns count, the entry order is irrelevant.  A column index outside [0, n)
+ * is never dereferenced and makes that whole row of Y NaN (all k entries).  The bits depend on the data only: not on k,
+ * the column tiling, ldx / ldy, fpe (0 or >= 2), early_exit, the internal path, the grid, the index width or the order
+ * of the rows.  fpe == 1 is the plain, non-reproducible fp64 product on the same structure.  The padding between k and
+ * ldy in Y is never written.  X and Y must not overlap.  All offsets (row * ld) are 64-bit.
+ * m == 0 or k == 0: success, nothing is launched.  m, n, k < 0, ldx < k, ldy < k, index_bits other than 32 / 64 or
+ * fpe < 0: hipErrorInvalidValue.  Stream-ordered launches only (classification on the device, no host synchronisation,
+ * the context workspace): capturable into a hipGraph after exblas_reserve_workspace or one call with the same (m, k).
+ * Returns 0 or a hipError_t. */
+int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                          const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
+                          int64_t ldy, int fpe, int early_exit, void *stream);
+/* Test hook for ExSpMM (same bits on every path): 0 automatic, 1 every output rounded from an integer accumulator,
+ * 2 outputs rounded in registers wherever the rounding test certifies it (no row is split), 3 every row split into
+ * small chunks (16 entries per group of lanes) across waves, as long as the accumulator budget has a slot for it (see
+ * exblas_workspace_bytes). */
+void exblas_set_spmm_path(int mode);
+/* The most recent ExSpMM on this device: out[0] outputs (i, j) rounded in registers, out[1] outputs rounded from an
+ * integer accumulator after the main kernel deferred them, out[2] rows split across workgroups, out[3] chunks of those
+ * rows.  Synchronises the device; valid until the next call that uses the workspace; -1 when unknown. */
+int exblas_last_spmm_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -281,6 +311,9 @@ int exblas_exgemm_ctx(exblas_ctx_t *ctx, char transa, char transb, int m, int n,
 int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, double beta,
                           double *d_y, int fpe, int early_exit, void *stream);
+int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
+                          const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
+                          double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
 int exblas_reserve_workspace_ctx(exblas_ctx_t *ctx, size_t bytes);
 size_t exblas_workspace_bytes_ctx(exblas_ctx_t *ctx);
 int exblas_last_gemm_info_ctx(exblas_ctx_t *ctx, int *out8);
@@ -403,6 +436,12 @@ int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, c
  * synchronous.  Returns 0 or hipErrorInvalidValue (also for a negative row_ptr entry). */
 int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
                       double alpha, const double *x, double beta, double *y, int fpe, int early_exit);
+/* exblas_exspmm_csr_dev on host arrays (X: n rows of ldx, Y: m rows of ldy, updated in place; the padding of Y keeps
+ * its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue (also for a negative row_ptr
+ * entry). */
+int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                      double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
+                      int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
