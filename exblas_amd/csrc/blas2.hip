@@ -28,6 +28,19 @@ constexpr int GV_TICKET_STRIDE = 4096 + 256;  // bytes between two ticket counte
 // 'N', expansion path: two rows per lane, x staged in LDS.  For the matrices k_gemvN_fpe_sx cannot stream with 16-byte
 // loads (odd m or lda, or a misaligned A).
 // ---------------------------------------------------------------------------------------------
+// The sink of a lane's second row.  The last lane of an odd m has no second row: its products are 0 * x_k, which is NaN
+// for an infinite x_k, and what the range guard then sinks must not reach another row's accumulator (it used to reach
+// row 0's).  The test sits on the spill / guard path only, not in the cascade.
+struct SecondRowSink {
+    GlobalSink g;
+    bool on;
+    __device__ __forceinline__ void note(unsigned) {}
+    __device__ __forceinline__ void add(double x)
+    {
+        if (on) g.add(x);
+    }
+};
+
 template <int N, bool EE>
 __global__ void __launch_bounds__(GV_BLOCK) k_gemvN_fpe(int m, int n, double alpha, const double *__restrict__ a,
                                                         long long lda, const double *__restrict__ x, long long incx,
@@ -44,7 +57,8 @@ __global__ void __launch_bounds__(GV_BLOCK) k_gemvN_fpe(int m, int n, double alp
     double f0[N], f1[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) f0[i] = f1[i] = 0.0;
-    GlobalSink s0{ws + (v0 ? r0 : 0) * SET_WORDS}, s1{ws + (v1 ? r0 + 1 : 0) * SET_WORDS};
+    GlobalSink s0{ws + (v0 ? r0 : 0) * SET_WORDS};
+    SecondRowSink s1{{ws + (v1 ? r0 + 1 : 0) * SET_WORDS}, v1};
 
     for (int kc = k0; kc < k1; kc += GV_KC) {
         const int cnt = min(GV_KC, k1 - kc);

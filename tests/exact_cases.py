@@ -1,4 +1,5 @@
-"""Constructed ExGEMV / ExGEMM inputs whose exact results are known as Python integers, and the integer reference.
+"""Constructed ExGEMV / ExGEMM / ExSpMV / ExSpMM inputs whose exact results are known as Python integers, and the
+integer reference.
 
 Nothing here touches the GPU, the library or the oracle: operands are built as Python integers (``dtype=object``
 matrices) times powers of two, the exact result is ``ndarray.dot`` on those object arrays, and the expected double is
@@ -460,3 +461,285 @@ def range_rows_gemv(inner=12):
     return SimpleNamespace(inner=inner, names=[r[0] for r in rows], g=G, x=x, y0=y0, exact=sums, exact_with_y=with_y,
                            want=np.array([round_nearest_even(s) for s in sums]),
                            want_with_y=np.array([round_nearest_even(s) for s in with_y]))
+
+
+# ---------------------------------------------------------------------------------------------
+# sparse views: the constructed rows as CSR (ExSpMV / ExSpMM)
+# ---------------------------------------------------------------------------------------------
+def csr_from_rows(g, x, itype=np.int64, n_cols=None, spread=False, zeros="keep", dup=None, shuffle=False, seed=0):
+    """The dense constructed G (outputs x inner, float64) and x (inner, or inner x k for ExSpMM) as CSR: returns
+    (crow, col, val, xs, n_cols).
+
+    The columns are an injective random map of the positions along a row into [0, n_cols), n_cols >= inner (the default
+    leaves about a sixth of the columns unused), so the indices are unsorted within a row.  The entries are stored in
+    the order of the positions -- a layout's leading, H and d entries stay where the layout puts them, in whichever
+    lane and chunk that is -- or in a random order with shuffle = True.  With spread = True every row has its own map
+    and x is scattered once per row (n_cols >= outputs * inner), otherwise all rows share one.  Every entry (row) of xs
+    that no stored entry refers to holds NaN.  zeros = "keep" stores the explicit zeros of G (every row has exactly
+    `inner` entries), "drop" leaves them out (the lengths then mix).  dup = a position along the row: the entry there
+    is stored as two entries of the same column whose values add up to it exactly (duplicate columns each count); the
+    second one goes to the end of the row, which is one entry longer."""
+    g, x = np.asarray(g, dtype=np.float64), np.asarray(x, dtype=np.float64)
+    outputs, inner = g.shape
+    assert x.shape[0] == inner and x.ndim in (1, 2) and zeros in ("keep", "drop")
+    rng = np.random.default_rng([seed, outputs, inner, int(spread)])
+    used = inner * (outputs if spread else 1)
+    n_cols = max(int(n_cols or 0), used + used // 5 + 3)
+    perm = rng.permutation(n_cols)
+    xs = np.full((n_cols,) + x.shape[1:], np.nan)
+    cols, vals, crow = [], [], [0]
+    for i in range(outputs):
+        cmap = perm[i * inner:(i + 1) * inner] if spread else perm[:inner]
+        pos = np.arange(inner) if zeros == "keep" else np.nonzero(g[i])[0]
+        c, v = cmap[pos], g[i, pos]
+        xs[c] = x[pos]
+        if dup is not None and (pos == dup).any():
+            at = int(np.nonzero(pos == dup)[0][0])
+            first = np.trunc(v[at] / 2)
+            rest = v[at] - first
+            assert first + rest == v[at] and Fraction(float(first)) + Fraction(float(rest)) == Fraction(float(v[at]))
+            v = np.concatenate([v, [rest]])
+            v[at] = first
+            c = np.concatenate([c, [c[at]]])
+        order = rng.permutation(len(v)) if shuffle else np.arange(len(v))
+        cols.append(c[order])
+        vals.append(v[order])
+        crow.append(crow[-1] + len(v))
+    col = np.concatenate(cols) if cols else np.zeros(0, dtype=np.int64)
+    val = np.concatenate(vals) if vals else np.zeros(0)
+    assert n_cols < np.iinfo(itype).max and crow[-1] < np.iinfo(itype).max
+    return np.array(crow, dtype=itype), col.astype(itype), val, xs, n_cols
+
+
+def csr_dense_int(crow, col, val, xs):
+    """The exact products of a CSR matrix with integer-valued entries against xs, row by row, as Python integers (the
+    converter's round trip: every stored entry counts, duplicates included; an unreferenced NaN must not be read)."""
+    out = []
+    for i in range(len(crow) - 1):
+        a, b = int(crow[i]), int(crow[i + 1])
+        xv = xs[col[a:b]]
+        assert not np.isnan(xv).any()
+        out.append(sum(int(v) * int(w) for v, w in zip(val[a:b].tolist(), xv.tolist())))
+    return obj(out) if out else np.zeros(0, dtype=object)
+
+
+def planted_spmm(rows, kcols, inner, S, seed=0, layout="tail", plant=None, beta=0):
+    """planted_gemm(kcols, rows, inner, S) as an ExSpMM: the sparse matrix is B^T (rows x inner, dense here: g_int / g,
+    to be stored by csr_from_rows), X = A^T (inner x kcols, row-major) and Y = (A B)^T, so that every output is a planted
+    class.  From kcols >= 16 on column 3 cancels to exactly zero and column kcols - 2 is a short exact value.  `plant` =
+    'H' or 'd' moves that term of every output into Y0 (planted_gemv's options: beta = 1 with Y0 = the term, or
+    beta = -3/4 with Y0 = -4 term and -2 term left in the product); with beta = 0, Y0 holds NaN."""
+    c = planted_gemm(kcols, rows, inner, S, seed=seed, layout=layout)
+    G, Xi = c.b_int.T.copy(), c.a_int.T.copy()
+    beta = Fraction(beta)
+    y0 = np.zeros((rows, kcols), dtype=object)
+    if plant is not None:
+        assert beta in (1, Fraction(-3, 4))
+        p = c.pos[plant]
+        term = np.outer(G[:, p], Xi[p, :])
+        if beta == 1:
+            y0, Xi[p, :] = term, 0
+        else:
+            y0, Xi[p, :] = term * -4, Xi[p, :] * -2
+    else:
+        assert beta == 0
+    y_int = gemm_exact(G, Xi)
+    if beta != 0:
+        t = [[Fraction(beta) * int(v) + int(s) for v, s in zip(r0, r1)] for r0, r1 in zip(y0, y_int)]
+        assert all(v.denominator == 1 for r in t for v in r)
+        y_int = obj([[int(v) for v in r] for r in t])
+    assert (y_int == c.c_int.T).all()
+    y0f = to_f64(y0) if beta != 0 else np.full((rows, kcols), np.nan)
+    return SimpleNamespace(rows=rows, kcols=kcols, inner=inner, S=S, layout=layout, plant=plant, beta=float(beta), g_int=G,
+                           x_int=Xi, y0_int=y0, g=to_f64(G), x=to_f64(Xi), y0=y0f, c_int=y_int, c_exp=0,
+                           classes=c.classes.T.copy(), tie_up=c.tie_up.T.copy(), want=np.ascontiguousarray(c.want.T), pos=c.pos)
+
+
+COMPLETE_CLASSES = ("tie", "tie_odd", "carry", "tie+1", "tie-1")
+
+
+def split53(v):
+    """an integer as a list of integers of at most 53 significant bits each that add up to it"""
+    sign, c, out = (-1 if v < 0 else 1), abs(int(v)), []
+    while c:
+        sh = max(0, c.bit_length() - 53)
+        piece = (c >> sh) << sh
+        out.append(sign * piece)
+        c -= piece
+    return out
+
+
+def complete_to(T, cls, gap):
+    """Terms that move the integer partial sum T to a chosen class: an exact tie whose kept mantissa is even (``tie``)
+    or odd (``tie_odd``: round-to-even goes away from zero), a tie under 53 ones (``carry``), or one deciding unit above
+    / below a tie in magnitude (``tie+1`` / ``tie-1``) with that unit `gap` >= 1 bits below the half unit.  The leading
+    53 bits of T are kept (but for their last bit, or all ones for ``carry``); what T holds below them is cancelled.
+
+    Returns a namespace: `terms` (integers of at most 53 significant bits, ceil(low / 53) + 1 of them at most, low the
+    number of bits of the scaled T below the half unit; ``carry`` may take one more), `scale` (T counts in units of
+    2^-scale of the terms: a short T is shifted up so that the deciding unit is an integer), `unit` (the deciding unit
+    is 2^unit) and `total` = (T << scale) + sum(terms), whose class in units of 2^unit is asserted."""
+    assert cls in COMPLETE_CLASSES and gap >= 1
+    T = int(T)
+    sign, a = (-1 if T < 0 else 1), abs(T)
+    scale = max(0, gap + 54 - a.bit_length()) if a else 0
+    a <<= scale
+    if a == 0:
+        a = 1 << (gap + 53)
+    sh = a.bit_length() - 53
+    mant = a >> sh
+    if cls == "tie":
+        mant &= ~1
+    elif cls == "tie_odd":
+        mant = (mant | 1) - (2 if mant | 1 == (1 << 53) - 1 else 0)      # (53 ones would be the carry class)
+    elif cls == "carry":
+        mant = (1 << 53) - 1
+    d = {"tie+1": 1, "tie-1": -1}.get(cls, 0)
+    unit = sh - 1 - gap
+    assert unit >= 0
+    total = sign * ((mant << sh) + (1 << (sh - 1)) + d * (1 << unit))
+    terms = split53(total - (T << scale))
+    assert len(terms) <= -(-(sh - 1) // 53) + (2 if cls == "carry" else 1), (len(terms), sh)
+    assert (T << scale) + sum(terms) == total and total % (1 << unit) == 0
+    got, up = classify(total >> unit)
+    assert got == ("tie" if cls == "tie_odd" else cls) and (cls not in ("tie", "tie_odd") or up == (cls == "tie_odd"))
+    return SimpleNamespace(terms=terms, scale=scale, unit=unit, total=total)
+
+
+INEXACT_CLOSE = 4                      # positions along the row that complete_to's terms take (x = 1 there)
+_INEXACT_CLASSES = ("tie", "tie+1", "tie_odd", "tie-1", "carry")
+
+
+def planted_inexact(outputs, inner, S, seed=0, layout="tail", beta=0):
+    """Rows G (outputs x inner) against one x whose two leading products are a * b with a, b odd integers of 40 to 53
+    random bits -- up to 106 bits wide, so fl(a b) is inexact and the TwoProd error term carries bits of the result --
+    then small exact products u v 2^f, and INEXACT_CLOSE positions with x = 1 that hold complete_to's terms: output j
+    is of class (tie, tie+1, tie to odd, tie-1, carry)[j % 5], negative where j % 3 == 1, with the deciding unit
+    gap = S - 34 bits below the half unit (as in planted_gemm).  `layout` moves the leading products and the closing
+    terms along the row as in planted_gemm.  Every operand is an integer; `unit[j]` is the deciding unit of output j
+    as a power of two.  beta = -3/4 adds beta y0 with y0_j = +-4 W_j 2^50, W_j odd of exactly 53 bits: 3 W_j has 54 or 55
+    bits, so TwoProd(beta, y0_j) has a non-zero error term too, about as large as the half unit of the result; with
+    beta = 0, y0 holds NaN."""
+    assert inner >= 2 + INEXACT_CLOSE and S >= 35 and outputs >= 15
+    beta = Fraction(beta)
+    assert beta in (0, Fraction(-3, 4))
+    rng = np.random.default_rng([seed, outputs, inner, S, 77])
+    gap, nf = S - 34, inner - 2 - INEXACT_CLOSE
+
+    def wide():
+        bits = int(rng.integers(40, 54))
+        return (int(rng.integers(0, 1 << 62)) % (1 << (bits - 1))) | (1 << (bits - 1)) | 1
+
+    x = np.zeros(inner, dtype=object)
+    x[0], x[1] = wide(), -wide()
+    x[2:2 + nf] = obj(rng.integers(-8, 9, nf))
+    x[2 + nf:] = 1
+    G = np.zeros((outputs, inner), dtype=object)
+    y0 = np.zeros(outputs, dtype=object)
+    units = []
+    for j in range(outputs):
+        row = np.zeros(inner, dtype=object)
+        row[0], row[1] = wide(), wide() * (1 if j % 2 else -1)
+        f = rng.integers(0, 51, nf)
+        row[2:2 + nf] = obj(rng.integers(-8, 9, nf)) * obj([1 << int(s) for s in f])
+        yj = 0
+        if beta != 0:
+            yj = (4 * ((int(rng.integers(0, 1 << 52)) | (1 << 52) | 1)) << 50) * (1 if j % 4 < 2 else -1)
+        T = int(row.dot(x)) - 3 * (yj // 4)
+        if (T < 0) != (j % 3 == 1):
+            row, yj, T = -row, -yj, -T
+        fix = complete_to(T, _INEXACT_CLASSES[j % 5], gap)
+        row = row * (1 << fix.scale)
+        row[2 + nf:2 + nf + len(fix.terms)] = fix.terms
+        G[j], y0[j] = row, yj << fix.scale
+        units.append(fix.unit)
+        assert int(row.dot(x)) - 3 * (int(y0[j]) // 4) == fix.total
+    lead = [0, 1]
+    rnd, close = list(range(2, 2 + nf)), list(range(2 + nf, inner))
+    half = len(rnd) // 2
+    order = {"tail": lead + rnd + close,
+             "split": close[:1] + rnd[:half] + lead + rnd[half:] + close[1:],
+             "head": close[:1:-1] + rnd[:half] + lead + rnd[half:] + close[1::-1]}[layout]
+    assert sorted(order) == list(range(inner))
+    G, x = G[:, order], x[order]
+    c_int = gemv_exact(G, x, beta, y0)
+    for row in G:                                        # ExGEMV's product domain: multiples of 2^-1074 below 2^1024
+        assert all(abs(int(v) * int(w)) < 1 << 1024 for v, w in zip(row, x))
+    reduced = obj([int(v) >> u for v, u in zip(c_int, units)])
+    assert all(int(v) % (1 << u) == 0 for v, u in zip(c_int, units))
+    cls, up = classify_all(reduced)
+    gf, xf = to_f64(G), to_f64(x)
+    with np.errstate(over="ignore"):                     # the error terms are there: fl(a b) != a b in the leading products
+        p = gf[:, order.index(0)] * xf[order.index(0)]
+    assert all(int(v) != int(G[j, order.index(0)]) * int(x[order.index(0)]) for j, v in enumerate(p.tolist()))
+    pos = {"lead": order.index(0), "dup": order.index(1), "close": [order.index(q) for q in close]}
+    y0f = to_f64(y0) if beta != 0 else np.full(outputs, np.nan)
+    if beta != 0:                                        # ... and fl(beta y0) != beta y0
+        assert all(Fraction(float(beta) * v) != beta * int(w) for v, w in zip(y0f.tolist(), y0))
+    return SimpleNamespace(outputs=outputs, inner=inner, S=S, layout=layout, beta=float(beta), y0_int=y0, y0=y0f,
+                           g_int=G, x_int=x, g=gf, x=xf, c_int=reduced,
+                           c_exact=c_int, unit=units, classes=cls, tie_up=up, want=rounded(c_int), pos=pos)
+
+
+ADVERSARIAL_WINDOWS = (60, 120, 200, 400)
+
+
+def adversarial_rows(count, seed=0):
+    """`count` CSR rows of 1 to 200 entries with private columns: integers of 1 to 53 random bits times powers of two
+    spread over a window of 60, 120, 200 or 400 bits, against x = +-2^t (every product is exact).  A random subset of
+    the entries of some rows is stored a second time, negated, elsewhere in the row (exact cancellation), and every
+    second row that is long enough is closed by complete_to (class and gap in 1 .. 70 at random; its terms against
+    x = 1).  Two rows in five have 56 to 72 entries before that, so the lengths straddle 64.  Every operand and product
+    is a multiple of 2^-1074 below 2^1000 (and at least 2^-930, so that halving x is exact on the result).  Returns crow, col (int64), val, xs, n_cols, want (Fraction-rounded),
+    classes, lens and the exact sums as (integer, exponent) pairs."""
+    rng = np.random.default_rng([seed, count, 4242])
+    vals, xvals, crow, want, classes, exact = [], [], [0], [], [], []
+    for r in range(count):
+        n = int(rng.integers(56, 73)) if r % 5 < 2 else int(rng.integers(1, 191))
+        W = ADVERSARIAL_WINDOWS[int(rng.integers(0, 4))]
+        close = r % 2 == 1 and n >= 4
+        base = int(rng.integers(-900, 480 - W))
+        bits = rng.integers(1, 54, n)
+        mant = [(int(rng.integers(0, 1 << 62)) % (1 << (int(b) - 1))) | (1 << (int(b) - 1)) for b in bits]
+        sgn = rng.choice((-1, 1), n)
+        ve = base + rng.integers(0, W, n)
+        t = rng.integers(-30, 31, n)
+        xs_sgn = rng.choice((-1, 1), n)
+        ent = [(int(s) * m, int(e), int(xs_), int(tt)) for s, m, e, xs_, tt in zip(sgn, mant, ve, xs_sgn, t)]
+        if r % 3 == 0 and n >= 2:                       # exact cancellation: the entry again, negated
+            twice = [q for q in ent if rng.random() < 0.35][:(200 - 10 - n)]
+            ent += [(-m, e, xs_, tt) for m, e, xs_, tt in twice]
+        lo = min(e + tt for _, e, _, tt in ent)
+        T = sum((m * xs_) << (e + tt - lo) for m, e, xs_, tt in ent)
+        cls_name = None
+        if close:
+            cls_name = COMPLETE_CLASSES[int(rng.integers(0, 5))]
+            fix = complete_to(T, cls_name, int(rng.integers(1, 71)))
+            assert lo - fix.scale >= -1074
+            for term in fix.terms:
+                tz = (term & -term).bit_length() - 1
+                ent.append((term >> tz, lo - fix.scale + tz, 1, 0))
+            T, lo = fix.total >> fix.unit, lo - fix.scale + fix.unit
+        order = rng.permutation(len(ent))
+        ent = [ent[int(q)] for q in order]
+        assert 1 <= len(ent) <= 200
+        for m, e, xs_, tt in ent:                       # operands and products: multiples of 2^-1074 below 2^1000
+            assert e >= -1074 and e + tt - 1 >= -1074      # (ExSpMM also runs x / 2)
+            assert abs(m).bit_length() + e < 1000 and abs(m).bit_length() + e + tt + 1 < 1000 and abs(m).bit_length() <= 53
+            vals.append(math.ldexp(float(m), e))
+            xvals.append(math.ldexp(float(xs_), tt))
+        crow.append(crow[-1] + len(ent))
+        cname = classify(T)[0]
+        assert cls_name is None or cname == ("tie" if cls_name == "tie_odd" else cls_name)
+        classes.append(cname)
+        exact.append((T, lo))
+        want.append(round_nearest_even(Fraction(T) * Fraction(2) ** lo))
+    nnz = crow[-1]
+    n_cols = nnz + nnz // 7 + 5
+    col = rng.permutation(n_cols)[:nnz].astype(np.int64)
+    xs = np.full(n_cols, np.nan)
+    xs[col] = xvals
+    lens = np.diff(crow)
+    assert count < 500 or ((lens < 64).any() and (lens == 64).any() and (lens == 65).any() and (lens > 72).any())
+    return SimpleNamespace(count=count, crow=np.array(crow, dtype=np.int64), col=col, val=np.array(vals), xs=xs, n_cols=n_cols,
+                           want=np.array(want), classes=np.array(classes, dtype=object), lens=lens, exact=exact)

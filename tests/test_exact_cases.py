@@ -1,4 +1,4 @@
-"""CPU tests of the constructed ExGEMV / ExGEMM cases (tests/exact_cases.py): the constructions meet their own
+"""CPU tests of the constructed ExGEMV / ExGEMM cases and their sparse views (tests/exact_cases.py): the constructions meet their own
 conditions, and the oracle (and MPFR where built) returns the integer reference's bits on every output.  The integer
 reference shares no code with the library or the oracle; where the two disagree the oracle is wrong."""
 from fractions import Fraction
@@ -146,3 +146,159 @@ def test_range_rows_gemv_vs_oracle(oracle, inner):
             if oracle.mpfr() is not None:
                 m, n, a, lda, xs, ys = X.gemv_operands(r.g, r.x, r.y0, trans)
                 assert (_bits(oracle.mpfr_exgemv(trans, m, n, 1.0, a, lda, xs, beta, ys)) == _bits(want)).all(), (trans, beta)
+
+
+# ---------------------------------------------------------------------------------------------
+# sparse views (ExSpMV / ExSpMM): the oracle is called per row / per output, on the stored entries and the gathered x
+# ---------------------------------------------------------------------------------------------
+from test_gpu_spmm import _oracle_outputs  # noqa: E402  (plain helpers: nothing in them touches the GPU)
+from test_gpu_spmv import _oracle_rows  # noqa: E402
+
+
+def _mpfr_rows(oracle, crow, col, val, xs, beta, y0):
+    out = np.empty(len(crow) - 1)
+    for i in range(len(out)):
+        a, b = int(crow[i]), int(crow[i + 1])
+        out[i] = oracle.mpfr_exgemv("N", 1, b - a, 1.0, val[a:b], 1, np.ascontiguousarray(xs[col[a:b]]), beta, y0[i:i + 1])[0]
+    return out
+
+
+@pytest.mark.parametrize("cls", X.COMPLETE_CLASSES)
+def test_complete_to(cls):
+    rng = np.random.default_rng(5)
+    for T in [0, 1, -1, 2**53 - 1, -(2**53 - 1), 2**105 + 12345, -(2**400 + 2**17 + 1)] + \
+             [int(rng.integers(-2**62, 2**62)) << int(rng.integers(0, 300)) for _ in range(40)]:
+        for gap in (1, 2, 20, 29, 30, 31, 70, 84):
+            fix = X.complete_to(T, cls, gap)               # (asserts the class of the total itself)
+            assert all(abs(t) >> ((abs(t) & -abs(t)).bit_length() - 1) < 2**53 for t in fix.terms)
+            assert (T << fix.scale) + sum(fix.terms) == fix.total and (T < 0) == (fix.total < 0)
+            low = abs(fix.total).bit_length() - 54         # bits below the half unit
+            assert len(fix.terms) <= -(-low // 53) + (2 if cls == "carry" else 1)
+            got = X.classify(fix.total >> fix.unit)
+            assert got[0] == {"tie_odd": "tie"}.get(cls, cls)
+            if cls in ("tie", "tie_odd"):
+                assert got[1] == (cls == "tie_odd")
+            # the deciding unit is `gap` bits below the half unit: half an ulp of the rounded total is 2^(unit + gap)
+            assert (abs(fix.total).bit_length() - 54) - fix.unit == gap
+            X.to_f64(X.obj(fix.terms))
+
+
+@pytest.mark.parametrize("outputs,inner,S,layout,plant,beta", [
+    (40, 27, 54, "split", None, 0), (48, 70, 63, "head", "H", 1), (33, 300, 118, "tail", "d", -0.75),
+    (32, 4200, 64, "split", "d", 1)])
+def test_csr_from_rows_vs_oracle(oracle, outputs, inner, S, layout, plant, beta):
+    c = X.planted_gemv(outputs, inner, S, seed=3, layout=layout, plant=plant, beta=beta)
+    X.planted_mix(c)
+    y0 = c.y0 if beta else np.full(outputs, np.nan)
+    seen = set()
+    for kw in (dict(), dict(itype=np.int32, spread=True), dict(zeros="drop"), dict(dup=c.pos["lead"]),
+               dict(itype=np.int32, zeros="drop", dup=c.pos["lead"], spread=True, shuffle=True, n_cols=3 * outputs * inner)):
+        crow, col, val, xs, n_cols = X.csr_from_rows(c.g, c.x, seed=4, **kw)
+        assert crow.dtype == col.dtype == kw.get("itype", np.int64) and len(xs) == n_cols >= inner
+        assert n_cols >= kw.get("n_cols", 0) and 0 <= col.min() and col.max() < n_cols
+        lens = np.diff(crow)
+        if kw.get("zeros") != "drop":
+            assert (lens == inner + (1 if "dup" in kw else 0)).all()
+        else:
+            assert lens.min() <= 5 and len(set(lens.tolist())) > 1       # the carry rows: 4 non-zeros
+        ref = np.zeros(n_cols, dtype=bool)
+        ref[col] = True
+        assert np.isnan(xs[~ref]).all() and (~ref).sum() >= n_cols // 7 and not np.isnan(xs[ref]).any()
+        for i in range(outputs):                            # injective within a row (but for the duplicate), unsorted
+            cc = col[crow[i]:crow[i + 1]]
+            assert len(set(cc.tolist())) == len(cc) - (1 if "dup" in kw else 0)
+        assert (np.diff(col[crow[0]:crow[1]]) < 0).any()
+        if not kw.get("shuffle") and kw.get("zeros") != "drop":   # the layout's positions are the stored positions
+            assert (val[crow[5]:crow[5] + inner][[c.pos["H"], c.pos["d"]]] == c.g[5, [c.pos["H"], c.pos["d"]]]).all()
+        if kw.get("spread"):
+            assert set(col[crow[0]:crow[1]].tolist()).isdisjoint(col[crow[1]:crow[2]].tolist())
+        # the converter's round trip in Python integers (beta y0 apart), then the oracle on the stored entries
+        prod = X.csr_dense_int(crow, col, val, xs)
+        assert (prod == X.gemv_exact(c.g_int, c.x_int)).all()
+        got = _oracle_rows(oracle, crow, col, val, xs, 1.0, c.beta, y0, mode=oracle.ROUND_EXACT)
+        assert (_bits(got) == _bits(c.want)).all(), (kw, c.classes[_bits(got) != _bits(c.want)][:8])
+        if oracle.mpfr() is not None and inner <= 300:
+            assert (_bits(_mpfr_rows(oracle, crow, col, val, xs, c.beta, c.y0)) == _bits(c.want)).all(), kw
+        seen.add(_bits(got).tobytes())
+    assert len(seen) == 1                                   # drop, dup and spread do not change the result
+
+
+@pytest.mark.parametrize("rows,kcols,inner,S,layout,plant,beta", [
+    (27, 1, 5, 54, "tail", None, 0), (40, 3, 27, 63, "split", "H", 1), (33, 17, 64, 64, "head", "d", -0.75),
+    (20, 33, 65, 90, "split", None, 0), (17, 65, 1025, 118, "head", "H", -0.75)])
+def test_planted_spmm_vs_oracle(oracle, rows, kcols, inner, S, layout, plant, beta):
+    c = X.planted_spmm(rows, kcols, inner, S, seed=5, layout=layout, plant=plant, beta=beta)
+    count = X.planted_mix(c)
+    if kcols >= 16:
+        assert count["zero"] >= rows and (c.classes[:, 3] == "zero").all() and (c.classes[:, kcols - 2] == "exact").any()
+    assert c.want.shape == (rows, kcols) and (c.c_int == X.gemm_exact(c.g_int, c.x_int) +
+                                               [[Fraction(c.beta) * int(v) for v in r] for r in c.y0_int]).all()
+    assert np.isnan(c.y0).all() if beta == 0 else (c.y0 != 0).sum() >= rows * kcols // 3
+    for kw in (dict(), dict(itype=np.int32, zeros="drop", dup=c.pos["lead"], spread=True)):
+        crow, col, val, Xd, n_cols = X.csr_from_rows(c.g, c.x, seed=6, **kw)
+        assert Xd.shape == (n_cols, kcols)
+        got = _oracle_outputs(oracle, crow, col, val, Xd, 1.0, c.beta, c.y0, mode=oracle.ROUND_EXACT)
+        bad = _bits(got) != _bits(c.want)
+        assert not bad.any(), (kw, c.classes[bad][:8])
+    if oracle.mpfr() is not None and inner <= 65:
+        for j in range(kcols):
+            y0 = np.ascontiguousarray(c.y0[:, j]) if beta else np.zeros(rows)
+            w = _mpfr_rows(oracle, crow, col, val, np.ascontiguousarray(Xd[:, j]), c.beta, y0)
+            assert (_bits(w) == _bits(c.want[:, j])).all(), j
+
+
+@pytest.mark.parametrize("outputs,inner,S,layout,beta", [
+    (40, 6, 54, "tail", 0), (64, 27, 63, "split", -0.75), (45, 300, 64, "head", 0), (30, 5000, 118, "split", -0.75),
+    (35, 70, 90, "tail", -0.75)])
+def test_planted_inexact_vs_oracle(oracle, outputs, inner, S, layout, beta):
+    c = X.planted_inexact(outputs, inner, S, seed=7, layout=layout, beta=beta)
+    X.planted_mix(c)
+    assert (X.gemv_exact(c.g_int, c.x_int, Fraction(beta), c.y0_int) == c.c_exact).all()
+    assert np.isnan(c.y0).all() if beta == 0 else (np.abs(c.y0) >= 2.0**104).all()
+    assert all(int(v) == int(r) << u for v, r, u in zip(c.c_exact, c.c_int, c.unit))
+    plain = c.g @ c.x + (beta * c.y0 if beta else 0.0)
+    assert (plain != c.want).sum() > outputs // 8          # fp64 is wrong here
+    seen = set()
+    for kw in (dict(), dict(itype=np.int32, zeros="drop", dup=c.pos["lead"], spread=True)):
+        crow, col, val, xs, n_cols = X.csr_from_rows(c.g, c.x, seed=8, **kw)
+        got = _oracle_rows(oracle, crow, col, val, xs, 1.0, c.beta, c.y0, mode=oracle.ROUND_EXACT)
+        assert (_bits(got) == _bits(c.want)).all(), (kw, c.classes[_bits(got) != _bits(c.want)][:8])
+        if oracle.mpfr() is not None and inner <= 300:
+            y0 = c.y0 if beta else np.zeros(outputs)
+            assert (_bits(_mpfr_rows(oracle, crow, col, val, xs, c.beta, y0)) == _bits(c.want)).all(), kw
+        seen.add(_bits(got).tobytes())
+    assert len(seen) == 1
+
+
+def test_adversarial_rows_vs_oracle(oracle):
+    a = X.adversarial_rows(1500, seed=9)
+    assert a.lens.min() >= 1 and a.lens.max() <= 200 and {63, 64, 65} <= set(a.lens.tolist())
+    cls = a.classes
+    for name in ("tie", "carry", "tie+1", "tie-1", "other"):
+        assert (cls == name).sum() >= 50, name
+    assert 4 * ((cls == "tie") | (cls == "carry")).sum() >= a.count
+    ref = np.zeros(a.n_cols, dtype=bool)
+    ref[a.col] = True
+    assert np.isnan(a.xs[~ref]).all() and not np.isnan(a.xs[ref]).any() and len(set(a.col.tolist())) == len(a.col)
+    for i in (0, 1, 2, 3, 700, 1499):                       # the expected values, recomputed from the stored doubles
+        s = sum(Fraction(float(v)) * Fraction(float(w)) for v, w in
+                zip(a.val[a.crow[i]:a.crow[i + 1]], a.xs[a.col[a.crow[i]:a.crow[i + 1]]]))
+        assert s == Fraction(a.exact[i][0]) * Fraction(2) ** a.exact[i][1] and X.round_nearest_even(s) == a.want[i]
+    got = _oracle_rows(oracle, a.crow, a.col, a.val, a.xs, 1.0, 0.0, np.full(a.count, np.nan), mode=oracle.ROUND_EXACT)
+    bad = _bits(got) != _bits(a.want)
+    assert not bad.any(), (cls[bad][:8], np.nonzero(bad)[0][:8])
+    if oracle.mpfr() is not None:
+        assert (_bits(_mpfr_rows(oracle, a.crow, a.col, a.val, a.xs, 0.0, np.zeros(a.count))) == _bits(a.want)).all()
+    for scale in (-1.0, 2.0, 0.5):                          # the columns ExSpMM runs: exact scalings of x
+        w = _oracle_rows(oracle, a.crow, a.col, a.val, a.xs * scale, 1.0, 0.0, np.zeros(a.count), mode=oracle.ROUND_EXACT)
+        assert (_bits(w) == _bits(a.want * scale)).all(), scale
+
+
+def test_range_rows_as_csr_vs_oracle(oracle):
+    for inner in (12, 20000):
+        r = X.range_rows_gemv(inner)
+        for kw in (dict(), dict(zeros="drop", itype=np.int32)):
+            crow, col, val, xs, n_cols = X.csr_from_rows(r.g, r.x, seed=10, **kw)
+            for beta, want in ((0.0, r.want), (1.0, r.want_with_y)):
+                got = _oracle_rows(oracle, crow, col, val, xs, 1.0, beta, r.y0, mode=oracle.ROUND_EXACT)
+                assert (_bits(got) == _bits(want)).all(), (inner, kw, beta)
