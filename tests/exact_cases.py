@@ -1,5 +1,5 @@
-"""Constructed ExGEMV / ExGEMM / ExSpMV / ExSpMM inputs whose exact results are known as Python integers, and the
-integer reference.
+"""Constructed ExGEMV / ExGEMM / ExSpMV / ExSpMM / ExTRSV inputs whose exact results are known as Python integers (for
+ExTRSV: from a Fraction substitution), and the integer reference.
 
 Nothing here touches the GPU, the library or the oracle: operands are built as Python integers (``dtype=object``
 matrices) times powers of two, the exact result is ``ndarray.dot`` on those object arrays, and the expected double is
@@ -743,3 +743,307 @@ def adversarial_rows(count, seed=0):
     assert count < 500 or ((lens < 64).any() and (lens == 64).any() and (lens == 65).any() and (lens > 72).any())
     return SimpleNamespace(count=count, crow=np.array(crow, dtype=np.int64), col=col, val=np.array(vals), xs=xs, n_cols=n_cols,
                            want=np.array(want), classes=np.array(classes, dtype=object), lens=lens, exact=exact)
+
+
+# ---------------------------------------------------------------------------------------------
+# ExTRSV: planted totals along a substitution chain
+# ---------------------------------------------------------------------------------------------
+TRSV_BLOCK = 64                        # rows per block-row of the kernel: the anchors open every block of this size
+TRSV_GAPS = (1, 30, 110, 250)          # bits between the half unit and the deciding unit: inside one double, inside the
+#                                        three register levels, below them, far below them
+TRSV_RAND = 5                          # random entries per planted row (against earlier planted rows' x)
+# (n, W, mantissa bits, filler): the systems the CPU and the GPU tests share -- a partial block, exactly one block, one
+# row more (that row closes against the first block's anchors only), a few blocks with the dense filler, more than
+# ten blocks in both windows
+TRSV_CASES = ((40, 40, 20, False), (64, 400, 53, False), (65, 40, 53, False), (200, 400, 53, True), (130, 40, 30, True),
+              (700, 400, 53, False), (714, 40, 53, False))
+
+
+def _p2(e):
+    return Fraction(2) ** int(e)
+
+
+def _exact_double(v):
+    """a dyadic Fraction -> the double that holds it exactly"""
+    f = float(v)
+    assert Fraction(f) == v, "an operand is not representable as a double"
+    return f
+
+
+def trsv_exact(L, b, unit=False):
+    """Plain Fraction substitution on the logical lower-triangular system L x = b (dense float64, substitution order
+    = row order):  T_i = b_i - sum_{j < i} L_ij x_j exactly over the already-fixed doubles x_j, then
+    x_i = round_nearest_even(T_i) / L_ii as the IEEE quotient of two doubles (unit: x_i = round_nearest_even(T_i)).
+    Zero entries are skipped, so a non-finite x_j may only sit where nothing consumes it.  Returns (x, totals)."""
+    L, b = np.asarray(L, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    n = len(b)
+    x, totals, xf = np.zeros(n), [], [None] * n
+    for i in range(n):
+        T = Fraction(float(b[i]))
+        for j in np.nonzero(L[i, :i])[0].tolist():
+            if xf[j] is None:
+                xf[j] = Fraction(float(x[j]))
+            T -= Fraction(float(L[i, j])) * xf[j]
+        r = round_nearest_even(T)
+        x[i] = r if unit else r / float(L[i, i])
+        totals.append(T)
+    return x, totals
+
+
+def _odd(rng, bits):
+    """an odd integer of exactly `bits` bits"""
+    return (int(rng.integers(0, 1 << 62)) % (1 << (bits - 1))) | (1 << (bits - 1)) | 1
+
+
+def _take(preferred, other):
+    """the next column of the preferred pool, of the other one when that is empty"""
+    return preferred.pop() if preferred else other.pop()
+
+
+def planted_trsv(n, seed=0, W=40, mbits=53, filler=False, unit=False, anchors=None):
+    """A logical lower-triangular system (dense L, b) whose row totals T_i = b_i - sum_j L_ij x_j are planted ties and
+    near-ties over a solution of full 53-bit doubles, with the expected solution from Fraction arithmetic alone.
+
+    The first `anchors` rows of every block of TRSV_BLOCK rows are anchor rows: x_i = 1 exactly (a random b_i, with the
+    filler its products too, and L_ii := round_nearest_even(T_i); unit: b_i = 1 and nothing else).  A tail block that
+    is no longer than `anchors` rows has none: its rows close against earlier blocks only.  Every other row is planted:
+      * TRSV_RAND random entries against earlier planted columns, odd integers of `mbits` bits scaled so that the
+        products a x_j step down from about 1 over a window of W bits (mbits = 53: every such product has fl(a x) != a x,
+        asserted); with `filler`, +-2^f in every other earlier planted column (exact products below 2^-8), so that the
+        strict triangle is dense but for the anchor columns;
+      * the row is negated if need be so that planted row k is negative where k % 3 == 1, and closed by
+        complete_to(T, COMPLETE_CLASSES[k % 5], TRSV_GAPS[(k // 5) % 4]).  Of the closing amount, the 52 bits around a
+        quarter unit of the result go into b_i (so that b_i +- a quarter unit is a double again: `b_control`, which
+        moves every planted total a quarter unit away from its tie); the rest, cut by split53, goes negated into
+        anchor columns: the row's own block (consumed in the diagonal phase), earlier blocks (the tile phase), or
+        alternating, by k % 3;
+      * planted rows with k % 7 == 3 also get a pair +-G against two anchor columns (an earlier block's and the row's
+        own where there is one), G of 53 random bits and 2^120 or 2^150 times the total (`cancel`): it cancels exactly,
+        but while it sits in an expansion most bits of the total can only be kept in the remainder;
+      * L_ii = +-d 2^e with d odd, 3 <= d < 4096, and e such that 1/2 < |x_i| < 2; unit: x_i = round_nearest_even(T_i),
+        which is of the order of 1 because the entries are scaled against the x_j they meet.
+    The first (planted rows) % 5 of them are turned into anchors, so the classes come in equal numbers.
+
+    Returns L, b, want (x), totals (Fractions), per row: classes ('anchor' for anchors), tie_up, gap, c_int (the total
+    in units of its deciding unit), own (per planted row: for each closing term in the matrix whether it sits in the
+    row's own block, leading term first, the deciding one last), cancel, planted (mask), b_control, counts (planted_mix)."""
+    A = anchors or (16 if W > 100 else 12)
+    assert n > A and 1 <= mbits <= 53 and W >= 16
+    rng = np.random.default_rng([seed, n, W, mbits, int(filler), int(unit), 4711])
+    blocks = -(-n // TRSV_BLOCK)
+    anchor = np.zeros(n, dtype=bool)
+    for B in range(blocks):
+        lo_, hi_ = B * TRSV_BLOCK, min(n, (B + 1) * TRSV_BLOCK)
+        if B == 0 or hi_ - lo_ > A:
+            anchor[lo_:lo_ + A] = True
+    spare = np.nonzero(~anchor)[0]
+    anchor[spare[:len(spare) % 5]] = True
+    L, b, x, bc = np.zeros((n, n)), np.zeros(n), np.zeros(n), np.zeros(n)
+    xf, totals = [None] * n, [None] * n
+    classes = np.full(n, "anchor", dtype=object)
+    tie_up, gap_of, c_int = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=object)
+    own, cancel = [None] * n, np.zeros(n, dtype=np.int64)
+    done = []                                              # planted rows so far
+    k = inexact = 0
+    for i in range(n):
+        blk = i // TRSV_BLOCK
+        ent = {}                                           # column -> Fraction
+        if anchor[i] and unit:
+            b[i], x[i], xf[i], totals[i] = 1.0, 1.0, Fraction(1), Fraction(1)
+            L[i, i] = 1.0
+            continue
+        cols = []
+        if not anchor[i] and done:
+            near = [j for j in done if j // TRSV_BLOCK == blk]
+            cols = list(rng.choice(near, min(len(near), TRSV_RAND // 2), replace=False)) if near else []
+            rest = [j for j in done if j not in cols]
+            cols += list(rng.choice(rest, min(len(rest), TRSV_RAND - len(cols)), replace=False)) if rest else []
+            for t, j in enumerate(int(c) for c in cols):
+                o = 0 if t == 0 else int(rng.integers(1, W))
+                xe = math.frexp(x[j])[1]
+                a = Fraction(_odd(rng, mbits) * (1 if rng.random() < 0.5 else -1)) * _p2(-o - mbits + 1 - xe)
+                ent[j] = a
+                if mbits == 53 and abs(math.frexp(x[j])[0]) != 0.5:   # the TwoProd error term carries bits of the total
+                    assert Fraction(float(a) * x[j]) != a * xf[j]      # (a carry row's x is a power of two if unit)
+                    inexact += 1
+        if filler and done:
+            fs = rng.integers(8, min(W, 60), len(done))
+            sg = rng.choice((-1, 1), len(done))
+            for j, f, s in zip(done, fs.tolist(), sg.tolist()):
+                if j not in ent:
+                    ent[j] = s * _p2(-f - math.frexp(x[j])[1])
+                    assert Fraction(float(ent[j]) * x[j]) == ent[j] * xf[j]
+        T = -sum((a * xf[j] for j, a in ent.items()), Fraction(0))
+        if anchor[i]:
+            bi = Fraction(_odd(rng, 53) * (1 if rng.random() < 0.5 else -1)) * _p2(-52)
+            T += bi
+            r = round_nearest_even(T)
+            assert r != 0.0
+            b[i], L[i, i], x[i], xf[i], totals[i] = _exact_double(bi), r, 1.0, Fraction(1), T
+            for j, a in ent.items():
+                L[i, j] = _exact_double(a)
+            continue
+        cls, gap = COMPLETE_CLASSES[k % 5], TRSV_GAPS[(k // 5) % len(TRSV_GAPS)]
+        if (T < 0) != (k % 3 == 1):
+            ent, T = {j: -a for j, a in ent.items()}, -T
+        lo = -(T.denominator.bit_length() - 1) if T else -(gap + 53)
+        Ti = T.numerator
+        assert Fraction(Ti) * _p2(lo) == T
+        fix = complete_to(Ti, cls, gap)
+        u = lo - fix.scale                                 # the closing terms count in units of 2^u
+        diff = fix.total - (Ti << fix.scale)
+        # The closing amount `diff` is cut in two.  b_i takes the 52 bits of |diff| from bit `low` up, a window that
+        # holds the quarter-unit position sh - 2 with k0 = 2, 25 or 49 bits below it: |bpart| < 2^52 and q = 2^k0 in
+        # units of 2^low, so bpart +- q has at most 53 bits and b_control is a double again.  What is left of diff
+        # above and below the window goes to the anchor columns in pieces of 53 bits.
+        sh = abs(fix.total).bit_length() - 53              # the unit in the last place of the rounded total is 2^sh
+        k0 = min((2, 25, 49)[k % 3], sh - 2)
+        low, q = sh - 2 - k0, 1 << (sh - 2)                # q: a quarter of that unit
+        bpart = (-1 if diff < 0 else 1) * (((abs(diff) >> low) & ((1 << 52) - 1)) << low)
+        terms = split53(diff - bpart)
+        away = (-1 if fix.total < 0 else 1) * (-1 if cls == "tie-1" else 1)      # the side that leads away from the tie
+        b[i], bc[i] = _exact_double(Fraction(bpart) * _p2(u)), _exact_double(Fraction(bpart + away * q) * _p2(u))
+        mine = [j for j in np.nonzero(anchor[:i])[0].tolist() if j // TRSV_BLOCK == blk]
+        early = [j for j in np.nonzero(anchor[:i])[0].tolist() if j // TRSV_BLOCK != blk]
+        assert len(terms) <= len(mine) + len(early), "the closing terms do not fit the anchors available"
+        mine = [mine[int(p)] for p in rng.permutation(len(mine))]
+        early = [early[int(p)] for p in rng.permutation(len(early))]
+        flags = []
+        for t, term in enumerate(terms):                   # k % 3: own block first, earlier blocks first, alternating
+            own_first = (True, False, t % 2 == 0)[k % 3]
+            j = _take(mine, early) if own_first else _take(early, mine)
+            flags.append(j // TRSV_BLOCK == blk)
+            ent[j] = -Fraction(term) * _p2(u)
+        if k % 7 == 3 and mine and len(mine) + len(early) >= 2:
+            # a pair that cancels exactly, 2^120 or 2^150 times the total: while it is in the expansion the bits of the
+            # total below 2^-39 (2^-9) of it can only be kept in the LDS remainder, under the bound B
+            c = (120, 150)[(k // 7) % 2]
+            big = Fraction(_odd(rng, 53)) * _p2(abs(fix.total).bit_length() + u + c - 53)
+            ent[_take(early, mine)] = -big                 # consumed in the tile phase where there is an earlier block
+            ent[_take(mine, early)] = big
+            cancel[i] = c
+        for j, a in ent.items():
+            L[i, j] = _exact_double(a)
+        tot = Fraction(fix.total) * _p2(u)
+        assert tot == Fraction(float(b[i])) - sum((Fraction(float(L[i, j])) * xf[j] for j in ent), Fraction(0))
+        r = round_nearest_even(tot)
+        if unit:
+            L[i, i], x[i] = 1.0, r
+        else:
+            d = _odd(rng, int(rng.integers(2, 13)))
+            L[i, i] = math.ldexp(float(d), math.frexp(r)[1] - d.bit_length()) * (1 if rng.random() < 0.5 else -1)
+            x[i] = r / float(L[i, i])
+        xf[i], totals[i] = Fraction(float(x[i])), tot
+        c_int[i] = fix.total >> fix.unit
+        name, up = classify(c_int[i])
+        classes[i], tie_up[i], gap_of[i], own[i] = name, up, gap, tuple(flags)
+        done.append(i)
+        k += 1
+    planted = ~anchor
+    assert np.isfinite(x).all() and (np.abs(x) > 2.0 ** -6).all() and (np.abs(x) < 2.0 ** 6).all()
+    assert (x[anchor] == 1.0).all() and k % 5 == 0 and (mbits < 53 or inexact >= 3 * k)
+    chk, chk_tot = trsv_exact(L, b, unit)                  # the whole system again, from the doubles alone
+    assert (chk.view(np.int64) == x.view(np.int64)).all() and chk_tot == totals
+    counts = planted_mix(SimpleNamespace(classes=classes[planted], tie_up=tie_up[planted], c_int=c_int[planted]))
+    for g in TRSV_GAPS:
+        assert ((gap_of == g) & planted).any()
+    if any(anchor[B * TRSV_BLOCK] for B in range(1, blocks)):   # both placements of the deciding (last) closing term
+        deep = [own[i][-1] for i in np.nonzero(planted & (gap_of >= 30))[0] if own[i]]
+        assert any(deep) and not all(deep)
+    assert (cancel == 120).any() and (cancel == 150).any()
+    bc[anchor] = b[anchor]
+    return SimpleNamespace(n=n, W=W, mbits=mbits, filler=filler, unit=unit, anchors=A, L=L, b=b, want=x, totals=totals,
+                           classes=classes, tie_up=tie_up, gap=gap_of, c_int=c_int, own=own, cancel=cancel, planted=planted,
+                           b_control=bc, counts=counts)
+
+
+def trsv_must_round_as_integers(case):
+    """rows the register certificate cannot decide: exact ties and carries, and near-ties whose deciding unit is 30 or
+    more bits below the half unit (the kernel inflates its error bound by 1.0000001, about 1 + 2^-23.25, so a total
+    within 2^-24 of the half unit, relative to it, cannot be certified: 30 leaves margin over that figure)"""
+    ties = (case.classes == "tie") | (case.classes == "carry")
+    near = (case.classes == "tie+1") | (case.classes == "tie-1")
+    return int((ties | (near & (case.gap >= 30))).sum())
+
+
+def trsv_operands(L, b, uplo, trans, diag="N", lda_pad=0, offa=0, incx=1, offx=0):
+    """ExTRSV's arguments for the logical system (L, b): column-major A with op(A) lower ('L','N' stores L; 'U','T' its
+    transpose) or upper ('U','N' and 'L','T': the system reversed, so that backward substitution meets the rows in the
+    logical order).  The triangle that must not be read, the lda padding, the offset prefixes and the incx gaps hold
+    NaN, and so does the stored diagonal for diag = 'U'.  Returns (a, lda, xs, idx): logical row i is xs[idx[i]]."""
+    L = np.asarray(L, dtype=np.float64)
+    n = L.shape[0]
+    M = np.where(np.tri(n, dtype=bool), L, np.nan)         # logical, NaN above the diagonal
+    if diag == "U":
+        np.fill_diagonal(M, np.nan)
+    forward = (uplo == "L") != (trans == "T")
+    if not forward:
+        M = M[::-1, ::-1]
+    if trans == "T":
+        M = M.T                                            # M[r, c] is now element (r, c) of the stored A
+    lda = n + lda_pad
+    a = np.full(offa + n * lda, np.nan)
+    a[offa:].reshape(n, lda)[:, :n] = M.T                  # column c of A is contiguous
+    idx = offx + (np.arange(n) if forward else np.arange(n - 1, -1, -1)) * incx
+    xs = np.full(offx + (n - 1) * incx + 1, np.nan)
+    xs[idx] = b
+    return a, lda, xs, idx
+
+
+def range_rows_trsv(lead=0):
+    """Rows of a triangular system whose totals sit at the ends of the double range, after `lead` rows of x = 1 and
+    six support rows that fix x = 2^511, 2^-537, v, w (v, w in [1, 2) with 53-bit odd mantissas), 1 and 2^-600.  With
+    lead + 6 a multiple of 64 (lead = 58) the support rows close one block of the kernel and the range rows open the
+    next: every huge or tiny product is then formed in the tile phase and handed over; otherwise (lead = 0, 70) support
+    and range rows share a block and the products are formed in the diagonal phase.  The range rows come last in the
+    substitution order and no row consumes them; the one that overflows is the very last (0 * inf is NaN).  Returns
+    L, b, want, totals, names and `rows` (name -> index)."""
+    v, w = math.ldexp(float((1 << 52) | 0x5a5a5a5a5a5a5 | 1), -52), math.ldexp(float((1 << 52) | 0x3c3c3c3c3c3c3 | 1), -52)
+    dmax = float((1 << 1024) - (1 << 971))
+    big = math.ldexp(float((1 << 53) - 1), 947)             # the largest double below 2^1000
+    sup = [2.0 ** 511, 2.0 ** -537, v, w, 1.0, 2.0 ** -600]
+    H, Lo, V, Wc, One, Sm = (lead + t for t in range(6))
+    rows = [   # name, b, diagonal, {column: entry}
+        ("just below the overflow tie", dmax, 1.0, {H: -2.0 ** 459, Lo: 2.0 ** -537}),
+        ("b = 2^1000, tie to even", 2.0 ** 1000, 3.0, {H: -2.0 ** 436}),
+        ("b below 2^1000, carry", big, -5.0, {H: -2.0 ** 435}),
+        ("product = 2^1000, tie to odd", 3 * 2.0 ** 947, 7.0, {H: -2.0 ** 489}),
+        ("product below 2^1000, carry", 2.0 ** 946, 3.0, {H: -math.ldexp(float((1 << 53) - 1), 947 - 511)}),
+        ("subnormal total, quotient a tie", 2.0 ** -1022, 2.0, {Lo: math.ldexp(float((1 << 52) - 3), -537)}),
+        ("subnormal total, negative", -2.0 ** -1022, 1.0, {Lo: -math.ldexp(float((1 << 52) - 5), -537)}),
+        ("subnormal quotient", math.ldexp(1.0 + 2.0 ** -52, -1000), 3 * 2.0 ** 40, {Lo: -2.0 ** -516}),
+        ("subnormal quotient of a near-tie", math.ldexp(1.0 + 2.0 ** -52, -1000), -3 * 2.0 ** 33,
+         {Lo: -2.0 ** -516, Sm: 2.0 ** -474}),
+        ("zero by cancellation, positive diagonal", 2.0 ** -30, 3.0, {V: w, Wc: -v, One: 2.0 ** -30}),
+        ("zero by cancellation, negative diagonal", -2.0 ** -30, -3.0, {V: -w, Wc: v, One: -2.0 ** -30}),
+        ("tie at the overflow threshold", dmax, 1.0, {H: -2.0 ** 459}),
+    ]
+    n = lead + len(sup) + len(rows)
+    L, b = np.zeros((n, n)), np.ones(n)
+    np.fill_diagonal(L, 1.0)
+    b[lead:lead + len(sup)] = sup
+    index = {}
+    for t, (name, bi, dia, ent) in enumerate(rows):
+        i = lead + len(sup) + t
+        b[i], L[i, i], index[name] = bi, dia, i
+        for j, a in ent.items():
+            L[i, j] = a
+    want, totals = trsv_exact(L, b)
+    tiny = 5e-324
+    assert (want[:lead + len(sup)] == b[:lead + len(sup)]).all() and np.isfinite(want[:-1]).all()
+    assert want[index["just below the overflow tie"]] == dmax and want[index["tie at the overflow threshold"]] == math.inf
+    assert totals[index["tie at the overflow threshold"]] == (1 << 1024) - (1 << 970)
+    assert totals[index["just below the overflow tie"]] == (1 << 1024) - (1 << 970) - Fraction(1, 1 << 1074)
+    assert want[index["b = 2^1000, tie to even"]] == 2.0 ** 1000 / 3.0
+    assert want[index["b below 2^1000, carry"]] == 2.0 ** 1000 / -5.0
+    assert want[index["product = 2^1000, tie to odd"]] == (2.0 ** 1000 + 2.0 ** 949) / 7.0
+    assert want[index["product below 2^1000, carry"]] == 2.0 ** 1000 / 3.0
+    assert totals[index["subnormal total, quotient a tie"]] == Fraction(3, 1 << 1074)
+    assert want[index["subnormal total, quotient a tie"]] == 2 * tiny
+    assert want[index["subnormal total, negative"]] == -5 * tiny
+    for name in ("subnormal quotient", "subnormal quotient of a near-tie"):
+        assert 0.0 < abs(want[index[name]]) < 2.0 ** -1030 and totals[index[name]] > Fraction(1, 1 << 1001)
+    zp, zn = want[index["zero by cancellation, positive diagonal"]], want[index["zero by cancellation, negative diagonal"]]
+    assert zp == 0.0 and zn == 0.0 and math.copysign(1.0, zp) == 1.0 and math.copysign(1.0, zn) == -1.0
+    assert totals[index["zero by cancellation, positive diagonal"]] == 0 and Fraction(v * w) != Fraction(v) * Fraction(w)
+    return SimpleNamespace(n=n, lead=lead, L=L, b=b, want=want, totals=totals, names=[r[0] for r in rows], rows=index)

@@ -1,7 +1,8 @@
-"""CPU tests of the constructed ExGEMV / ExGEMM cases and their sparse views (tests/exact_cases.py): the constructions meet their own
+"""CPU tests of the constructed ExGEMV / ExGEMM cases, their sparse views and the ExTRSV systems (tests/exact_cases.py): the constructions meet their own
 conditions, and the oracle (and MPFR where built) returns the integer reference's bits on every output.  The integer
 reference shares no code with the library or the oracle; where the two disagree the oracle is wrong."""
 from fractions import Fraction
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -302,3 +303,112 @@ def test_range_rows_as_csr_vs_oracle(oracle):
             for beta, want in ((0.0, r.want), (1.0, r.want_with_y)):
                 got = _oracle_rows(oracle, crow, col, val, xs, 1.0, beta, r.y0, mode=oracle.ROUND_EXACT)
                 assert (_bits(got) == _bits(want)).all(), (inner, kw, beta)
+
+
+# ---------------------------------------------------------------------------------------------
+# ExTRSV: planted totals along the substitution chain, the control system and the range rows
+# ---------------------------------------------------------------------------------------------
+TRSV_ORIENT = (("L", "N"), ("U", "N"), ("L", "T"), ("U", "T"))
+TRSV_ORACLE_VARIANTS = ((0, False), (4, True), (8, True))
+
+
+def _trsv_vs_oracle(oracle, L, b, want, diag, what, mpfr=True):
+    for uplo, trans in TRSV_ORIENT:
+        a, lda, xs, idx = X.trsv_operands(L, b, uplo, trans, diag, lda_pad=3, offa=2, incx=2, offx=1)
+        for fpe, ee in TRSV_ORACLE_VARIANTS:
+            rc, got = oracle.extrsv(uplo, trans, diag, len(b), a, lda, xs, fpe, ee, incx=2, offa=2, offx=1,
+                                    mode=oracle.ROUND_EXACT)
+            bad = _bits(got[idx]) != _bits(want)
+            assert rc == 0 and not bad.any(), (what, uplo, trans, fpe, ee, np.nonzero(bad)[0][:8])
+            keep = np.ones(len(got), dtype=bool)
+            keep[idx] = False
+            assert np.isnan(got[keep]).all()
+        if mpfr and oracle.mpfr() is not None:
+            a, lda, xs, idx = X.trsv_operands(L, b, uplo, trans, diag)
+            got = oracle.mpfr_extrsv(uplo, trans, diag, len(b), a, lda, xs, True)
+            assert (_bits(got[idx]) == _bits(want)).all(), (what, uplo, trans, "mpfr")
+
+
+def test_trsv_exact_and_operands():
+    L = np.array([[2.0, 0, 0], [1.0, 4.0, 0], [0.5, -3.0, -8.0]])
+    b = np.array([6.0, 7.0, 1.5])
+    x, tot = X.trsv_exact(L, b)
+    assert x.tolist() == [3.0, 1.0, -0.375] and tot == [6, 4, 3]
+    assert X.trsv_exact(L, b, unit=True)[0].tolist() == [6.0, 1.0, 1.5]
+    # a total that is a tie (1 + 2^-53 -> 1), then an inexact quotient: the IEEE division of the rounded total
+    x, tot = X.trsv_exact(np.array([[1.0, 0], [-2.0 ** -53, 3.0]]), np.array([1.0, 1.0]))
+    assert tot[1] == 1 + Fraction(1, 2**53) and x[1] == 1.0 / 3.0
+    for uplo, trans in TRSV_ORIENT:
+        for diag in "NU":
+            a, lda, xs, idx = X.trsv_operands(L, b, uplo, trans, diag, lda_pad=2, offa=3, incx=3, offx=1)
+            assert lda == 5 and len(a) == 3 + 15 and len(xs) == 1 + 6 + 1 and (xs[idx] == b).all()
+            A = a[3:].reshape(3, 5)[:, :3].T                # A[r, c]
+            op = A.T if trans == "T" else A
+            fwd = (uplo == "L") != (trans == "T")
+            assert idx.tolist() == ([1, 4, 7] if fwd else [7, 4, 1])
+            logical = op if fwd else op[::-1, ::-1]
+            low = np.tril(np.ones((3, 3), bool), -1 if diag == "U" else 0)
+            assert (logical[low] == L[low]).all() and np.isnan(logical[~low]).all()
+            assert np.isnan(A[np.triu_indices(3, 1) if uplo == "L" else np.tril_indices(3, -1)]).all()
+            assert np.isnan(a[:3]).all() and np.isnan(a[3:].reshape(3, 5)[:, 3:]).all() and np.isnan(xs).sum() == len(xs) - 3
+
+
+@pytest.mark.parametrize("unit", [False, True])
+@pytest.mark.parametrize("n,W,mbits,filler", X.TRSV_CASES)
+def test_planted_trsv_vs_oracle(oracle, n, W, mbits, filler, unit):
+    c = X.planted_trsv(n, seed=21, W=W, mbits=mbits, filler=filler, unit=unit)   # (asserts its own conditions)
+    p = c.planted
+    assert c.counts == X.planted_mix(SimpleNamespace(classes=c.classes[p], tie_up=c.tie_up[p], c_int=c.c_int[p]))
+    assert c.counts["tie"] + c.counts["carry"] + c.counts["tie+1"] + c.counts["tie-1"] == p.sum() >= (n * 5) // 8
+    assert set(c.gap[p].tolist()) == set(X.TRSV_GAPS) and (c.want[~p] == 1.0).all()
+    big = np.nonzero(c.cancel)[0]                           # the exactly cancelling pairs: 2^120 / 2^150 times the total
+    assert 8 * len(big) >= p.sum() and not c.cancel[~p].any()
+    for i in big[:6]:
+        top = np.abs(c.L[i, :i]).max()
+        assert (c.L[i, :i] == top).sum() == 1 and (c.L[i, :i] == -top).sum() == 1
+        assert 2.0 ** (c.cancel[i] - 2) < top / abs(float(c.totals[i])) < 2.0 ** (c.cancel[i] + 2)
+    # the expected x and the totals follow from the doubles alone, and each total is of the class it is labelled with
+    x, tot = X.trsv_exact(c.L, c.b, unit)
+    assert (_bits(x) == _bits(c.want)).all() and tot == c.totals
+    for i in np.nonzero(p)[0][:: max(1, int(p.sum()) // 40)]:
+        T = c.totals[i]
+        a = abs(T.numerator) << max(0, 60 - abs(T.numerator).bit_length())
+        half = 1 << (a.bit_length() - 54)
+        r = a % (2 * half)
+        dev = {"tie": 0, "carry": 0, "tie+1": 1, "tie-1": -1}[c.classes[i]]
+        assert (r - half) * (1 << int(c.gap[i])) == dev * half, (i, c.classes[i])
+        if c.classes[i] == "carry":
+            assert a >> (a.bit_length() - 53) == 2**53 - 1
+    if filler:
+        cols = p.copy()                                     # dense but for the anchor columns
+        assert (c.L[np.ix_(p, cols)][np.tril_indices(int(p.sum()), -1)] != 0).all()
+    if n > X.TRSV_BLOCK:                                    # closing terms in the row's own block and in earlier ones
+        flags = [f for f in c.own if f]
+        assert any(all(f) for f in flags) and any(not any(f) for f in flags)
+    plain = np.zeros(n)                                     # fp64 substitution is wrong here
+    for i in range(n):
+        plain[i] = (c.b[i] - c.L[i, :i] @ plain[:i]) / (1.0 if unit else c.L[i, i])
+    assert (plain != c.want).sum() > n // 8
+    diag = "U" if unit else "N"
+    _trsv_vs_oracle(oracle, c.L, c.b, c.want, diag, (n, W, "planted"))
+    # the control: every planted b_i a quarter unit of its total further from the tie
+    moved = c.b_control != c.b
+    assert (moved == p).all()
+    xc, totc = X.trsv_exact(c.L, c.b_control, unit)
+    first = int(np.nonzero(p)[0][0])
+    q = abs(totc[first] - c.totals[first])
+    assert q * 4 == Fraction(np.spacing(abs(X.round_nearest_even(c.totals[first])))) or c.classes[first] == "carry"
+    assert np.isfinite(xc).all() and (_bits(xc) != _bits(c.want)).any()
+    _trsv_vs_oracle(oracle, c.L, c.b_control, xc, diag, (n, W, "control"), mpfr=False)
+
+
+@pytest.mark.parametrize("lead", [0, 58, 70])
+def test_range_rows_trsv_vs_oracle(oracle, lead):
+    r = X.range_rows_trsv(lead)                             # (asserts the values it was built for)
+    first = min(r.rows.values())                            # lead = 58: the range rows open the second block of 64
+    assert first == lead + 6 and (first % X.TRSV_BLOCK == 0) == (lead == 58)
+    assert r.n == lead + 18 and np.isinf(r.want).sum() == 1 and np.isinf(r.want[-1])
+    assert (np.abs(r.want[np.isfinite(r.want)]) >= 2.0**1000 / 8).sum() >= 5
+    sub = np.abs(r.want) < 2.0**-1022
+    assert (sub & (r.want != 0)).sum() >= 4 and (r.want == 0).sum() == 2
+    _trsv_vs_oracle(oracle, r.L, r.b, r.want, "N", ("range", lead))
