@@ -610,84 +610,40 @@ hipError_t finalize_sets(const long long *d_sets, int nsets, unsigned flags_or, 
     return hipGetLastError();
 }
 
-// variant selection: gpu:ExSUM.cpp:64-84 (fpe < 2 -> superaccumulators only; early_exit buckets 4/6/8)
+// fpe < 2: superaccumulators only (gpu:ExSUM.cpp:64-71).  Early exit with fpe > 8: nothing is launched, the
+// accumulators stay zero and the caller reads 0.0, the reference's silent return.
 hipError_t exsum_dispatch(Ctx &c, const double *a, long long n, long long inca, int fpe, int early_exit,
-                          hipStream_t st, bool *supported)
+                          hipStream_t st)
 {
-    *supported = true;
     if (fpe < 2) return launch_exsum<0, false>(c, a, n, inca, st);
-    if (early_exit) {
-        if (fpe <= 4) return launch_exsum<4, true>(c, a, n, inca, st);
-        if (fpe <= 6) return launch_exsum<6, true>(c, a, n, inca, st);
-        if (fpe <= 8) return launch_exsum<8, true>(c, a, n, inca, st);
-    } else {
-        switch (fpe) {
-        case 2: return launch_exsum<2, false>(c, a, n, inca, st);
-        case 3: return launch_exsum<3, false>(c, a, n, inca, st);
-        case 4: return launch_exsum<4, false>(c, a, n, inca, st);
-        case 5: return launch_exsum<5, false>(c, a, n, inca, st);
-        case 6: return launch_exsum<6, false>(c, a, n, inca, st);
-        case 7: return launch_exsum<7, false>(c, a, n, inca, st);
-        // fpe > 8 without early exit: the reference builds ExSUM.FPE.cl with -DNBFPE=fpe (gpu:ExSUM.cpp:80-81).  The
-        // exact sum does not depend on the expansion size, so the largest instantiation returns the same bits.
-        default: return launch_exsum<8, false>(c, a, n, inca, st);
-        }
-    }
-    *supported = false;  // early_exit with fpe > 8: the reference silently returns 0.0 (gpu:ExSUM.cpp:72-83)
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    select_variant<2>(fpe, early_exit, [&](auto N, auto EE) { e = launch_exsum<N(), EE()>(c, a, n, inca, st); });
+    return e;
 }
 
-// same variant rules as exsum (gpu:ExSUM.cpp:64-84); an unsupported combination yields 0.0 for every segment
+// same variant rules as exsum; an unsupported combination yields 0.0 for every segment
 hipError_t exsum_segmented_dispatch(const double *values, const long long *offsets, long long nseg, int fpe,
                                     int early_exit, int round_mode, hipStream_t st, double *out)
 {
     if (nseg <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nseg + WAVES - 1) / WAVES)), block(BLOCK);
-#define SEG_GO(N, EE) \
-    hipLaunchKernelGGL((k_exsum_segmented<N, EE>), grid, block, 0, st, values, offsets, nseg, round_mode, out)
-    if (fpe < 2) SEG_GO(0, false);
-    else if (early_exit) {
-        if (fpe <= 4) SEG_GO(4, true);
-        else if (fpe <= 6) SEG_GO(6, true);
-        else if (fpe <= 8) SEG_GO(8, true);
-        else return hipMemsetAsync(out, 0, sizeof(double) * nseg, st);
-    } else {
-        switch (fpe) {
-        case 2: SEG_GO(2, false); break;
-        case 3: SEG_GO(3, false); break;
-        case 4: SEG_GO(4, false); break;
-        case 5: SEG_GO(5, false); break;
-        case 6: SEG_GO(6, false); break;
-        case 7: SEG_GO(7, false); break;
-        default: SEG_GO(8, false); break;  // fpe >= 8 (see exsum_dispatch)
-        }
-    }
-#undef SEG_GO
+    auto go = [&](auto N, auto EE) {
+        hipLaunchKernelGGL((k_exsum_segmented<N(), EE()>), grid, block, 0, st, values, offsets, nseg, round_mode, out);
+    };
+    if (fpe < 2) go(std::integral_constant<int, 0>(), std::false_type());
+    else if (!select_variant<2>(fpe, early_exit, go)) return hipMemsetAsync(out, 0, sizeof(double) * nseg, st);
     return hipGetLastError();
 }
 
-// ExDOT.cpp:69-98 (fpe < 3 -> superaccumulators only)
+// fpe < 3: superaccumulators only (ExDOT.cpp:69-76); early exit with fpe > 8 as in exsum_dispatch
 hipError_t exdot_dispatch(Ctx &c, const double *a, long long inca, const double *b, long long incb, long long n,
-                          int fpe, int early_exit, hipStream_t st, bool *supported)
+                          int fpe, int early_exit, hipStream_t st)
 {
-    *supported = true;
     if (fpe < 3) return launch_exdot<0, false>(c, a, inca, b, incb, n, st);
-    if (early_exit) {
-        if (fpe <= 4) return launch_exdot<4, true>(c, a, inca, b, incb, n, st);
-        if (fpe <= 6) return launch_exdot<6, true>(c, a, inca, b, incb, n, st);
-        if (fpe <= 8) return launch_exdot<8, true>(c, a, inca, b, incb, n, st);
-    } else {
-        switch (fpe) {
-        case 3: return launch_exdot<3, false>(c, a, inca, b, incb, n, st);
-        case 4: return launch_exdot<4, false>(c, a, inca, b, incb, n, st);
-        case 5: return launch_exdot<5, false>(c, a, inca, b, incb, n, st);
-        case 6: return launch_exdot<6, false>(c, a, inca, b, incb, n, st);
-        case 7: return launch_exdot<7, false>(c, a, inca, b, incb, n, st);
-        default: return launch_exdot<8, false>(c, a, inca, b, incb, n, st);  // fpe >= 8 (ExDOT.cpp:93-94)
-        }
-    }
-    *supported = false;
-    return hipSuccess;
+    hipError_t e = hipSuccess;
+    select_variant<3>(fpe, early_exit,
+                      [&](auto N, auto EE) { e = launch_exdot<N(), EE()>(c, a, inca, b, incb, n, st); });
+    return e;
 }
 
 }  // namespace exb

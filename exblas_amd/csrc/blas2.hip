@@ -569,15 +569,15 @@ static hipError_t gemv_variant(Ctx &c, bool trans, int m, int n, double alpha, c
     else return gemvN_fpe<N, EE>(c, m, n, alpha, a, lda, x, incx, beta, y, incy, round_mode, st);
 }
 
-// variant selection: ExGEMV.cpp:81-107 (fpe == 0 superaccumulators, fpe == 1 plain DGEMV, early-exit buckets 4/6/8)
+// fpe == 0: superaccumulators only, fpe == 1: plain DGEMV (ExGEMV.cpp:81-94).  Early exit with fpe > 8: y untouched,
+// the reference's silent return.
 hipError_t exgemv_dispatch(Ctx &c, char transa, int m, int n, double alpha, const double *a, int lda, const double *x,
                            int incx, double beta, double *y, int incy, int fpe, int early_exit, int round_mode,
                            hipStream_t st)
 {
     if (m <= 0 || n <= 0) return hipSuccess;
     const bool t = (transa == 'T' || transa == 't');
-#define GV_ARGS c, t, m, n, alpha, a, lda, x, incx, beta, y, incy, round_mode, st
-    if (fpe == 0) return gemv_variant<0, false>(GV_ARGS);
+    if (fpe == 0) return gemv_variant<0, false>(c, t, m, n, alpha, a, lda, x, incx, beta, y, incy, round_mode, st);
     if (fpe == 1) {
         if (t)
             hipLaunchKernelGGL(k_dgemvT, dim3(n), dim3(64), 0, st, m, alpha, a, (long long)lda, x, (long long)incx, beta,
@@ -587,31 +587,11 @@ hipError_t exgemv_dispatch(Ctx &c, char transa, int m, int n, double alpha, cons
                                (long long)lda, x, (long long)incx, beta, y, (long long)incy);
         return hipGetLastError();
     }
-    if (early_exit) {
-        if (fpe <= 4) return gemv_variant<4, true>(GV_ARGS);
-        if (fpe <= 6) return gemv_variant<6, true>(GV_ARGS);
-        if (fpe <= 8) return gemv_variant<8, true>(GV_ARGS);
-        return hipSuccess;  // early_exit with fpe > 8: y untouched, the reference's silent return (ExGEMV.cpp:96-106)
-    }
-    switch (fpe) {
-    case 2: return gemv_variant<2, false>(GV_ARGS);
-    case 3: return gemv_variant<3, false>(GV_ARGS);
-    case 4: return gemv_variant<4, false>(GV_ARGS);
-    case 5: return gemv_variant<5, false>(GV_ARGS);
-    case 6: return gemv_variant<6, false>(GV_ARGS);
-    case 7: return gemv_variant<7, false>(GV_ARGS);
-    default: return gemv_variant<8, false>(GV_ARGS);  // fpe >= 8: ExGEMV.FPE.cl with NBFPE = fpe (ExGEMV.cpp:103-104), same bits
-    }
-#undef GV_ARGS
+    hipError_t e = hipSuccess;
+    select_variant<2>(fpe, early_exit, [&](auto N, auto EE) {
+        e = gemv_variant<N(), EE()>(c, t, m, n, alpha, a, lda, x, incx, beta, y, incy, round_mode, st);
+    });
+    return e;
 }
 
 }  // namespace exb
-
-// tools/ only: what the occupancy API says for the production 'N' kernel (blocks of 256 threads per CU)
-extern "C" int exblas_debug_gemv_occupancy(void)
-{
-    int nb = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, exb::k_gemvN_fpe_sx<8, true>, exb::GV_BLOCK, 0) != hipSuccess)
-        return -1;
-    return nb;
-}

@@ -112,30 +112,20 @@ static hipError_t gemm_variant(char transa, char transb, int m, int n, int k, do
     return hipGetLastError();
 }
 
-// one (fpe, early_exit) variant of the scalar kernel on a row block
+// one (fpe, early_exit) variant of the scalar kernel on a row block; fpe < 3: superaccumulators only (ExGEMM.cpp:78-87)
 static hipError_t gemm_scalar(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
                               const double *b, int ldb, double beta, double *cmat, int ldc, int fpe, int early_exit,
                               int round_mode, hipStream_t st, const int *gate)
 {
-#define GM_ARGS transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, cmat, ldc, round_mode, st, gate
-    if (fpe < 3) return gemm_variant<0, false>(GM_ARGS);
-    if (early_exit) {
-        if (fpe <= 4) return gemm_variant<4, true>(GM_ARGS);
-        if (fpe <= 6) return gemm_variant<6, true>(GM_ARGS);
-        return gemm_variant<8, true>(GM_ARGS);
-    }
-    switch (fpe) {
-    case 3: return gemm_variant<3, false>(GM_ARGS);
-    case 4: return gemm_variant<4, false>(GM_ARGS);
-    case 5: return gemm_variant<5, false>(GM_ARGS);
-    case 6: return gemm_variant<6, false>(GM_ARGS);
-    case 7: return gemm_variant<7, false>(GM_ARGS);
-    default: return gemm_variant<8, false>(GM_ARGS);  // fpe >= 8: ExGEMM.FPE.cl with NBFPE = fpe (ExGEMM.cpp:96-97), same bits
-    }
-#undef GM_ARGS
+    hipError_t e = hipSuccess;
+    auto go = [&](auto N, auto EE) {
+        e = gemm_variant<N(), EE()>(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, cmat, ldc, round_mode, st, gate);
+    };
+    if (fpe < 3) go(std::integral_constant<int, 0>(), std::false_type());
+    else select_variant<3>(fpe, early_exit, go);  // early exit with fpe > 8 never gets here (exgemm_dispatch)
+    return e;
 }
 
-// variant selection: ExGEMM.cpp:78-99 (fpe < 3 superaccumulators only; early-exit buckets 4/6/8).
 // chunks != nullptr: the rows of C are produced chunk by chunk and chunks->hook runs after each (row-sharded GEMM).
 hipError_t exgemm_dispatch(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a,
                            int lda, const double *b, int ldb, double beta, double *cmat, int ldc, int fpe,

@@ -4,6 +4,10 @@
 // reference's public headers (include/blas1.hpp:48,74; blas2.hpp:57,95; blas3.hpp:56) and replace
 // src/gpu/blas/blas{1,2,3}/Ex*.cpp: same argument meaning, same variant dispatch, same error
 // behaviour (print + exit on fpe < 0 or device failure, 0.0 for Ng <= 0 / unsupported variants).
+//
+// Each routine has one implementation on an explicit context (the *_on functions); the *_dev, *_ctx and host-pointer
+// entry points are thin layers over it.  The two CSR routines share their argument checks (csr_check_args) and their
+// host-pointer path (csr_host_call); the per-device knobs and the workspace release go through for_each_layer.
 #include "../../include/exblas_hip.h"
 #include "../../include/blas1.hpp"
 #include "../../include/blas2.hpp"
@@ -56,14 +60,6 @@ static constexpr int MAX_DEV = 16;
 static Ctx g_ctx[MAX_LAYERS][MAX_DEV];
 static std::mutex g_ctx_mu;
 static int g_last_layer[MAX_DEV];  // which layer ran the most recent exgemv / exgemm / extrsv (diagnostics only)
-
-// run f on every context of `device` that exists (tuning knobs are per device, not per layer)
-template <class F>
-static void for_each_layer(int device, F &&f)
-{
-    for (int l = 0; l < MAX_LAYERS; ++l)
-        if (g_ctx[l][device].device >= 0) f(g_ctx[l][device]);
-}
 
 static int current_device()
 {
@@ -143,6 +139,21 @@ Ctx &ctx(int device, int layer)
 }
 
 Ctx &default_ctx() { return ctx(-1); }
+
+// run f on every context of the current device that exists (layer 0 is created if need be), each under its lock:
+// tuning knobs and the workspace release are per device, not per layer
+template <class F>
+static void for_each_layer(F &&f)
+{
+    ctx(-1);
+    const int device = current_device();
+    for (int l = 0; l < MAX_LAYERS; ++l) {
+        Ctx &c = g_ctx[l][device];
+        if (c.device < 0) continue;
+        std::lock_guard<std::mutex> lk(c.mu);
+        f(c);
+    }
+}
 
 void *stage_buf(Ctx &c, int slot, size_t bytes)
 {
@@ -352,9 +363,7 @@ int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant)
     // variant: kept in the signature for existing callers.  Refused before the device is touched: a stale A/B script
     // fails instead of timing the one production kernel under a variant's name.
     if (variant != -1 && variant != 0) return (int)hipErrorInvalidValue;
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
+    for_each_layer([&](Ctx &c) {
         if (blocks_per_cu > 0) c.blocks_per_cu = c.bpc_sum = c.bpc_dot = c.bpc_sa = c.bpc_heavy = blocks_per_cu;
         if (ngroups > 0 && ngroups != c.ngroups) {
             EXB_CHECK(hipDeviceSynchronize());
@@ -428,82 +437,36 @@ int exblas_last_gemm_slices(void)
     return v[1] > v[2] ? v[1] : v[2];
 }
 
-void exblas_set_gemm_max_slices(int s)
-{
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        c.gemm_max_slices = s;
-    });
-}
+void exblas_set_gemm_max_slices(int s) { for_each_layer([&](Ctx &c) { c.gemm_max_slices = s; }); }
+void exblas_set_gemm_max_moduli(int l) { for_each_layer([&](Ctx &c) { c.gemm_max_moduli = l; }); }
+void exblas_set_gemm_path(int mode) { for_each_layer([&](Ctx &c) { c.gemm_path = mode; }); }
 
-void exblas_set_gemm_max_moduli(int l)
-{
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        c.gemm_max_moduli = l;
-    });
-}
+static int sparse_path(int mode) { return (mode >= 0 && mode <= 3) ? mode : 0; }
+void exblas_set_spmv_path(int mode) { for_each_layer([&](Ctx &c) { c.spmv_path = sparse_path(mode); }); }
+void exblas_set_spmm_path(int mode) { for_each_layer([&](Ctx &c) { c.spmm_path = sparse_path(mode); }); }
 
-void exblas_set_gemm_path(int mode)
+// the four counters of the last sparse call on the last-used layer, from its workspace header (synchronises)
+static int last_sparse_info(const long long *Ctx::*info_dev, int64_t *out4)
 {
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        c.gemm_path = mode;
-    });
-}
-
-void exblas_set_spmv_path(int mode)
-{
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        c.spmv_path = (mode >= 0 && mode <= 3) ? mode : 0;
-    });
+    if (!out4) return (int)hipErrorInvalidValue;
+    Ctx &c = ctx(-1, g_last_layer[current_device()]);
+    std::lock_guard<std::mutex> lk(c.mu);
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (!(c.*info_dev)) return -1;
+    long long h[8];
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(h, c.*info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
+    return 0;
 }
 
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows split across workgroups,
-// out[3] chunks of the split rows; read from the device (synchronises)
-int exblas_last_spmv_info(int64_t *out4)
-{
-    if (!out4) return (int)hipErrorInvalidValue;
-    Ctx &c = ctx(-1, g_last_layer[current_device()]);
-    std::lock_guard<std::mutex> lk(c.mu);
-    for (int i = 0; i < 4; ++i) out4[i] = 0;
-    if (!c.spmv_info_dev) return -1;
-    long long h[8];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(h, c.spmv_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
-    return 0;
-}
-
-void exblas_set_spmm_path(int mode)
-{
-    ctx(-1);
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        c.spmm_path = (mode >= 0 && mode <= 3) ? mode : 0;
-    });
-}
+// out[3] chunks of the split rows
+int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&Ctx::spmv_info_dev, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from an accumulator, out[2] rows split across workgroups,
-// out[3] chunks of the split rows; read from the device (synchronises)
-int exblas_last_spmm_info(int64_t *out4)
-{
-    if (!out4) return (int)hipErrorInvalidValue;
-    Ctx &c = ctx(-1, g_last_layer[current_device()]);
-    std::lock_guard<std::mutex> lk(c.mu);
-    for (int i = 0; i < 4; ++i) out4[i] = 0;
-    if (!c.spmm_info_dev) return -1;
-    long long h[8];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(h, c.spmm_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
-    return 0;
-}
+// out[3] chunks of the split rows
+int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_info_dev, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -511,9 +474,8 @@ static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inc
 {
     if (fpe < 0 || n > 0x7fffffffll) return (int)hipErrorInvalidValue;
     std::lock_guard<std::mutex> lk(c.mu);
-    bool ok = true;
     // unsupported (fpe, early_exit) combination: nothing is launched, the accumulators stay zero -> 0.0
-    return n > 0 ? (int)exsum_dispatch(c, d_a, n, inca, fpe, early_exit, st, &ok) : 0;
+    return n > 0 ? (int)exsum_dispatch(c, d_a, n, inca, fpe, early_exit, st) : 0;
 }
 
 static int exdot_accumulate_on(Ctx &c, const double *d_a, int64_t inca, const double *d_b, int64_t incb, int64_t n,
@@ -521,8 +483,7 @@ static int exdot_accumulate_on(Ctx &c, const double *d_a, int64_t inca, const do
 {
     if (fpe < 0 || n > 0x7fffffffll) return (int)hipErrorInvalidValue;
     std::lock_guard<std::mutex> lk(c.mu);
-    bool ok = true;
-    return n > 0 ? (int)exdot_dispatch(c, d_a, inca, d_b, incb, n, fpe, early_exit, st, &ok) : 0;
+    return n > 0 ? (int)exdot_dispatch(c, d_a, inca, d_b, incb, n, fpe, early_exit, st) : 0;
 }
 
 static int finish_on(Ctx &c, hipStream_t st, int64_t *d_out)
@@ -541,12 +502,25 @@ static int exgemv_on(Ctx &c, char transa, int m, int n, double alpha, const doub
                                 round_mode(), st);
 }
 
+// The argument checks of the CSR calls, on host or device pointers alike (ExSpMV: k = 1, ldx = ldy = 1).  *empty: nothing
+// to compute (m == 0 or k == 0), which is decided before the pointers are looked at.
+static int csr_check_args(int m, int n, int k, int index_bits, const void *row_ptr, const double *x, int64_t ldx,
+                          const double *y, int64_t ldy, int fpe, bool *empty)
+{
+    *empty = false;
+    if (m < 0 || n < 0 || k < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
+    if (ldx < k || ldy < k) return (int)hipErrorInvalidValue;
+    *empty = m == 0 || k == 0;
+    if (!*empty && (!row_ptr || !y || (n > 0 && !x))) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
 static int exspmv_on(Ctx &c, int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                      const double *d_val, double alpha, const double *d_x, double beta, double *d_y, int fpe,
                      int early_exit, hipStream_t st)
 {
-    if (m < 0 || n < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
-    if (m > 0 && (!d_row_ptr || !d_y || (n > 0 && !d_x))) return (int)hipErrorInvalidValue;
+    bool empty;   // m == 0 goes on: the call still counts as the device's last one, and the dispatch launches nothing
+    if (int rc = csr_check_args(m, n, 1, index_bits, d_row_ptr, d_x, 1, d_y, 1, fpe, &empty)) return rc;
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exspmv_dispatch(c, m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe,
@@ -557,10 +531,9 @@ static int exspmm_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_
                      const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
                      int64_t ldy, int fpe, int early_exit, hipStream_t st)
 {
-    if (m < 0 || n < 0 || k < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
-    if (ldx < k || ldy < k) return (int)hipErrorInvalidValue;
-    if (m == 0 || k == 0) return 0;
-    if (!d_row_ptr || !d_y || (n > 0 && !d_x)) return (int)hipErrorInvalidValue;
+    bool empty;
+    const int rc = csr_check_args(m, n, k, index_bits, d_row_ptr, d_x, ldx, d_y, ldy, fpe, &empty);
+    if (rc || empty) return rc;
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exspmm_dispatch(c, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy,
@@ -849,34 +822,24 @@ int exblas_last_gemm_info_ctx(exblas_ctx_t *h, int *out8)
 }
 #undef EXB_HANDLE
 
-int exblas_reserve_workspace(size_t bytes)
-{
-    Ctx &c = ctx(-1);
-    std::lock_guard<std::mutex> lk(c.mu);
-    hipError_t e = hipSuccess;
-    workspace(c, bytes, nullptr, &e);
-    return (int)e;
-}
+int exblas_reserve_workspace(size_t bytes) { return exblas_reserve_workspace_ctx(nullptr, bytes); }
+size_t exblas_workspace_bytes(void) { return exblas_workspace_bytes_ctx(nullptr); }
 
-size_t exblas_workspace_bytes(void)
+// frees the parked blocks of a context whose lock is held; *first keeps the first failure
+static void free_retired(Ctx &c, hipError_t *first)
 {
-    Ctx &c = ctx(-1);
-    std::lock_guard<std::mutex> lk(c.mu);
-    return c.ws_bytes;
+    for (void *p : c.retired) {
+        hipError_t e = hipFree(p);
+        if (*first == hipSuccess) *first = e;
+    }
+    c.retired.clear();
 }
 
 int exblas_release_retired_workspaces(void)
 {
     ctx(-1);
     hipError_t first = hipDeviceSynchronize();
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        for (void *p : c.retired) {
-            hipError_t e = hipFree(p);
-            if (first == hipSuccess) first = e;
-        }
-        c.retired.clear();
-    });
+    for_each_layer([&](Ctx &c) { free_retired(c, &first); });
     return (int)first;
 }
 
@@ -884,13 +847,8 @@ int exblas_release_workspace(void)
 {
     ctx(-1);
     hipError_t first = hipDeviceSynchronize();
-    for_each_layer(current_device(), [&](Ctx &c) {
-        std::lock_guard<std::mutex> lk(c.mu);
-        for (void *p : c.retired) {
-            hipError_t e = hipFree(p);
-            if (first == hipSuccess) first = e;
-        }
-        c.retired.clear();
+    for_each_layer([&](Ctx &c) {
+        free_retired(c, &first);
         if (c.ws) {
             hipError_t e = hipFree(c.ws);
             if (first == hipSuccess) first = e;
@@ -1254,54 +1212,19 @@ int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int
     return 0;
 }
 
-int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
-                      double alpha, const double *x, double beta, double *y, int fpe, int early_exit)
-{
-    if (m < 0 || n < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
-    if (m == 0) return 0;
-    if (!row_ptr || !y || (n > 0 && !x)) return (int)hipErrorInvalidValue;
-    // the entries the call reads: [0, max row_ptr); a negative row_ptr entry is refused
-    const size_t isz = index_bits / 8;
-    long long nnz = 0;
-    for (int i = 0; i <= m; ++i) {
-        const long long v = index_bits == 32 ? (long long)((const int32_t *)row_ptr)[i] : ((const int64_t *)row_ptr)[i];
-        if (v < 0) return (int)hipErrorInvalidValue;
-        if (v > nnz) nnz = v;
-    }
-    if (nnz > 0 && (!col_idx || !val)) return (int)hipErrorInvalidValue;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
-    const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
-                 b_val = align_up((size_t)nnz * 8), b_x = align_up((size_t)n * 8), b_y = align_up((size_t)m * 8);
-    char *d;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d = (char *)stage_buf(c, 0, b_rp + b_ci + b_val + b_x + b_y);
-        EXB_CHECK(hipMemcpyAsync(d, row_ptr, (size_t)(m + 1) * isz, hipMemcpyHostToDevice, c.stream));
-        if (nnz > 0) {
-            EXB_CHECK(hipMemcpyAsync(d + b_rp, col_idx, (size_t)nnz * isz, hipMemcpyHostToDevice, c.stream));
-            EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci, val, (size_t)nnz * 8, hipMemcpyHostToDevice, c.stream));
-        }
-        if (n > 0) EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val, x, (size_t)n * 8, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val + b_x, y, (size_t)m * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    double *d_y = (double *)(d + b_rp + b_ci + b_val + b_x);
-    int rc = exspmv_on(c, m, n, index_bits, d, d + b_rp, (const double *)(d + b_rp + b_ci), alpha,
-                       (const double *)(d + b_rp + b_ci + b_val), beta, d_y, fpe, early_exit, c.stream);
-    if (rc) die("exblas_exspmv_csr", (hipError_t)rc, __FILE__, __LINE__);
-    EXB_CHECK(hipMemcpyAsync(y, d_y, (size_t)m * 8, hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
-}
+}  // extern "C"
 
-int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
-                      double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
-                      int early_exit)
+// The host-pointer CSR call: Y (m x k, row stride ldy) from X (n x k, row stride ldx); ExSpMV is k = 1, ldx = ldy = 1.
+// One staging block [row_ptr | col_idx | val | X | Y] goes to the device, launch(c, d_row_ptr, d_col_idx, d_val, d_x, d_y)
+// runs the routine on the context's stream, and Y comes back.
+template <class Launch>
+static int csr_host_call(const char *who, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                         const double *val, const double *x, int64_t ldx, double *y, int64_t ldy, int fpe,
+                         Launch &&launch)
 {
-    if (m < 0 || n < 0 || k < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
-    if (ldx < k || ldy < k) return (int)hipErrorInvalidValue;
-    if (m == 0 || k == 0) return 0;
-    if (!row_ptr || !y || (n > 0 && !x)) return (int)hipErrorInvalidValue;
+    bool empty;
+    const int bad = csr_check_args(m, n, k, index_bits, row_ptr, x, ldx, y, ldy, fpe, &empty);
+    if (bad || empty) return bad;
     // the entries the call reads: [0, max row_ptr); a negative row_ptr entry is refused
     const size_t isz = index_bits / 8;
     long long nnz = 0;
@@ -1318,26 +1241,51 @@ int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, 
     const size_t yspan = (size_t)(m - 1) * (size_t)ldy + (size_t)k;
     const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
                  b_val = align_up((size_t)nnz * 8), b_x = align_up(xspan * 8), b_y = align_up(yspan * 8);
-    char *d;
+    char *d, *d_val, *d_x, *d_y;
     {
         std::lock_guard<std::mutex> lk(c.mu);
         d = (char *)stage_buf(c, 0, b_rp + b_ci + b_val + b_x + b_y);
+        d_val = d + b_rp + b_ci;
+        d_x = d_val + b_val;
+        d_y = d_x + b_x;
         EXB_CHECK(hipMemcpyAsync(d, row_ptr, (size_t)(m + 1) * isz, hipMemcpyHostToDevice, c.stream));
         if (nnz > 0) {
             EXB_CHECK(hipMemcpyAsync(d + b_rp, col_idx, (size_t)nnz * isz, hipMemcpyHostToDevice, c.stream));
-            EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci, val, (size_t)nnz * 8, hipMemcpyHostToDevice, c.stream));
+            EXB_CHECK(hipMemcpyAsync(d_val, val, (size_t)nnz * 8, hipMemcpyHostToDevice, c.stream));
         }
-        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d + b_rp + b_ci + b_val + b_x, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
+        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d_x, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
+        EXB_CHECK(hipMemcpyAsync(d_y, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
     }
-    double *d_y = (double *)(d + b_rp + b_ci + b_val + b_x);
-    int rc = exspmm_on(c, m, n, k, index_bits, d, d + b_rp, (const double *)(d + b_rp + b_ci), alpha,
-                       (const double *)(d + b_rp + b_ci + b_val), ldx, beta, d_y, ldy, fpe, early_exit, c.stream);
-    if (rc) die("exblas_exspmm_csr", (hipError_t)rc, __FILE__, __LINE__);
+    const int rc = launch(c, (const void *)d, (const void *)(d + b_rp), (const double *)d_val, (const double *)d_x,
+                          (double *)d_y);
+    if (rc) die(who, (hipError_t)rc, __FILE__, __LINE__);
     // the padding of Y comes back as it went
     EXB_CHECK(hipMemcpyAsync(y, d_y, yspan * 8, hipMemcpyDeviceToHost, c.stream));
     EXB_CHECK(hipStreamSynchronize(c.stream));
     return 0;
+}
+
+extern "C" {
+
+int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                      double alpha, const double *x, double beta, double *y, int fpe, int early_exit)
+{
+    return csr_host_call("exblas_exspmv_csr", m, n, 1, index_bits, row_ptr, col_idx, val, x, 1, y, 1, fpe,
+                         [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *d_x, double *d_y) {
+                             return exspmv_on(c, m, n, index_bits, d_rp, d_ci, d_val, alpha, d_x, beta, d_y, fpe, early_exit,
+                                              c.stream);
+                         });
+}
+
+int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                      double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
+                      int early_exit)
+{
+    return csr_host_call("exblas_exspmm_csr", m, n, k, index_bits, row_ptr, col_idx, val, x, ldx, y, ldy, fpe,
+                         [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *d_x, double *d_y) {
+                             return exspmm_on(c, m, n, k, index_bits, d_rp, d_ci, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
+                                              early_exit, c.stream);
+                         });
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

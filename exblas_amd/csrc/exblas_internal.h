@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace exb {
@@ -81,13 +82,52 @@ void *workspace(Ctx &c, size_t bytes, hipStream_t st, hipError_t *err);
         if (_e != hipSuccess) exb::die(#expr, _e, __FILE__, __LINE__); \
     } while (0)
 
+// The reference's (fpe, early_exit) -> kernel-variant rule, shared by every routine (gpu:ExSUM.cpp:64-84,
+// ExDOT.cpp:69-98, ExGEMV.cpp:81-107, ExGEMM.cpp:78-99, ExTRSV.cpp:70-123).  For fpe >= MIN_N, calls
+// f(std::integral_constant<int, N>, std::bool_constant<EE>) with the expansion size N and early-exit flag EE of the
+// variant and returns true; returns false without calling f where the reference has no variant.
+//  - early exit: the sizes fall into the buckets 4 / 6 / 8; with fpe > 8 the reference silently does nothing
+//    (gpu:ExSUM.cpp:72-83, ExGEMV.cpp:96-106, ExGEMM.cpp:88-99).
+//  - no early exit: every size up to 8 has its own instantiation.  Above 8 the reference builds its *.FPE.cl with
+//    -DNBFPE=fpe (gpu:ExSUM.cpp:80-81, ExDOT.cpp:93-94, ExGEMV.cpp:103-104, ExGEMM.cpp:96-97); the exact result does not
+//    depend on the expansion size, so the largest instantiation returns the same bits.
+// What a routine does below MIN_N (superaccumulators only, the plain kernels of fpe == 1) and what "no variant" means
+// to its caller stay at the call site.  MIN_N is 2 or 3; sizes below it are not instantiated.
+template <int MIN_N, class F>
+bool select_variant(int fpe, int early_exit, F &&f)
+{
+    static_assert(MIN_N == 2 || MIN_N == 3, "expansion sizes start at 2 (sum, gemv, trsv) or 3 (dot, gemm)");
+    using std::false_type;
+    using std::integral_constant;
+    using std::true_type;
+    if (early_exit) {
+        if (fpe <= 4) f(integral_constant<int, 4>(), true_type());
+        else if (fpe <= 6) f(integral_constant<int, 6>(), true_type());
+        else if (fpe <= 8) f(integral_constant<int, 8>(), true_type());
+        else return false;
+        return true;
+    }
+    switch (fpe) {
+    case 2:
+        if constexpr (MIN_N <= 2) f(integral_constant<int, 2>(), false_type());
+        break;
+    case 3: f(integral_constant<int, 3>(), false_type()); break;
+    case 4: f(integral_constant<int, 4>(), false_type()); break;
+    case 5: f(integral_constant<int, 5>(), false_type()); break;
+    case 6: f(integral_constant<int, 6>(), false_type()); break;
+    case 7: f(integral_constant<int, 7>(), false_type()); break;
+    default: f(integral_constant<int, 8>(), false_type()); break;
+    }
+    return true;
+}
+
 struct GemmChunks;
 
 // blas1.hip
 hipError_t exsum_dispatch(Ctx &c, const double *a, long long n, long long inca, int fpe, int early_exit,
-                          hipStream_t st, bool *supported);
+                          hipStream_t st);
 hipError_t exdot_dispatch(Ctx &c, const double *a, long long inca, const double *b, long long incb, long long n,
-                          int fpe, int early_exit, hipStream_t st, bool *supported);
+                          int fpe, int early_exit, hipStream_t st);
 hipError_t exsum_segmented_dispatch(const double *values, const long long *offsets, long long nseg, int fpe,
                                     int early_exit, int round_mode, hipStream_t st, double *out);
 hipError_t finalize_groups(Ctx &c, hipStream_t st, long long *d_out, long long *d_ext_out = nullptr);

@@ -34,7 +34,6 @@ constexpr long long SM_LONG_MIN = 1024;         // rows longer than this are spl
 constexpr long long SM_CHUNK = 1024;            // entries per lane group (64 / G of them in a wave) and chunk of a split row
 constexpr int SM_HIST = 16;                     // header words [16, 80): split candidates by floor(log2(length))
 constexpr int SM_HDR_WORDS = SM_HIST + 64;
-constexpr long long SM_CHUNK_SMALL = 16;        // path 3
 constexpr size_t SM_LACC_BYTES = (size_t)32 << 20;   // budget of the split rows' accumulators (k * 576 bytes a row)
 constexpr int SM_DEF_G = 8;                     // lanes per deferred output when every row of the item is short
 constexpr long long SM_DEF_SHORT = 64;
@@ -204,15 +203,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_main(int m, int n, int k, Ite
                 fpe_absorb_prod<SP_N, true, SM_U>(f, p, er, sink);
                 if (!__any(active && flags == 0)) break;   // every output of the item is deferred already
             }
-            {   // beta * Y[i, j]: ExGEMV's rules (beta = 0 ignores Y, 1 adds it exactly, else the error-free product)
-                double p[1] = {0.0}, er[1] = {0.0};
-                if (active && beta != 0.0) {
-                    const double yv = *yp;
-                    if (beta == 1.0) p[0] = yv;
-                    else p[0] = two_prod(beta, yv, er[0]);
-                }
-                fpe_absorb_prod<SP_N, true, 1>(f, p, er, sink);
-            }
+            sp_absorb_beta(f, active, beta, yp, 0, sink);
             bool defer = false;
             if (active) {
                 double r;
@@ -365,12 +356,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long(int n, int k, ItemGeom g
     for (long long u = wave0; u < total; u += nwaves) {
         const long long t = u / geo.tiles;
         const long long j = (u % geo.tiles) * 64 + (lane & (G - 1));
-        long long lo = 0, hi = nl;   // the last idx with lbase[idx] <= t (bases are non-decreasing)
-        while (hi - lo > 1) {
-            const long long mid = (lo + hi) >> 1;
-            if (lbase[mid] <= t) lo = mid;
-            else hi = mid;
-        }
+        const long long lo = sp_chunk_owner(lbase, nl, t);
         const int row = lrows[lo];
         const long long r0 = (long long)rp[row], r1 = max(r0, (long long)rp[row + 1]);
         const long long p0 = r0 + (t - lbase[lo]) * chunk, p1 = min(r1, p0 + chunk);
@@ -431,17 +417,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int 
         } else {
             long long v0 = g[lane], v1 = lane < NL - 64 ? g[64 + lane] : 0;
             unsigned flags = (g[NL] ? FLAG_PINF : 0u) | (g[NL + 1] ? FLAG_NINF : 0u) | (g[NL + 2] ? FLAG_NAN : 0u);
-            if (beta != 0.0) {
-                const double yv = *yp;
-                if (beta == 1.0) {
-                    wave_add_double(v0, v1, yv, flags);
-                } else {
-                    double e;
-                    const double p = two_prod_safe(beta, yv, e);
-                    wave_add_double(v0, v1, p, flags);
-                    if (e != 0.0) wave_add_double(v0, v1, e, flags);
-                }
-            }
+            sp_wave_add_beta(v0, v1, beta, yp, 0, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
             if (lane == 0) *yp = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
         }
@@ -457,8 +433,8 @@ static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I 
                               const double *x, long long ldx, double beta, double *y, long long ldy, int force_defer,
                               int round_mode, hipStream_t st)
 {
-    const int path = c.spmm_path;
-    const long long long_min = path == 3 ? -1 : (path == 2 ? 0x7fffffffffffffffll : SM_LONG_MIN);
+    const SplitRule split = sp_split_rule(c.spmm_path, SM_LONG_MIN, SM_CHUNK);
+    const long long long_min = split.long_min;
     const int lcap = (int)min((long long)m, (long long)(SM_LACC_BYTES / ((size_t)k * SET_WORDS * 8)));
     ItemGeom geo;
     geo.lg = 0;
@@ -466,7 +442,7 @@ static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I 
     geo.tiles = geo.lg == 6 ? ((long long)k + 63) / 64 : 1;
     // a wave's lane groups share a chunk's entries round-robin: the chunk grows with their number, so that a column of a
     // split row sees the same number of atomic flushes whatever k is
-    const long long chunk = (path == 3 ? SM_CHUNK_SMALL : SM_CHUNK) * (64 >> geo.lg);
+    const long long chunk = split.chunk * (64 >> geo.lg);
     const long long rpw = 64 >> geo.lg, nitems = (((long long)m + rpw - 1) / rpw) * geo.tiles;
     const size_t b_hdr = 1024, b_lslot = align256((size_t)m * 4), b_lrows = align256((size_t)lcap * 4),
                  b_lbase = align256((size_t)(lcap + 1) * 8), b_bm = align256((size_t)nitems * 8),
@@ -519,14 +495,11 @@ hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const vo
     if (m == 0 || k == 0) return hipSuccess;
     // fpe == 0, the accumulator test path and the reference rounding mode round every output from an integer accumulator
     const int force_defer = (fpe == 0 || c.spmm_path == 1 || round_mode) ? 1 : 0;
-    if (index_bits == 32) {
-        const int *rp = (const int *)row_ptr, *ci = (const int *)col_idx;
-        if (fpe == 1) return spmm_launch<true>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, 0, 0, st);
-        return spmm_launch<false>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, force_defer, round_mode, st);
-    }
-    const long long *rp = (const long long *)row_ptr, *ci = (const long long *)col_idx;
-    if (fpe == 1) return spmm_launch<true>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, 0, 0, st);
-    return spmm_launch<false>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, force_defer, round_mode, st);
+    return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
+        constexpr bool PLAIN = decltype(plain)::value;   // the plain kernels neither defer nor round
+        return spmm_launch<PLAIN>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, PLAIN ? 0 : force_defer,
+                                  PLAIN ? 0 : round_mode, st);
+    });
 }
 
 }  // namespace exb

@@ -134,15 +134,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
                 }
                 fpe_absorb_prod<SP_N, true, U>(f, p, er, sink);
             }
-            {   // beta * y: ExGEMV's rules (beta = 0 ignores y, 1 adds it exactly, else the error-free product)
-                double p[1] = {0.0}, er[1] = {0.0};
-                if (valid && sub == 0 && beta != 0.0) {
-                    const double yv = y[row];
-                    if (beta == 1.0) p[0] = yv;
-                    else p[0] = two_prod(beta, yv, er[0]);
-                }
-                fpe_absorb_prod<SP_N, true, 1>(f, p, er, sink);
-            }
+            sp_absorb_beta(f, valid && sub == 0, beta, y, row, sink);
             // exact tree merge of the group's expansions into its first lane
 #pragma unroll
             for (int s = 1; s < G; s <<= 1) {
@@ -219,12 +211,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restri
     const long long wave0 = (long long)blockIdx.x * SP_WAVES + w, nwaves = (long long)gridDim.x * SP_WAVES;
     unsigned long long n_chunks = 0;
     for (long long t = wave0; t < total; t += nwaves) {
-        long long lo = 0, hi = nl;   // the last idx with lbase[idx] <= t (bases are non-decreasing)
-        while (hi - lo > 1) {
-            const long long mid = (lo + hi) >> 1;
-            if (lbase[mid] <= t) lo = mid;
-            else hi = mid;
-        }
+        const long long lo = sp_chunk_owner(lbase, nl, t);
         const int row = lrows[lo];
         const long long r0 = (long long)rp[row], r1 = max(r0, (long long)rp[row + 1]);
         const long long p0 = r0 + (t - lbase[lo]) * chunk, p1 = min(r1, p0 + chunk);
@@ -296,17 +283,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__rest
         } else {
             long long v0 = g[lane], v1 = lane < NL - 64 ? g[64 + lane] : 0;
             unsigned flags = (unsigned)g[SP_ACC_FLAGS] & FLAG_NONFINITE;
-            if (beta != 0.0) {
-                const double yv = y[row];
-                if (beta == 1.0) {
-                    wave_add_double(v0, v1, yv, flags);
-                } else {
-                    double e;
-                    const double p = two_prod_safe(beta, yv, e);
-                    wave_add_double(v0, v1, p, flags);
-                    if (e != 0.0) wave_add_double(v0, v1, e, flags);
-                }
-            }
+            sp_wave_add_beta(v0, v1, beta, y, row, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
             if (lane == 0) y[row] = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
         }
@@ -324,8 +301,7 @@ static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, co
 {
     const int path = c.spmv_path;
     const long long short_max = path == 3 ? -1 : SP_SHORT_MAX;
-    const long long long_min = path == 3 ? -1 : (path == 2 ? 0x7fffffffffffffffll : SP_LONG_MIN);
-    const long long chunk = path == 3 ? SP_CHUNK_SMALL : SP_CHUNK;
+    const auto [long_min, chunk] = sp_split_rule(path, SP_LONG_MIN, SP_CHUNK);
     const int lcap = path == 3 ? m : (int)min((long long)m, SP_LCAP);
     const size_t b_hdr = 256, b_med = align256((size_t)m * 4), b_lrows = align256((size_t)lcap * 4),
                  b_lbase = align256((size_t)(lcap + 1) * 8), b_lacc = (size_t)lcap * SET_WORDS * 8;
@@ -374,14 +350,10 @@ hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row
     // fpe == 0 (superaccumulator only, as in the other routines) and the accumulator test path round every row from
     // its integer accumulator; the reference rounding mode is only reproduced there
     const int force_fb = (fpe == 0 || c.spmv_path == 1 || round_mode) ? 1 : 0;
-    if (index_bits == 32) {
-        const int *rp = (const int *)row_ptr, *ci = (const int *)col_idx;
-        if (fpe == 1) return spmv_launch<true>(c, m, n, rp, ci, val, alpha, x, beta, y, 0, 0, st);
-        return spmv_launch<false>(c, m, n, rp, ci, val, alpha, x, beta, y, force_fb, round_mode, st);
-    }
-    const long long *rp = (const long long *)row_ptr, *ci = (const long long *)col_idx;
-    if (fpe == 1) return spmv_launch<true>(c, m, n, rp, ci, val, alpha, x, beta, y, 0, 0, st);
-    return spmv_launch<false>(c, m, n, rp, ci, val, alpha, x, beta, y, force_fb, round_mode, st);
+    return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
+        constexpr bool PLAIN = decltype(plain)::value;   // the plain kernels neither force the accumulator nor round
+        return spmv_launch<PLAIN>(c, m, n, rp, ci, val, alpha, x, beta, y, PLAIN ? 0 : force_fb, PLAIN ? 0 : round_mode, st);
+    });
 }
 
 }  // namespace exb

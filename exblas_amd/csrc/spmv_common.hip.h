@@ -1,5 +1,6 @@
 // spmv_common.hip.h -- what the sparse kernels (spmv.hip: ExSpMV, spmm.hip: ExSpMM) share: geometry constants, the
-// guarded gather of x, the certified in-register rounding test and the chunk-base scan of split rows.
+// guarded gather of x, the certified in-register rounding test, the beta * y term, the chunk-base scan and chunk-owner
+// search of split rows, and the host-side choice of index type, plain / exact kernels and split thresholds.
 #pragma once
 #include "superacc.hip.h"
 #include "fpe.hip.h"
@@ -76,6 +77,49 @@ __device__ __forceinline__ bool spmv_round_fast(double (&f)[N], double &out)
     return true;
 }
 
+// beta * y under ExGEMV's rules (beta = 0 ignores y, 1 adds it exactly, else the error-free product), absorbed into a
+// lane's expansion; `take` says whether this lane carries the term (y[at] is read by no other)
+template <class Sink>
+__device__ __forceinline__ void sp_absorb_beta(double (&f)[SP_N], bool take, double beta, const double *y, long long at,
+                                               Sink &sink)
+{
+    double p[1] = {0.0}, er[1] = {0.0};
+    if (take && beta != 0.0) {
+        const double yv = y[at];
+        if (beta == 1.0) p[0] = yv;
+        else p[0] = two_prod(beta, yv, er[0]);
+    }
+    fpe_absorb_prod<SP_N, true, 1>(f, p, er, sink);
+}
+
+// the same term added into the accumulator a wave holds in (v0, v1)
+__device__ __forceinline__ void sp_wave_add_beta(long long &v0, long long &v1, double beta, const double *y,
+                                                 long long at, unsigned &flags)
+{
+    if (beta == 0.0) return;
+    const double yv = y[at];
+    if (beta == 1.0) {
+        wave_add_double(v0, v1, yv, flags);
+    } else {
+        double e;
+        const double p = two_prod_safe(beta, yv, e);
+        wave_add_double(v0, v1, p, flags);
+        if (e != 0.0) wave_add_double(v0, v1, e, flags);
+    }
+}
+
+// split rows: which of the nl rows owns chunk t, i.e. the last idx with lbase[idx] <= t (bases are non-decreasing)
+__device__ __forceinline__ long long sp_chunk_owner(const long long *__restrict__ lbase, long long nl, long long t)
+{
+    long long lo = 0, hi = nl;
+    while (hi - lo > 1) {
+        const long long mid = (lo + hi) >> 1;
+        if (lbase[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // split rows: chunk counts of the rows in lrows[0 .. min(hdr[1], lcap)) -> exclusive scan (lbase), total in hdr[2]
 template <class I>
 __global__ void __launch_bounds__(1024) k_spmv_long_prep(const I *__restrict__ rp, const int *__restrict__ lrows,
@@ -116,5 +160,29 @@ __global__ void __launch_bounds__(1024) k_spmv_long_prep(const I *__restrict__ r
 }
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// exblas_set_spmv_path / exblas_set_spmm_path -> which rows are split and at what chunk: 3 splits every row at the small
+// chunk, 2 splits none, the others keep the routine's own threshold and chunk
+struct SplitRule {
+    long long long_min, chunk;
+};
+static inline SplitRule sp_split_rule(int path, long long long_min, long long chunk)
+{
+    if (path == 3) return {-1, SP_CHUNK_SMALL};
+    return {path == 2 ? 0x7fffffffffffffffll : long_min, chunk};
+}
+
+// the four host-side instantiations of a sparse routine: f(std::bool_constant<PLAIN>, rp, ci) with the index arrays
+// typed (int32 or int64) and PLAIN set for fpe == 1, the plain fp64 sums
+template <class F>
+static hipError_t sp_dispatch(int index_bits, int fpe, const void *row_ptr, const void *col_idx, F &&f)
+{
+    if (index_bits == 32) {
+        const int *rp = (const int *)row_ptr, *ci = (const int *)col_idx;
+        return fpe == 1 ? f(std::true_type(), rp, ci) : f(std::false_type(), rp, ci);
+    }
+    const long long *rp = (const long long *)row_ptr, *ci = (const long long *)col_idx;
+    return fpe == 1 ? f(std::true_type(), rp, ci) : f(std::false_type(), rp, ci);
+}
 
 }  // namespace exb

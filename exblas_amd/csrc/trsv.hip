@@ -400,8 +400,9 @@ hipError_t trsv_variant(int n, const double *a, long long rs, long long cs, doub
 
 }  // namespace
 
-// variant selection: ExTRSV.cpp:70-123.  Returns hipErrorNotSupported for the iterative-refinement values of fpe
-// (>= 9), whose kernel files the reference names but does not ship.
+// fpe == 0: superaccumulators only, fpe == 1: plain DTRSV, the other sizes by select_variant (ExTRSV.cpp:70-123).
+// Returns hipErrorNotSupported for the iterative-refinement values of fpe (>= 9), whose kernel files the reference
+// names but does not ship.
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,
                            int incx, int fpe, int early_exit, int round_mode, hipStream_t st)
 {
@@ -419,28 +420,17 @@ hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, con
     e = hipMemsetAsync(sync, 0, 64, st);
     if (e != hipSuccess) return e;
     if ((e = hipMemsetAsync(xq, 0xff, (size_t)n * sizeof(double), st)) != hipSuccess) return e;
-#define TV_ARGS n, a, rs, cs, x, (long long)incx, rev, unit, round_mode, sync, xq, st
-    if (fpe == 0) return trsv_variant<0, false>(TV_ARGS);
+    const long long ix = incx;
+    if (fpe == 0) return trsv_variant<0, false>(n, a, rs, cs, x, ix, rev, unit, round_mode, sync, xq, st);
     if (fpe == 1) {
-        hipLaunchKernelGGL(k_dtrsv, dim3((n + TB - 1) / TB), dim3(TB * TW), 0, st, n, a, rs, cs, x, (long long)incx, rev,
-                           unit, sync, xq);
+        hipLaunchKernelGGL(k_dtrsv, dim3((n + TB - 1) / TB), dim3(TB * TW), 0, st, n, a, rs, cs, x, ix, rev, unit, sync,
+                           xq);
         return hipGetLastError();
     }
-    if (early_exit) {
-        if (fpe <= 4) return trsv_variant<4, true>(TV_ARGS);
-        if (fpe <= 6) return trsv_variant<6, true>(TV_ARGS);
-        return trsv_variant<8, true>(TV_ARGS);
-    }
-    switch (fpe) {
-    case 2: return trsv_variant<2, false>(TV_ARGS);
-    case 3: return trsv_variant<3, false>(TV_ARGS);
-    case 4: return trsv_variant<4, false>(TV_ARGS);
-    case 5: return trsv_variant<5, false>(TV_ARGS);
-    case 6: return trsv_variant<6, false>(TV_ARGS);
-    case 7: return trsv_variant<7, false>(TV_ARGS);
-    default: return trsv_variant<8, false>(TV_ARGS);
-    }
-#undef TV_ARGS
+    select_variant<2>(fpe, early_exit, [&](auto N, auto EE) {
+        e = trsv_variant<N(), EE()>(n, a, rs, cs, x, ix, rev, unit, round_mode, sync, xq, st);
+    });
+    return e;
 }
 
 }  // namespace exb
