@@ -46,6 +46,8 @@ C_ABI_SYMBOLS = [
     "exblas_last_spmv_info",
     "exblas_exspmm_csr_dev", "exblas_exspmm_csr_ctx", "exblas_exspmm_csr", "exblas_set_spmm_path",
     "exblas_last_spmm_info",
+    "exblas_exsptrsv_csr_dev", "exblas_exsptrsv_csr_ctx", "exblas_exsptrsv_csr", "exblas_set_sptrsv_path",
+    "exblas_last_sptrsv_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -177,6 +179,12 @@ def load_library():
     L.exblas_set_spmm_path.argtypes = [i32]
     L.exblas_set_spmm_path.restype = None
     L.exblas_last_spmm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exsptrsv_csr_dev.argtypes = [C.c_char, C.c_char, i32, i32, vp, vp, vp, vp, i32, i32, vp]
+    L.exblas_exsptrsv_csr_ctx.argtypes = [vp] + L.exblas_exsptrsv_csr_dev.argtypes
+    L.exblas_exsptrsv_csr.argtypes = [C.c_char, C.c_char, i32, i32, vp, vp, vp, vp, i32, i32]
+    L.exblas_set_sptrsv_path.argtypes = [i32]
+    L.exblas_set_sptrsv_path.restype = None
+    L.exblas_last_sptrsv_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -428,6 +436,80 @@ def last_spmv_info():
     return tuple(int(v) for v in out)
 
 
+SPTRSV_STALLED = -3  # EXBLAS_SPTRSV_STALLED: the watchdog of an ExSpTRSV call was raised
+
+
+def _sptrsv_flags(uplo, diag):
+    if not isinstance(uplo, str) or uplo not in ("L", "l", "U", "u"):
+        raise ValueError(f"exsptrsv: uplo must be 'L' or 'U', got {uplo!r}")
+    if not isinstance(diag, str) or diag not in ("N", "n", "U", "u"):
+        raise ValueError(f"exsptrsv: diag must be 'N' or 'U', got {diag!r}")
+    return uplo.encode(), diag.encode()
+
+
+def _sptrsv_check(A, x, uplo, diag):
+    """Validates a device ExSpTRSV call before anything is launched; returns (crow, col, val, m, index_bits, uplo, diag)."""
+    torch = _torch()
+    crow, col, val, m, n = _csr_parts(A)
+    if m != n:
+        raise ValueError(f"exsptrsv: A must be square, got shape ({m}, {n})")
+    u, d = _sptrsv_flags(uplo, diag)
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"exsptrsv: {name} must be a torch tensor")
+    if val.dtype != torch.float64 or x.dtype != torch.float64:
+        raise TypeError("exsptrsv: values and x must be float64")
+    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
+        raise TypeError("exsptrsv: row pointers and column indices must both be int32 or both int64")
+    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1:
+        raise ValueError("exsptrsv: crow, col and val must be 1-D")
+    if crow.numel() != m + 1:
+        raise ValueError(f"exsptrsv: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
+    if col.numel() != val.numel():
+        raise ValueError("exsptrsv: col and val differ in length")
+    if x.dim() != 1 or x.numel() != m:
+        raise ValueError(f"exsptrsv: x must be a 1-D float64 tensor of m = {m} entries")
+    if not x.is_contiguous():
+        raise ValueError("exsptrsv: x must be contiguous (it is solved in place)")
+    devs = {t.device for t in (crow, col, val, x)}
+    if len(devs) != 1:
+        raise ValueError("exsptrsv: crow, col, val and x must be on one device")
+    _require_gpu()
+    if not val.is_cuda:
+        raise ValueError("exsptrsv: the tensors must be on the GPU")
+    return crow.contiguous(), col.contiguous(), val.contiguous(), m, (32 if crow.dtype == torch.int32 else 64), u, d
+
+
+def exsptrsv_dev(A, x, uplo="L", diag="N", fpe=8, early_exit=True):
+    """ExSpTRSV: solves A x = b in place on x (b on entry), exact and reproducible, stream-ordered on the current stream:
+    x_i = Round(b_i - sum of the stored val * x_j before the diagonal) / d_i in substitution order (diag 'U': no division),
+    bit for bit what extrsv_dev gives on the densified matrix.  A: square torch.sparse_csr_tensor or (crow, col, val,
+    (m, m)) on the GPU (float64 values, int32 or int64 indices); entries of the other triangle are skipped.  Returns x."""
+    torch = _torch()
+    crow, col, val, m, bits, u, d = _sptrsv_check(A, x, uplo, diag)
+    _check(load_library().exblas_exsptrsv_csr_dev(u, d, m, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()),
+                                                  C.c_void_p(val.data_ptr()), C.c_void_p(x.data_ptr()), int(fpe),
+                                                  int(bool(early_exit)), _stream_ptr(torch)), "exsptrsv_dev")
+    return x
+
+
+def set_sptrsv_path(mode):
+    """Test hook: 0 automatic, 1 every row rounded from its integer accumulator, 2 every row in the one-row-per-wave
+    form.  Same bits on every path."""
+    load_library().exblas_set_sptrsv_path(int(mode))
+
+
+def last_sptrsv_info():
+    """(rows rounded in registers, rows rounded from their accumulator, rows without a stored diagonal under 'N', stored
+    entries skipped) of the last ExSpTRSV; raises when that call's watchdog was raised."""
+    out = (C.c_int64 * 4)()
+    rc = load_library().exblas_last_sptrsv_info(out)
+    if rc == SPTRSV_STALLED:
+        raise RuntimeError("exblas_amd: the last exsptrsv stalled: a wave gave up waiting for a solved value")
+    _check(rc, "last_sptrsv_info")
+    return tuple(int(v) for v in out)
+
+
 def _spmm_check(A, X, Y):
     """Validates a device ExSpMM call before anything is launched; returns (crow, col, val, X, m, n, k, index_bits, Y)."""
     torch = _torch()
@@ -592,6 +674,15 @@ class Context:
                                                     _stream_ptr(torch)), "exspmv_ctx")
         return y
 
+    def exsptrsv(self, A, x, uplo="L", diag="N", fpe=8, early_exit=True):
+        torch = _torch()
+        crow, col, val, m, bits, u, d = _sptrsv_check(A, x, uplo, diag)
+        _check(load_library().exblas_exsptrsv_csr_ctx(self.handle, u, d, m, bits, C.c_void_p(crow.data_ptr()),
+                                                      C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
+                                                      C.c_void_p(x.data_ptr()), int(fpe), int(bool(early_exit)),
+                                                      _stream_ptr(torch)), "exsptrsv_ctx")
+        return x
+
     def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
         torch = _torch()
         crow, col, val, X, m, n, k, bits, Y = _spmm_check(A, X, Y)
@@ -736,6 +827,39 @@ def exspmv(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
     _check(load_library().exblas_exspmv_csr(m, n, bits, p(crow), p(col), p(val), float(alpha), p(x), float(beta),
                                             p(y), int(fpe), int(bool(early_exit))), "exspmv")
     return y
+
+
+def exsptrsv(A, b, uplo="L", diag="N", fpe=8, early_exit=True):
+    """ExSpTRSV on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv), b float64 of m entries;
+    returns the solution (a new float64 array; b is not changed)."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError("exsptrsv: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
+    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
+    if len(shape) != 2 or int(shape[0]) != int(shape[1]):
+        raise ValueError("exsptrsv: shape must be (m, m)")
+    m = int(shape[0])
+    u, d = _sptrsv_flags(uplo, diag)
+    b = np.asarray(b)
+    if val.dtype != np.float64 or b.dtype != np.float64:
+        raise TypeError("exsptrsv: values and b must be float64")
+    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
+        raise TypeError("exsptrsv: row pointers and column indices must both be int32 or both int64")
+    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or b.ndim != 1:
+        raise ValueError("exsptrsv: row_ptr, col_idx, val and b must be 1-D")
+    if m < 0 or crow.size != m + 1 or col.size != val.size or b.size != m:
+        raise ValueError("exsptrsv: inconsistent sizes of row_ptr / col_idx / val / b")
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError("exsptrsv: row_ptr entries must lie in [0, nnz]")
+    x = np.array(b, dtype=np.float64, copy=True)
+    _require_gpu()
+    crow, col, val = (np.ascontiguousarray(a) for a in (crow, col, val))
+    bits = 32 if crow.dtype == np.int32 else 64
+    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    rc = load_library().exblas_exsptrsv_csr(u, d, m, bits, p(crow), p(col), p(val), p(x), int(fpe), int(bool(early_exit)))
+    if rc == SPTRSV_STALLED:
+        raise RuntimeError("exblas_amd: exsptrsv stalled: a wave gave up waiting for a solved value")
+    _check(rc, "exsptrsv")
+    return x
 
 
 def exspmm(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):

@@ -96,6 +96,7 @@ static void init_ctx(Ctx &c, int device, int layer)
         c.ngroups = z.ngroups; c.gemm_path = z.gemm_path;
         c.spmv_path = z.spmv_path;
         c.spmm_path = z.spmm_path;
+        c.sptrsv_path = z.sptrsv_path;
         c.gemm_max_slices = z.gemm_max_slices;
         c.gemm_max_moduli = z.gemm_max_moduli;
     }
@@ -468,6 +469,31 @@ int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&Ctx::spmv_in
 // out[3] chunks of the split rows
 int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_info_dev, out4); }
 
+void exblas_set_sptrsv_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsv_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
+
+// the header of a context's last ExSpTRSV (8 words; zeros when that call launched nothing); synchronises
+static int sptrsv_header(Ctx &c, long long (&h)[8])
+{
+    for (int i = 0; i < 8; ++i) h[i] = 0;
+    if (!c.sptrsv_info_dev) return 0;
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpy(h, c.sptrsv_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return 0;
+}
+
+// out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
+// under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
+int exblas_last_sptrsv_info(int64_t *out4)
+{
+    if (!out4) return (int)hipErrorInvalidValue;
+    Ctx &c = ctx(-1, g_last_layer[current_device()]);
+    std::lock_guard<std::mutex> lk(c.mu);
+    long long h[8];
+    const int rc = sptrsv_header(c, h);
+    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
+    return rc ? rc : (h[1] ? EXBLAS_SPTRSV_STALLED : 0);
+}
+
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
                                hipStream_t st)
@@ -538,6 +564,20 @@ static int exspmm_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exspmm_dispatch(c, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy,
                                 fpe, early_exit, round_mode(), st);
+}
+
+static bool one_of(char ch, const char *set) { return ch != 0 && strchr(set, ch) != nullptr; }
+
+static int exsptrsv_on(Ctx &c, char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                       const double *d_val, double *d_x, int fpe, int early_exit, hipStream_t st)
+{
+    if (!one_of(uplo, "LlUu") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    bool empty;   // m == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = csr_check_args(m, 0, 1, index_bits, d_row_ptr, nullptr, 1, d_x, 1, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exsptrsv_dispatch(c, uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                                  round_mode(), st);
 }
 
 static int extrsv_on(Ctx &c, char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x,
@@ -626,6 +666,13 @@ int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row
 {
     return exspmm_on(ctx(-1), m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
                      early_exit, (hipStream_t)stream);
+}
+
+int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                            const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
+{
+    return exsptrsv_on(ctx(-1), uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                       (hipStream_t)stream);
 }
 
 int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x, int incx,
@@ -782,6 +829,14 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, 
                      early_exit, (hipStream_t)stream);
 }
 
+int exblas_exsptrsv_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return exsptrsv_on(*cp, uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                       (hipStream_t)stream);
+}
+
 int exblas_extrsv_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x,
                       int incx, int fpe, int early_exit, void *stream)
 {
@@ -858,6 +913,7 @@ int exblas_release_workspace(void)
         c.gemm_info_dev = nullptr;  // it pointed into the workspace
         c.spmv_info_dev = nullptr;
         c.spmm_info_dev = nullptr;
+        c.sptrsv_info_dev = nullptr;
     });
     return (int)first;
 }
@@ -1286,6 +1342,24 @@ int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, 
                              return exspmm_on(c, m, n, k, index_bits, d_rp, d_ci, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
                                               early_exit, c.stream);
                          });
+}
+
+// the shared CSR host path with no X: x (b on entry, the solution on return) travels as its Y
+int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
+                        const double *val, double *x, int fpe, int early_exit)
+{
+    if (!one_of(uplo, "LlUu") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    const int rc = csr_host_call("exblas_exsptrsv_csr", m, 0, 1, index_bits, row_ptr, col_idx, val, nullptr, 1, x, 1, fpe,
+                                 [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *, double *d_x) {
+                                     return exsptrsv_on(c, uplo, diag, m, index_bits, d_rp, d_ci, d_val, d_x, fpe, early_exit,
+                                                        c.stream);
+                                 });
+    if (rc || m == 0) return rc;
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> lk(c.mu);
+    long long h[8];
+    if (int e = sptrsv_header(c, h)) return e;
+    return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

@@ -43,6 +43,9 @@ struct Ctx {
     int spmm_path = 0;       // exblas_set_spmm_path: 0 automatic, 1 every output rounded from an integer accumulator,
                              // 2 in-register rounding wherever certified (no row split), 3 every row split at a small chunk
     const long long *spmm_info_dev = nullptr;  // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
+    int sptrsv_path = 0;     // exblas_set_sptrsv_path: 0 automatic, 1 every row rounded from its integer accumulator,
+                             // 2 every row in the one-row-per-wave form
+    long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -153,6 +156,10 @@ hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row
 hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
                            const double *val, double alpha, const double *x, long long ldx, double beta, double *y,
                            long long ldy, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// sptrsv.hip
+hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
+                             const double *val, double *x, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

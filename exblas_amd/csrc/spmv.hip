@@ -23,18 +23,6 @@
 
 namespace exb {
 
-struct RowSink {
-    long long *col;   // the row's 68 limbs in LDS
-    unsigned &flags;
-    __device__ __forceinline__ void add(double x)
-    {
-        lds_add<1>(col, x, flags);
-        flags |= SP_SPILL;
-    }
-    __device__ __forceinline__ void note(unsigned bits) { flags |= bits | SP_SPILL; }
-};
-
-
 // ---------------------------------------------------------------------------------------------
 // classification
 // ---------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
-// spmv_common.hip.h -- what the sparse kernels (spmv.hip: ExSpMV, spmm.hip: ExSpMM) share: geometry constants, the
-// guarded gather of x, the certified in-register rounding test, the beta * y term, the chunk-base scan and chunk-owner
+// spmv_common.hip.h -- what the sparse kernels (spmv.hip: ExSpMV, spmm.hip: ExSpMM, sptrsv.hip: ExSpTRSV) share: geometry
+// constants, the guarded gather of x, the row sink, the certified in-register rounding test, the beta * y term, the chunk-base scan and chunk-owner
 // search of split rows, and the host-side choice of index type, plain / exact kernels and split thresholds.
 #pragma once
 #include "superacc.hip.h"
@@ -32,6 +32,18 @@ __device__ __forceinline__ double gather_x(const double *__restrict__ x, I c, in
     flags |= FLAG_NAN | SP_SPILL;
     return 0.0;
 }
+
+// what an expansion cannot hold goes to the row's integer accumulator in LDS; the row then rounds from it
+struct RowSink {
+    long long *col;   // the row's 68 limbs in LDS
+    unsigned &flags;
+    __device__ __forceinline__ void add(double x)
+    {
+        lds_add<1>(col, x, flags);
+        flags |= SP_SPILL;
+    }
+    __device__ __forceinline__ void note(unsigned bits) { flags |= bits | SP_SPILL; }
+};
 
 // Certified round-to-nearest-even of the exact value of an expansion f (any N terms, finite, |f| < 2^1012).
 // Two error-free VecSum passes leave S = f0 + f1 + sum_{i>=2} f_i exactly; res + q = f0 + f1 exactly (TwoSum).  Then

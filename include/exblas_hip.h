@@ -135,7 +135,7 @@ int exblas_reserve_workspace(size_t bytes);
  * than one pass can be needed).  ExSpMM: 1024 + 4 m + 8 ceil(m / r) t + 12 L + 576 k L bytes (each term rounded up to 256),
  * r = 64 / min(64, k rounded up to a power of two) rows per wave, t = ceil(k / 64) column tiles (one bitmap word per 64
  * outputs), L = min(m, floor(32 MiB / (576 k))) accumulator slots for split rows: at most 32 MiB whatever k is; rows
- * past L run whole. */
+ * past L run whole.  ExSpTRSV: 256 + 8 m bytes (the header and the mailbox of m doubles). */
 size_t exblas_workspace_bytes(void);
 /* Frees the workspace blocks that later, larger calls replaced.  Synchronises the device; only call it when no graph
  * captured before the growth will be replayed again. */
@@ -263,6 +263,43 @@ void exblas_set_spmm_path(int mode);
  * integer accumulator after the main kernel deferred them, out[2] rows split across workgroups, out[3] chunks of those
  * rows.  Synchronises the device; valid until the next call that uses the workspace; -1 when unknown. */
 int exblas_last_spmm_info(int64_t *out4);
+/* ExSpTRSV: exact, reproducible sparse triangular solve A x = b for a square m x m CSR matrix A on device pointers
+ * (row_ptr[m+1], col_idx[nnz] int32 or int64, both the same width; val and x contiguous fp64).  d_x holds b on entry and
+ * the solution on return, as in exblas_extrsv_dev.  uplo 'L': forward, rows 0 .. m-1,
+ *     T_i = b_i - sum over the stored p of row i with col_idx[p] < i of val[p] * x[col_idx[p]]
+ * exactly over the already fixed doubles x_j (every TwoProd pair goes in; duplicates of an off-diagonal column all
+ * count; the order of a row's entries does not matter), then x_i = Round(T_i) / d_i as one IEEE fp64 quotient for diag
+ * 'N' and x_i = Round(T_i) for diag 'U'.  Round is the superaccumulator rounding of the current rounding mode
+ * (exblas_set_round_mode).  uplo 'U' is the mirror image: rows m-1 .. 0, entries with col_idx[p] > i.  For the same
+ * logical system the bits are those of exblas_extrsv_dev on the densified matrix.
+ * d_i is the FIRST stored entry of row i with col_idx[p] == i, in storage order; later diagonal duplicates are skipped.
+ * A row without one divides by +0.0 (Inf or NaN, as exblas_extrsv_dev gives for a zero diagonal).  Under diag 'U' stored
+ * diagonal entries are skipped.  Entries of the other triangle are skipped and their values never used (a NaN there
+ * changes nothing), so a full matrix can be passed for a Gauss-Seidel sweep.  A column index outside [0, m) is never
+ * dereferenced and makes x_i NaN.  Product domain and Inf / NaN propagation: those of ExTRSV / ExSpMV (an explicit zero
+ * times an infinite x_j is NaN).  row_ptr entries must lie in [0, nnz].
+ * The bits depend on the data and (uplo, diag, rounding mode) only: not on the grid, the index width, the entry order
+ * inside a row, the path (exblas_set_sptrsv_path), fpe (0 or >= 2), early_exit, the context or the stream.  fpe == 0
+ * rounds every row from its integer accumulator; fpe == 1 is the plain fp64 solve on the same structure (not exact;
+ * its order of operations is fixed, so it is deterministic).
+ * One stream-ordered chain (a preset kernel and the solve kernel, the context workspace: 256 + 8 m bytes), no host
+ * synchronisation and no analysis phase: capturable into a hipGraph after exblas_reserve_workspace or one call of the same
+ * m.  m == 0: success, nothing is launched.  A uplo other than L/U, a diag other than N/U, m < 0, index_bits other than
+ * 32 / 64 or fpe < 0: hipErrorInvalidValue.  Returns 0 or a hipError_t.
+ * Not provided: A^T solves (pass the transposed CSR), several right-hand sides, other storage formats. */
+int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                            const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
+/* Test hook for ExSpTRSV (same bits on every path): 0 automatic, 1 every row rounded from its integer accumulator,
+ * 2 every row in the one-row-per-wave form (64 lanes stride the row, one row per work item). */
+void exblas_set_sptrsv_path(int mode);
+/* The most recent ExSpTRSV on this device: out[0] rows rounded in registers, out[1] rows rounded from their integer
+ * accumulator, out[2] rows without a stored diagonal under diag 'N', out[3] stored entries skipped (other triangle,
+ * diagonal under 'U', duplicate diagonals); all 0 after a call that launched nothing, out[0] = out[1] = 0 for fpe == 1.
+ * Synchronises the device; valid until the next call that uses the workspace.  Returns 0, a hipError_t, or
+ * EXBLAS_SPTRSV_STALLED when a wave of that call waited for one solved value for more than 2 s and gave up (the values
+ * behind it are NaN): a fault of the library, which no valid input causes. */
+#define EXBLAS_SPTRSV_STALLED (-3)
+int exblas_last_sptrsv_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -311,6 +348,8 @@ int exblas_exgemm_ctx(exblas_ctx_t *ctx, char transa, char transb, int m, int n,
 int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, double beta,
                           double *d_y, int fpe, int early_exit, void *stream);
+int exblas_exsptrsv_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
 int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
@@ -442,6 +481,11 @@ int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const v
 int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
                       double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
                       int early_exit);
+/* exblas_exsptrsv_csr_dev on host arrays (x: b on entry, the solution on return): staged through the device, synchronous.
+ * Returns 0, hipErrorInvalidValue (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see
+ * exblas_last_sptrsv_info). */
+int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
+                        const double *val, double *x, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
