@@ -48,6 +48,8 @@ C_ABI_SYMBOLS = [
     "exblas_last_spmm_info",
     "exblas_exsptrsv_csr_dev", "exblas_exsptrsv_csr_ctx", "exblas_exsptrsv_csr", "exblas_set_sptrsv_path",
     "exblas_last_sptrsv_info",
+    "exblas_exsptrsm_csr_dev", "exblas_exsptrsm_csr_ctx", "exblas_exsptrsm_csr", "exblas_set_sptrsm_path",
+    "exblas_last_sptrsm_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -185,6 +187,12 @@ def load_library():
     L.exblas_set_sptrsv_path.argtypes = [i32]
     L.exblas_set_sptrsv_path.restype = None
     L.exblas_last_sptrsv_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exsptrsm_csr_dev.argtypes = [C.c_char, C.c_char, i32, i32, i32, vp, vp, vp, vp, i64, i32, i32, vp]
+    L.exblas_exsptrsm_csr_ctx.argtypes = [vp] + L.exblas_exsptrsm_csr_dev.argtypes
+    L.exblas_exsptrsm_csr.argtypes = [C.c_char, C.c_char, i32, i32, i32, vp, vp, vp, vp, i64, i32, i32]
+    L.exblas_set_sptrsm_path.argtypes = [i32]
+    L.exblas_set_sptrsm_path.restype = None
+    L.exblas_last_sptrsm_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -510,6 +518,79 @@ def last_sptrsv_info():
     return tuple(int(v) for v in out)
 
 
+def _sptrsm_check(A, X, uplo, diag):
+    """Validates a device ExSpTRSM call before anything is launched; returns (crow, col, val, m, k, ldx, index_bits, uplo,
+    diag)."""
+    torch = _torch()
+    crow, col, val, m, n = _csr_parts(A)
+    if m != n:
+        raise ValueError(f"exsptrsm: A must be square, got shape ({m}, {n})")
+    u, d = _sptrsv_flags(uplo, diag)
+    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"exsptrsm: {name} must be a torch tensor")
+    if val.dtype != torch.float64 or X.dtype != torch.float64:
+        raise TypeError("exsptrsm: values and X must be float64")
+    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
+        raise TypeError("exsptrsm: row pointers and column indices must both be int32 or both int64")
+    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1:
+        raise ValueError("exsptrsm: crow, col and val must be 1-D")
+    if crow.numel() != m + 1:
+        raise ValueError(f"exsptrsm: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
+    if col.numel() != val.numel():
+        raise ValueError("exsptrsm: col and val differ in length")
+    if X.dim() == 1:
+        raise ValueError("exsptrsm: X must be a 2-D block of right-hand sides; for one vector use exsptrsv_dev")
+    if X.dim() != 2 or X.shape[0] != m:
+        raise ValueError(f"exsptrsm: X must be a 2-D float64 tensor of m = {m} rows")
+    k = int(X.shape[1])
+    # a block that does not conform is refused, not copied: it is solved in place
+    if X.stride(1) != 1:
+        raise ValueError("exsptrsm: X must be row-major with stride(1) == 1 (it is solved in place)")
+    if X.stride(0) < k:
+        raise ValueError(f"exsptrsm: the rows of X overlap: stride(0) = {X.stride(0)} < k = {k}")
+    devs = {t.device for t in (crow, col, val, X)}
+    if len(devs) != 1:
+        raise ValueError("exsptrsm: crow, col, val and X must be on one device")
+    _require_gpu()
+    if not val.is_cuda:
+        raise ValueError("exsptrsm: the tensors must be on the GPU")
+    ldx = int(X.stride(0))
+    return crow.contiguous(), col.contiguous(), val.contiguous(), m, k, ldx, (32 if crow.dtype == torch.int32 else 64), u, d
+
+
+def exsptrsm_dev(A, X, uplo="L", diag="N", fpe=8, early_exit=True):
+    """ExSpTRSM: solves A X = B in place on the m x k block X (B on entry) for k right-hand sides at once, exact and
+    reproducible, stream-ordered on the current stream: column j is bit for bit what exsptrsv_dev gives on B[:, j], and
+    the matrix is paid for once per row, not once per row and column.  A as for exsptrsv_dev; X a 2-D float64 tensor
+    with stride(1) == 1 and stride(0) >= k (a view [:, :k] of a wider block is fine: its padding is not touched).
+    Returns X."""
+    torch = _torch()
+    crow, col, val, m, k, ldx, bits, u, d = _sptrsm_check(A, X, uplo, diag)
+    _check(load_library().exblas_exsptrsm_csr_dev(u, d, m, k, bits, C.c_void_p(crow.data_ptr()),
+                                                  C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
+                                                  C.c_void_p(X.data_ptr()), ldx, int(fpe), int(bool(early_exit)),
+                                                  _stream_ptr(torch)), "exsptrsm_dev")
+    return X
+
+
+def set_sptrsm_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one row per work item, 3 column
+    panels and tiles of 4 columns.  Same bits on every path."""
+    load_library().exblas_set_sptrsm_path(int(mode))
+
+
+def last_sptrsm_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, rows without a stored diagonal under 'N',
+    stored entries skipped) of the last ExSpTRSM; raises when that call's watchdog was raised."""
+    out = (C.c_int64 * 4)()
+    rc = load_library().exblas_last_sptrsm_info(out)
+    if rc == SPTRSV_STALLED:
+        raise RuntimeError("exblas_amd: the last exsptrsm stalled: a wave gave up waiting for a solved value")
+    _check(rc, "last_sptrsm_info")
+    return tuple(int(v) for v in out)
+
+
 def _spmm_check(A, X, Y):
     """Validates a device ExSpMM call before anything is launched; returns (crow, col, val, X, m, n, k, index_bits, Y)."""
     torch = _torch()
@@ -682,6 +763,15 @@ class Context:
                                                       C.c_void_p(x.data_ptr()), int(fpe), int(bool(early_exit)),
                                                       _stream_ptr(torch)), "exsptrsv_ctx")
         return x
+
+    def exsptrsm(self, A, X, uplo="L", diag="N", fpe=8, early_exit=True):
+        torch = _torch()
+        crow, col, val, m, k, ldx, bits, u, d = _sptrsm_check(A, X, uplo, diag)
+        _check(load_library().exblas_exsptrsm_csr_ctx(self.handle, u, d, m, k, bits, C.c_void_p(crow.data_ptr()),
+                                                      C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
+                                                      C.c_void_p(X.data_ptr()), ldx, int(fpe), int(bool(early_exit)),
+                                                      _stream_ptr(torch)), "exsptrsm_ctx")
+        return X
 
     def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
         torch = _torch()
@@ -860,6 +950,43 @@ def exsptrsv(A, b, uplo="L", diag="N", fpe=8, early_exit=True):
         raise RuntimeError("exblas_amd: exsptrsv stalled: a wave gave up waiting for a solved value")
     _check(rc, "exsptrsv")
     return x
+
+
+def exsptrsm(A, B, uplo="L", diag="N", fpe=8, early_exit=True):
+    """ExSpTRSM on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv), B float64 of shape
+    (m, k); returns the solution (a new m x k float64 array; B is not changed)."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError("exsptrsm: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
+    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
+    if len(shape) != 2 or int(shape[0]) != int(shape[1]):
+        raise ValueError("exsptrsm: shape must be (m, m)")
+    m = int(shape[0])
+    u, d = _sptrsv_flags(uplo, diag)
+    B = np.asarray(B)
+    if val.dtype != np.float64 or B.dtype != np.float64:
+        raise TypeError("exsptrsm: values and B must be float64")
+    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
+        raise TypeError("exsptrsm: row pointers and column indices must both be int32 or both int64")
+    if B.ndim == 1:
+        raise ValueError("exsptrsm: B must be a 2-D block of right-hand sides; for one vector use exsptrsv")
+    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or B.ndim != 2:
+        raise ValueError("exsptrsm: row_ptr, col_idx and val must be 1-D, B 2-D")
+    if m < 0 or crow.size != m + 1 or col.size != val.size or B.shape[0] != m:
+        raise ValueError("exsptrsm: inconsistent sizes of row_ptr / col_idx / val / B")
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError("exsptrsm: row_ptr entries must lie in [0, nnz]")
+    X = np.array(B, dtype=np.float64, copy=True, order="C")
+    k = int(X.shape[1])
+    _require_gpu()
+    crow, col, val = (np.ascontiguousarray(a) for a in (crow, col, val))
+    bits = 32 if crow.dtype == np.int32 else 64
+    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    rc = load_library().exblas_exsptrsm_csr(u, d, m, k, bits, p(crow), p(col), p(val), p(X), max(k, 1), int(fpe),
+                                            int(bool(early_exit)))
+    if rc == SPTRSV_STALLED:
+        raise RuntimeError("exblas_amd: exsptrsm stalled: a wave gave up waiting for a solved value")
+    _check(rc, "exsptrsm")
+    return X
 
 
 def exspmm(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):

@@ -97,6 +97,7 @@ static void init_ctx(Ctx &c, int device, int layer)
         c.spmv_path = z.spmv_path;
         c.spmm_path = z.spmm_path;
         c.sptrsv_path = z.sptrsv_path;
+        c.sptrsm_path = z.sptrsm_path;
         c.gemm_max_slices = z.gemm_max_slices;
         c.gemm_max_moduli = z.gemm_max_moduli;
     }
@@ -471,28 +472,37 @@ int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_in
 
 void exblas_set_sptrsv_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsv_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
 
-// the header of a context's last ExSpTRSV (8 words; zeros when that call launched nothing); synchronises
-static int sptrsv_header(Ctx &c, long long (&h)[8])
+void exblas_set_sptrsm_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsm_path = sparse_path(mode); }); }
+
+// the header of a context's last ExSpTRSV or ExSpTRSM (8 words; zeros when that call launched nothing); synchronises
+static int solve_header(const long long *info_dev, long long (&h)[8])
 {
     for (int i = 0; i < 8; ++i) h[i] = 0;
-    if (!c.sptrsv_info_dev) return 0;
+    if (!info_dev) return 0;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(h, c.sptrsv_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    if (hipMemcpy(h, info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return 0;
 }
 
-// out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
-// under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
-int exblas_last_sptrsv_info(int64_t *out4)
+// the four counters of the last-used layer's last solve; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
+static int last_solve_info(long long *Ctx::*info_dev, int64_t *out4)
 {
     if (!out4) return (int)hipErrorInvalidValue;
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
     std::lock_guard<std::mutex> lk(c.mu);
     long long h[8];
-    const int rc = sptrsv_header(c, h);
+    const int rc = solve_header(c.*info_dev, h);
     for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
     return rc ? rc : (h[1] ? EXBLAS_SPTRSV_STALLED : 0);
 }
+
+// out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
+// under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
+int exblas_last_sptrsv_info(int64_t *out4) { return last_solve_info(&Ctx::sptrsv_info_dev, out4); }
+
+// out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
+// under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
+int exblas_last_sptrsm_info(int64_t *out4) { return last_solve_info(&Ctx::sptrsm_info_dev, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -577,6 +587,19 @@ static int exsptrsv_on(Ctx &c, char uplo, char diag, int m, int index_bits, cons
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exsptrsv_dispatch(c, uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                                  round_mode(), st);
+}
+
+static int exsptrsm_on(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                       const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                       hipStream_t st)
+{
+    if (!one_of(uplo, "LlUu") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    bool empty;   // m == 0 or k == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = csr_check_args(m, 0, k, index_bits, d_row_ptr, nullptr, k, d_x, ldx, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exsptrsm_dispatch(c, uplo, diag, m, k, index_bits, d_row_ptr, d_col_idx, d_val, d_x, ldx, fpe, early_exit,
                                   round_mode(), st);
 }
 
@@ -672,6 +695,14 @@ int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const v
                             const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
 {
     return exsptrsv_on(ctx(-1), uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                       (hipStream_t)stream);
+}
+
+int exblas_exsptrsm_csr_dev(char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                            void *stream)
+{
+    return exsptrsm_on(ctx(-1), uplo, diag, m, k, index_bits, d_row_ptr, d_col_idx, d_val, d_x, ldx, fpe, early_exit,
                        (hipStream_t)stream);
 }
 
@@ -837,6 +868,15 @@ int exblas_exsptrsv_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int in
                        (hipStream_t)stream);
 }
 
+int exblas_exsptrsm_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                            void *stream)
+{
+    EXB_HANDLE(h);
+    return exsptrsm_on(*cp, uplo, diag, m, k, index_bits, d_row_ptr, d_col_idx, d_val, d_x, ldx, fpe, early_exit,
+                       (hipStream_t)stream);
+}
+
 int exblas_extrsv_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x,
                       int incx, int fpe, int early_exit, void *stream)
 {
@@ -914,6 +954,7 @@ int exblas_release_workspace(void)
         c.spmv_info_dev = nullptr;
         c.spmm_info_dev = nullptr;
         c.sptrsv_info_dev = nullptr;
+        c.sptrsm_info_dev = nullptr;
     });
     return (int)first;
 }
@@ -1358,7 +1399,25 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
     Ctx &c = ctx(-1, 1);
     std::lock_guard<std::mutex> lk(c.mu);
     long long h[8];
-    if (int e = sptrsv_header(c, h)) return e;
+    if (int e = solve_header(c.sptrsv_info_dev, h)) return e;
+    return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
+}
+
+// the same with a block: X (m x k, row stride ldx; B on entry, the solution on return) travels as the host path's Y
+int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                        const double *val, double *x, int64_t ldx, int fpe, int early_exit)
+{
+    if (!one_of(uplo, "LlUu") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    const int rc = csr_host_call("exblas_exsptrsm_csr", m, 0, k, index_bits, row_ptr, col_idx, val, nullptr, k, x, ldx, fpe,
+                                 [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *, double *d_x) {
+                                     return exsptrsm_on(c, uplo, diag, m, k, index_bits, d_rp, d_ci, d_val, d_x, ldx, fpe,
+                                                        early_exit, c.stream);
+                                 });
+    if (rc || m == 0 || k == 0) return rc;
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> lk(c.mu);
+    long long h[8];
+    if (int e = solve_header(c.sptrsm_info_dev, h)) return e;
     return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
 }
 

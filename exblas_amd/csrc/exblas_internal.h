@@ -46,6 +46,9 @@ struct Ctx {
     int sptrsv_path = 0;     // exblas_set_sptrsv_path: 0 automatic, 1 every row rounded from its integer accumulator,
                              // 2 every row in the one-row-per-wave form
     long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
+    int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
+                             // per item, 3 column panels and tiles of 4 columns
+    long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -160,6 +163,11 @@ hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const vo
 // sptrsv.hip
 hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
                              const double *val, double *x, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// sptrsm.hip
+hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *row_ptr,
+                             const void *col_idx, const double *val, double *x, long long ldx, int fpe, int early_exit,
+                             int round_mode, hipStream_t st);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

@@ -135,7 +135,9 @@ int exblas_reserve_workspace(size_t bytes);
  * than one pass can be needed).  ExSpMM: 1024 + 4 m + 8 ceil(m / r) t + 12 L + 576 k L bytes (each term rounded up to 256),
  * r = 64 / min(64, k rounded up to a power of two) rows per wave, t = ceil(k / 64) column tiles (one bitmap word per 64
  * outputs), L = min(m, floor(32 MiB / (576 k))) accumulator slots for split rows: at most 32 MiB whatever k is; rows
- * past L run whole.  ExSpTRSV: 256 + 8 m bytes (the header and the mailbox of m doubles). */
+ * past L run whole.  ExSpTRSV: 256 + 8 m bytes (the header and the mailbox of m doubles).  ExSpTRSM: 256 + 8 m min(k, P)
+ * bytes (the header and the mailbox of one column panel), P = max(64, 64 floor(EXBLAS_SPTRSM_MAILBOX_BYTES / (8 m) / 64))
+ * columns per panel: at most 64 MiB (EXBLAS_SPTRSM_MAILBOX_BYTES) unless 512 m exceeds it. */
 size_t exblas_workspace_bytes(void);
 /* Frees the workspace blocks that later, larger calls replaced.  Synchronises the device; only call it when no graph
  * captured before the growth will be replayed again. */
@@ -286,7 +288,8 @@ int exblas_last_spmm_info(int64_t *out4);
  * synchronisation and no analysis phase: capturable into a hipGraph after exblas_reserve_workspace or one call of the same
  * m.  m == 0: success, nothing is launched.  A uplo other than L/U, a diag other than N/U, m < 0, index_bits other than
  * 32 / 64 or fpe < 0: hipErrorInvalidValue.  Returns 0 or a hipError_t.
- * Not provided: A^T solves (pass the transposed CSR), several right-hand sides, other storage formats. */
+ * Several right-hand sides: exblas_exsptrsm_csr_dev.  Not provided: A^T solves (pass the transposed CSR), other storage
+ * formats. */
 int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                             const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
 /* Test hook for ExSpTRSV (same bits on every path): 0 automatic, 1 every row rounded from its integer accumulator,
@@ -300,6 +303,41 @@ void exblas_set_sptrsv_path(int mode);
  * behind it are NaN): a fault of the library, which no valid input causes. */
 #define EXBLAS_SPTRSV_STALLED (-3)
 int exblas_last_sptrsv_info(int64_t *out4);
+/* ExSpTRSM: ExSpTRSV with k right-hand sides.  d_x is an m x k ROW-MAJOR block with leading dimension ldx >= k that holds
+ * B on entry and the solution on return.  For every column j, X[:, j] afterwards is bit for bit what
+ * exblas_exsptrsv_csr_dev writes for (uplo, diag, A, B[:, j]), with everything said there: per row, in substitution order,
+ *     x_ij = Round(b_ij - sum_p val[p] * x[col_idx[p], j]) / d_i
+ * the sum exact over the already fixed doubles and rounded once in the current rounding mode, then one IEEE division (none
+ * for diag 'U'); the first stored diagonal entry is the divisor; the other triangle and later diagonal entries are
+ * skipped unread; a column index outside [0, m) makes that row NaN in every column.  The bits depend on the data and
+ * (uplo, diag, rounding mode) only: not on k, ldx, the grid, the column panel, the index width, the entry order inside a
+ * row, the path (exblas_set_sptrsm_path), fpe (0 or >= 2), early_exit, the context or the stream.  fpe == 0 rounds every
+ * output from an integer accumulator; fpe == 1 is the plain fp64 solve on the same structure (deterministic, not exact).
+ * Columns are independent: a NaN or Inf in column j of B changes no bit of another column.  The padding of a row of X
+ * beyond column k - 1 is neither read nor written.  All offsets (row * ldx) are 64-bit.
+ * The matrix is paid for once per row, not once per row and column: lanes own columns, so the wait for a solved row, the
+ * loads of its indices and values and the work ticket serve all columns of a tile of 64.  Columns are solved in panels
+ * of min(k, P) columns, one after the other in stream order (each a preset kernel and a solve kernel), P the largest
+ * multiple of 64 with 8 m P <= EXBLAS_SPTRSM_MAILBOX_BYTES, at least 64 (see exblas_workspace_bytes).  No host
+ * synchronisation, no analysis phase: capturable into a hipGraph after exblas_reserve_workspace or one call with the
+ * same (m, k).  m == 0 or k == 0: success, nothing is launched; k == 1 is valid.  The argument errors of
+ * exblas_exsptrsv_csr_dev, k < 0 or ldx < k: hipErrorInvalidValue.  Returns 0 or a hipError_t.
+ * Not provided: A^T solves, a column-major X, other storage formats. */
+#define EXBLAS_SPTRSM_MAILBOX_BYTES ((size_t)64 << 20)
+int exblas_exsptrsm_csr_dev(char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                            void *stream);
+/* Test hook for ExSpTRSM (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
+ * 2 one row per work item, 3 column panels of 4 columns and column tiles of 4 (the seams between panels and tiles then
+ * occur at small k). */
+void exblas_set_sptrsm_path(int mode);
+/* The most recent ExSpTRSM on this device: out[0] outputs (i, j) rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] rows without a stored diagonal under diag 'N', out[3] stored entries skipped.  out[2] and
+ * out[3] count the structure once: they equal exblas_last_sptrsv_info's for the same A whatever k and the panel width;
+ * out[0] + out[1] == m * k for fpe != 1 (both 0 for fpe == 1); all 0 after a call that launched nothing.  Synchronises
+ * the device; valid until the next call that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as
+ * exblas_last_sptrsv_info does. */
+int exblas_last_sptrsm_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -350,6 +388,9 @@ int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const
                           double *d_y, int fpe, int early_exit, void *stream);
 int exblas_exsptrsv_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
                             const void *d_col_idx, const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
+int exblas_exsptrsm_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                            void *stream);
 int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
@@ -486,6 +527,11 @@ int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, 
  * exblas_last_sptrsv_info). */
 int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
                         const double *val, double *x, int fpe, int early_exit);
+/* exblas_exsptrsm_csr_dev on host arrays (x: the m x k row-major block with leading dimension ldx, B on entry, the solution
+ * on return; its padding comes back as it went): staged through the device, synchronous.  Returns 0, hipErrorInvalidValue
+ * (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see exblas_last_sptrsm_info). */
+int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                        const double *val, double *x, int64_t ldx, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
