@@ -364,70 +364,112 @@ def exgemm_dev(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe
     return c
 
 
-def _csr_parts(A):
-    """(crow, col, val, (m, n)) of a torch.sparse_csr_tensor or of a (crow, col, val, shape) tuple."""
-    if isinstance(A, (tuple, list)):
-        if len(A) != 4:
-            raise ValueError("exspmv: A must be a sparse CSR tensor or a (crow, col, val, shape) tuple")
-        crow, col, val, shape = A
-    else:
-        torch = _torch()
-        if getattr(A, "layout", None) != torch.sparse_csr:
-            raise TypeError("exspmv: A must be a torch.sparse_csr_tensor or a (crow, col, val, shape) tuple")
-        crow, col, val, shape = A.crow_indices(), A.col_indices(), A.values(), tuple(A.shape)
+def _csr_rules(who, xp, crow, col, val, shape, square):
+    """The rules the CSR arrays of routine `who` obey, whatever holds them (xp: torch or numpy); returns (m, n, index_bits)."""
     if len(shape) != 2:
-        raise ValueError(f"exspmv: A must be 2-D, got shape {tuple(shape)}")
+        raise ValueError(f"{who}: A must be 2-D, got shape {tuple(shape)}")
     m, n = int(shape[0]), int(shape[1])
     if m < 0 or n < 0 or m > 0x7fffffff or n > 0x7fffffff:
-        raise ValueError(f"exspmv: unsupported shape {tuple(shape)}")
-    return crow, col, val, m, n
+        raise ValueError(f"{who}: unsupported shape {tuple(shape)}")
+    if square and m != n:
+        raise ValueError(f"{who}: A must be square, got shape ({m}, {n})")
+    if val.dtype != xp.float64:
+        raise TypeError(f"{who}: values must be float64")
+    if crow.dtype not in (xp.int32, xp.int64) or col.dtype != crow.dtype:
+        raise TypeError(f"{who}: row pointers and column indices must both be int32 or both int64")
+    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1:
+        raise ValueError(f"{who}: crow, col and val must be 1-D")
+    if crow.shape[0] != m + 1:
+        raise ValueError(f"{who}: crow has {crow.shape[0]} entries, expected m + 1 = {m + 1}")
+    if col.shape[0] != val.shape[0]:
+        raise ValueError(f"{who}: col and val differ in length")
+    return m, n, (32 if crow.dtype == xp.int32 else 64)
 
 
-def _spmv_check(A, x, y):
-    """Validates a device ExSpMV call before anything is launched; returns (crow, col, val, m, n, index_bits, y)."""
+def _csr_dev(who, A, square=False):
+    """The CSR operand of the device routine `who`: a torch.sparse_csr_tensor or a (crow, col, val, shape) tuple of torch
+    tensors.  Refuses what is wrong with it without needing a GPU; returns (crow, col, val, m, n, index_bits)."""
     torch = _torch()
-    crow, col, val, m, n = _csr_parts(A)
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)):
+    if isinstance(A, (tuple, list)):
+        if len(A) != 4:
+            raise ValueError(f"{who}: A must be a sparse CSR tensor or a (crow, col, val, shape) tuple")
+        crow, col, val, shape = A
+    else:
+        if getattr(A, "layout", None) != torch.sparse_csr:
+            raise TypeError(f"{who}: A must be a torch.sparse_csr_tensor or a (crow, col, val, shape) tuple")
+        crow, col, val, shape = A.crow_indices(), A.col_indices(), A.values(), tuple(A.shape)
+    for name, t in (("crow", crow), ("col", col), ("val", val)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"exspmv: {name} must be a torch tensor")
-    if val.dtype != torch.float64 or x.dtype != torch.float64:
-        raise TypeError("exspmv: values and x must be float64")
-    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
-        raise TypeError("exspmv: row pointers and column indices must both be int32 or both int64")
-    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1 or x.dim() != 1:
-        raise ValueError("exspmv: crow, col, val and x must be 1-D")
-    if crow.numel() != m + 1:
-        raise ValueError(f"exspmv: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
-    if col.numel() != val.numel():
-        raise ValueError("exspmv: col and val differ in length")
+            raise TypeError(f"{who}: {name} must be a torch tensor")
+    m, n, bits = _csr_rules(who, torch, crow, col, val, shape, square)
+    return crow.contiguous(), col.contiguous(), val.contiguous(), m, n, bits
+
+
+def _dense_dev(who, name, t, ndim):
+    """The type rules of the dense operand `name` of the device routine `who`."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a torch tensor")
+    if t.dtype != torch.float64:
+        raise TypeError(f"{who}: {name} must be float64")
+    if t.dim() != ndim:
+        raise ValueError(f"{who}: {name} must be {ndim}-D")
+
+
+def _on_gpu(who, **tensors):
+    """The tensors of a device call lie on one device (refused without needing a GPU), and that device is a GPU."""
+    if len({t.device for t in tensors.values()}) != 1:
+        raise ValueError(f"{who}: {', '.join(tensors)} must be on one device")
+    _require_gpu()
+    if not all(t.is_cuda for t in tensors.values()):
+        raise ValueError(f"{who}: the tensors must be on the GPU")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+SPTRSV_STALLED = -3  # EXBLAS_SPTRSV_STALLED: the watchdog of an ExSpTRSV or ExSpTRSM call was raised
+
+
+def _check_sparse(rc, what):
+    """_check for the sparse routines: a solve whose watchdog was raised is an error of its own."""
+    if rc == SPTRSV_STALLED:
+        raise RuntimeError(f"exblas_amd: {what} stalled: a wave gave up waiting for a solved value")
+    _check(rc, what)
+
+
+def _last_info(routine):
+    """The four counters of the last call of a sparse routine ("spmv", "spmm", "sptrsv", "sptrsm")."""
+    out = (C.c_int64 * 4)()
+    _check_sparse(getattr(load_library(), f"exblas_last_{routine}_info")(out), f"the last ex{routine}")
+    return tuple(int(v) for v in out)
+
+
+def _spmv_args(A, x, y, alpha, beta, fpe, early_exit):
+    """Validates a device ExSpMV call before anything is launched; returns (y, the C arguments up to the stream)."""
+    crow, col, val, m, n, bits = _csr_dev("exspmv", A)
+    _dense_dev("exspmv", "x", x, 1)
     if x.numel() < n:
         raise ValueError(f"exspmv: x has {x.numel()} entries, fewer than n = {n}")
     if y is not None:
-        if not isinstance(y, torch.Tensor) or y.dtype != torch.float64 or y.dim() != 1 or y.numel() != m:
-            raise ValueError(f"exspmv: y must be a 1-D float64 tensor of m = {m} entries")
-        if not y.is_contiguous():
-            raise ValueError("exspmv: y must be contiguous")
-    _require_gpu()
-    dev = val.device
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)) + ((("y", y),) if y is not None else ()):
-        if not t.is_cuda or t.device != dev:
-            raise ValueError(f"exspmv: {name} must be on the GPU, on the device of the values")
-    crow, col, val, x = crow.contiguous(), col.contiguous(), val.contiguous(), x.contiguous()
+        _dense_dev("exspmv", "y", y, 1)
+        if y.numel() != m or not y.is_contiguous():
+            raise ValueError(f"exspmv: y must be a contiguous vector of m = {m} entries")
+    _on_gpu("exspmv", crow=crow, col=col, val=val, x=x, **({} if y is None else {"y": y}))
+    x = x.contiguous()
     if y is None:
-        y = torch.zeros(m, dtype=torch.float64, device=dev)
-    return crow, col, val, x, m, n, (32 if crow.dtype == torch.int32 else 64), y
+        y = _torch().zeros(m, dtype=x.dtype, device=x.device)
+    return y, (m, n, bits, _ptr(crow), _ptr(col), _ptr(val), float(alpha), _ptr(x), float(beta), _ptr(y), int(fpe),
+               int(bool(early_exit)))
 
 
 def exspmv_dev(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
     """ExSpMV: y = Round(alpha A x + beta y) row by row, exact and reproducible, stream-ordered on the current stream.
     A: torch.sparse_csr_tensor (float64 values, int32 or int64 indices) or (crow, col, val, (m, n)) on the GPU; x a
     float64 vector of at least n entries; y (m entries) is updated in place, or allocated (zeros) when None."""
-    torch = _torch()
-    crow, col, val, x, m, n, bits, y = _spmv_check(A, x, y)
-    _check(load_library().exblas_exspmv_csr_dev(m, n, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()),
-                                                C.c_void_p(val.data_ptr()), float(alpha), C.c_void_p(x.data_ptr()),
-                                                float(beta), C.c_void_p(y.data_ptr()), int(fpe), int(bool(early_exit)),
-                                                _stream_ptr(torch)), "exspmv_dev")
+    y, args = _spmv_args(A, x, y, alpha, beta, fpe, early_exit)
+    _check(load_library().exblas_exspmv_csr_dev(*args, _stream_ptr(_torch())), "exspmv_dev")
     return y
 
 
@@ -439,53 +481,26 @@ def set_spmv_path(mode):
 
 def last_spmv_info():
     """(rows rounded in registers, rows rounded from their accumulator, rows split, chunks) of the last ExSpMV."""
-    out = (C.c_int64 * 4)()
-    _check(load_library().exblas_last_spmv_info(out), "last_spmv_info")
-    return tuple(int(v) for v in out)
+    return _last_info("spmv")
 
 
-SPTRSV_STALLED = -3  # EXBLAS_SPTRSV_STALLED: the watchdog of an ExSpTRSV call was raised
-
-
-def _sptrsv_flags(uplo, diag):
+def _solve_flags(who, uplo, diag):
     if not isinstance(uplo, str) or uplo not in ("L", "l", "U", "u"):
-        raise ValueError(f"exsptrsv: uplo must be 'L' or 'U', got {uplo!r}")
+        raise ValueError(f"{who}: uplo must be 'L' or 'U', got {uplo!r}")
     if not isinstance(diag, str) or diag not in ("N", "n", "U", "u"):
-        raise ValueError(f"exsptrsv: diag must be 'N' or 'U', got {diag!r}")
+        raise ValueError(f"{who}: diag must be 'N' or 'U', got {diag!r}")
     return uplo.encode(), diag.encode()
 
 
-def _sptrsv_check(A, x, uplo, diag):
-    """Validates a device ExSpTRSV call before anything is launched; returns (crow, col, val, m, index_bits, uplo, diag)."""
-    torch = _torch()
-    crow, col, val, m, n = _csr_parts(A)
-    if m != n:
-        raise ValueError(f"exsptrsv: A must be square, got shape ({m}, {n})")
-    u, d = _sptrsv_flags(uplo, diag)
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("x", x)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"exsptrsv: {name} must be a torch tensor")
-    if val.dtype != torch.float64 or x.dtype != torch.float64:
-        raise TypeError("exsptrsv: values and x must be float64")
-    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
-        raise TypeError("exsptrsv: row pointers and column indices must both be int32 or both int64")
-    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1:
-        raise ValueError("exsptrsv: crow, col and val must be 1-D")
-    if crow.numel() != m + 1:
-        raise ValueError(f"exsptrsv: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
-    if col.numel() != val.numel():
-        raise ValueError("exsptrsv: col and val differ in length")
-    if x.dim() != 1 or x.numel() != m:
-        raise ValueError(f"exsptrsv: x must be a 1-D float64 tensor of m = {m} entries")
-    if not x.is_contiguous():
-        raise ValueError("exsptrsv: x must be contiguous (it is solved in place)")
-    devs = {t.device for t in (crow, col, val, x)}
-    if len(devs) != 1:
-        raise ValueError("exsptrsv: crow, col, val and x must be on one device")
-    _require_gpu()
-    if not val.is_cuda:
-        raise ValueError("exsptrsv: the tensors must be on the GPU")
-    return crow.contiguous(), col.contiguous(), val.contiguous(), m, (32 if crow.dtype == torch.int32 else 64), u, d
+def _sptrsv_args(A, x, uplo, diag, fpe, early_exit):
+    """Validates a device ExSpTRSV call before anything is launched; returns the C arguments up to the stream."""
+    crow, col, val, m, _, bits = _csr_dev("exsptrsv", A, square=True)
+    u, d = _solve_flags("exsptrsv", uplo, diag)
+    _dense_dev("exsptrsv", "x", x, 1)
+    if x.numel() != m or not x.is_contiguous():
+        raise ValueError(f"exsptrsv: x must be a contiguous vector of m = {m} entries (it is solved in place)")
+    _on_gpu("exsptrsv", crow=crow, col=col, val=val, x=x)
+    return (u, d, m, bits, _ptr(crow), _ptr(col), _ptr(val), _ptr(x), int(fpe), int(bool(early_exit)))
 
 
 def exsptrsv_dev(A, x, uplo="L", diag="N", fpe=8, early_exit=True):
@@ -493,11 +508,8 @@ def exsptrsv_dev(A, x, uplo="L", diag="N", fpe=8, early_exit=True):
     x_i = Round(b_i - sum of the stored val * x_j before the diagonal) / d_i in substitution order (diag 'U': no division),
     bit for bit what extrsv_dev gives on the densified matrix.  A: square torch.sparse_csr_tensor or (crow, col, val,
     (m, m)) on the GPU (float64 values, int32 or int64 indices); entries of the other triangle are skipped.  Returns x."""
-    torch = _torch()
-    crow, col, val, m, bits, u, d = _sptrsv_check(A, x, uplo, diag)
-    _check(load_library().exblas_exsptrsv_csr_dev(u, d, m, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()),
-                                                  C.c_void_p(val.data_ptr()), C.c_void_p(x.data_ptr()), int(fpe),
-                                                  int(bool(early_exit)), _stream_ptr(torch)), "exsptrsv_dev")
+    args = _sptrsv_args(A, x, uplo, diag, fpe, early_exit)
+    _check(load_library().exblas_exsptrsv_csr_dev(*args, _stream_ptr(_torch())), "exsptrsv_dev")
     return x
 
 
@@ -510,53 +522,26 @@ def set_sptrsv_path(mode):
 def last_sptrsv_info():
     """(rows rounded in registers, rows rounded from their accumulator, rows without a stored diagonal under 'N', stored
     entries skipped) of the last ExSpTRSV; raises when that call's watchdog was raised."""
-    out = (C.c_int64 * 4)()
-    rc = load_library().exblas_last_sptrsv_info(out)
-    if rc == SPTRSV_STALLED:
-        raise RuntimeError("exblas_amd: the last exsptrsv stalled: a wave gave up waiting for a solved value")
-    _check(rc, "last_sptrsv_info")
-    return tuple(int(v) for v in out)
+    return _last_info("sptrsv")
 
 
-def _sptrsm_check(A, X, uplo, diag):
-    """Validates a device ExSpTRSM call before anything is launched; returns (crow, col, val, m, k, ldx, index_bits, uplo,
-    diag)."""
-    torch = _torch()
-    crow, col, val, m, n = _csr_parts(A)
-    if m != n:
-        raise ValueError(f"exsptrsm: A must be square, got shape ({m}, {n})")
-    u, d = _sptrsv_flags(uplo, diag)
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"exsptrsm: {name} must be a torch tensor")
-    if val.dtype != torch.float64 or X.dtype != torch.float64:
-        raise TypeError("exsptrsm: values and X must be float64")
-    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
-        raise TypeError("exsptrsm: row pointers and column indices must both be int32 or both int64")
-    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1:
-        raise ValueError("exsptrsm: crow, col and val must be 1-D")
-    if crow.numel() != m + 1:
-        raise ValueError(f"exsptrsm: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
-    if col.numel() != val.numel():
-        raise ValueError("exsptrsm: col and val differ in length")
-    if X.dim() == 1:
+def _sptrsm_args(A, X, uplo, diag, fpe, early_exit):
+    """Validates a device ExSpTRSM call before anything is launched; returns the C arguments up to the stream."""
+    crow, col, val, m, _, bits = _csr_dev("exsptrsm", A, square=True)
+    u, d = _solve_flags("exsptrsm", uplo, diag)
+    if getattr(X, "ndim", 2) == 1:
         raise ValueError("exsptrsm: X must be a 2-D block of right-hand sides; for one vector use exsptrsv_dev")
-    if X.dim() != 2 or X.shape[0] != m:
-        raise ValueError(f"exsptrsm: X must be a 2-D float64 tensor of m = {m} rows")
+    _dense_dev("exsptrsm", "X", X, 2)
+    if X.shape[0] != m:
+        raise ValueError(f"exsptrsm: X must have m = {m} rows")
     k = int(X.shape[1])
     # a block that does not conform is refused, not copied: it is solved in place
     if X.stride(1) != 1:
         raise ValueError("exsptrsm: X must be row-major with stride(1) == 1 (it is solved in place)")
     if X.stride(0) < k:
         raise ValueError(f"exsptrsm: the rows of X overlap: stride(0) = {X.stride(0)} < k = {k}")
-    devs = {t.device for t in (crow, col, val, X)}
-    if len(devs) != 1:
-        raise ValueError("exsptrsm: crow, col, val and X must be on one device")
-    _require_gpu()
-    if not val.is_cuda:
-        raise ValueError("exsptrsm: the tensors must be on the GPU")
-    ldx = int(X.stride(0))
-    return crow.contiguous(), col.contiguous(), val.contiguous(), m, k, ldx, (32 if crow.dtype == torch.int32 else 64), u, d
+    _on_gpu("exsptrsm", crow=crow, col=col, val=val, X=X)
+    return (u, d, m, k, bits, _ptr(crow), _ptr(col), _ptr(val), _ptr(X), int(X.stride(0)), int(fpe), int(bool(early_exit)))
 
 
 def exsptrsm_dev(A, X, uplo="L", diag="N", fpe=8, early_exit=True):
@@ -565,12 +550,8 @@ def exsptrsm_dev(A, X, uplo="L", diag="N", fpe=8, early_exit=True):
     the matrix is paid for once per row, not once per row and column.  A as for exsptrsv_dev; X a 2-D float64 tensor
     with stride(1) == 1 and stride(0) >= k (a view [:, :k] of a wider block is fine: its padding is not touched).
     Returns X."""
-    torch = _torch()
-    crow, col, val, m, k, ldx, bits, u, d = _sptrsm_check(A, X, uplo, diag)
-    _check(load_library().exblas_exsptrsm_csr_dev(u, d, m, k, bits, C.c_void_p(crow.data_ptr()),
-                                                  C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
-                                                  C.c_void_p(X.data_ptr()), ldx, int(fpe), int(bool(early_exit)),
-                                                  _stream_ptr(torch)), "exsptrsm_dev")
+    args = _sptrsm_args(A, X, uplo, diag, fpe, early_exit)
+    _check(load_library().exblas_exsptrsm_csr_dev(*args, _stream_ptr(_torch())), "exsptrsm_dev")
     return X
 
 
@@ -583,52 +564,7 @@ def set_sptrsm_path(mode):
 def last_sptrsm_info():
     """(outputs rounded in registers, outputs rounded from the accumulator, rows without a stored diagonal under 'N',
     stored entries skipped) of the last ExSpTRSM; raises when that call's watchdog was raised."""
-    out = (C.c_int64 * 4)()
-    rc = load_library().exblas_last_sptrsm_info(out)
-    if rc == SPTRSV_STALLED:
-        raise RuntimeError("exblas_amd: the last exsptrsm stalled: a wave gave up waiting for a solved value")
-    _check(rc, "last_sptrsm_info")
-    return tuple(int(v) for v in out)
-
-
-def _spmm_check(A, X, Y):
-    """Validates a device ExSpMM call before anything is launched; returns (crow, col, val, X, m, n, k, index_bits, Y)."""
-    torch = _torch()
-    crow, col, val, m, n = _csr_parts(A)
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"exspmm: {name} must be a torch tensor")
-    if val.dtype != torch.float64 or X.dtype != torch.float64:
-        raise TypeError("exspmm: values and X must be float64")
-    if crow.dtype not in (torch.int32, torch.int64) or col.dtype != crow.dtype:
-        raise TypeError("exspmm: row pointers and column indices must both be int32 or both int64")
-    if X.dim() == 1:
-        raise ValueError("exspmm: X must be 2-D (n x k); for one vector use exspmv_dev")
-    if crow.dim() != 1 or col.dim() != 1 or val.dim() != 1 or X.dim() != 2:
-        raise ValueError("exspmm: crow, col and val must be 1-D and X 2-D")
-    if crow.numel() != m + 1:
-        raise ValueError(f"exspmm: crow has {crow.numel()} entries, expected m + 1 = {m + 1}")
-    if col.numel() != val.numel():
-        raise ValueError("exspmm: col and val differ in length")
-    if X.shape[0] < n:
-        raise ValueError(f"exspmm: X has {X.shape[0]} rows, fewer than n = {n}")
-    k = int(X.shape[1])
-    if Y is not None:
-        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.dim() != 2 or tuple(Y.shape) != (m, k):
-            raise ValueError(f"exspmm: Y must be a 2-D float64 tensor of shape ({m}, {k})")
-        if m > 0 and k > 0 and (Y.stride(1) != 1 or (m > 1 and Y.stride(0) < k)):
-            raise ValueError("exspmm: Y is updated in place: it needs stride(1) == 1 and stride(0) >= k")
-    _require_gpu()
-    dev = val.device
-    for name, t in (("crow", crow), ("col", col), ("val", val), ("X", X)) + ((("Y", Y),) if Y is not None else ()):
-        if not t.is_cuda or t.device != dev:
-            raise ValueError(f"exspmm: {name} must be on the GPU, on the device of the values")
-    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
-    if k > 0 and X.shape[0] > 0 and (X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < k)):
-        X = X.contiguous()
-    if Y is None:
-        Y = torch.zeros((m, k), dtype=torch.float64, device=dev)
-    return crow, col, val, X, m, n, k, (32 if crow.dtype == torch.int32 else 64), Y
+    return _last_info("sptrsm")
 
 
 def _ld(t, k):
@@ -636,10 +572,28 @@ def _ld(t, k):
     return max(int(t.stride(0)), k) if t.shape[0] > 1 else k
 
 
-def _spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha, beta, fpe, early_exit):
-    return (m, n, k, bits, C.c_void_p(crow.data_ptr()), C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
-            float(alpha), C.c_void_p(X.data_ptr()), _ld(X, k), float(beta), C.c_void_p(Y.data_ptr()), _ld(Y, k),
-            int(fpe), int(bool(early_exit)))
+def _spmm_args(A, X, Y, alpha, beta, fpe, early_exit):
+    """Validates a device ExSpMM call before anything is launched; returns (Y, the C arguments up to the stream)."""
+    crow, col, val, m, n, bits = _csr_dev("exspmm", A)
+    if getattr(X, "ndim", 2) == 1:
+        raise ValueError("exspmm: X must be 2-D (n x k); for one vector use exspmv_dev")
+    _dense_dev("exspmm", "X", X, 2)
+    if X.shape[0] < n:
+        raise ValueError(f"exspmm: X has {X.shape[0]} rows, fewer than n = {n}")
+    k = int(X.shape[1])
+    if Y is not None:
+        torch = _torch()
+        if not isinstance(Y, torch.Tensor) or Y.dtype != torch.float64 or Y.dim() != 2 or tuple(Y.shape) != (m, k):
+            raise ValueError(f"exspmm: Y must be a 2-D float64 tensor of shape ({m}, {k})")
+        if m > 0 and k > 0 and (Y.stride(1) != 1 or (m > 1 and Y.stride(0) < k)):
+            raise ValueError("exspmm: Y is updated in place: it needs stride(1) == 1 and stride(0) >= k")
+    _on_gpu("exspmm", crow=crow, col=col, val=val, X=X, **({} if Y is None else {"Y": Y}))
+    if k > 0 and X.shape[0] > 0 and (X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < k)):
+        X = X.contiguous()
+    if Y is None:
+        Y = _torch().zeros((m, k), dtype=X.dtype, device=X.device)
+    return Y, (m, n, k, bits, _ptr(crow), _ptr(col), _ptr(val), float(alpha), _ptr(X), _ld(X, k), float(beta), _ptr(Y),
+               _ld(Y, k), int(fpe), int(bool(early_exit)))
 
 
 def exspmm_dev(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
@@ -647,10 +601,8 @@ def exspmm_dev(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
     stream; column j is bit for bit exspmv_dev(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_dev; X a 2-D float64
     tensor with at least n rows (row-major: a copy is made when X.stride(1) != 1, otherwise ldx = X.stride(0)); Y (m x k,
     stride(1) == 1, stride(0) >= k) is updated in place, or allocated (zeros) when None."""
-    torch = _torch()
-    crow, col, val, X, m, n, k, bits, Y = _spmm_check(A, X, Y)
-    _check(load_library().exblas_exspmm_csr_dev(*_spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha, beta, fpe,
-                                                            early_exit), _stream_ptr(torch)), "exspmm_dev")
+    Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
+    _check(load_library().exblas_exspmm_csr_dev(*args, _stream_ptr(_torch())), "exspmm_dev")
     return Y
 
 
@@ -662,9 +614,7 @@ def set_spmm_path(mode):
 
 def last_spmm_info():
     """(outputs rounded in registers, outputs rounded from an accumulator, rows split, chunks) of the last ExSpMM."""
-    out = (C.c_int64 * 4)()
-    _check(load_library().exblas_last_spmm_info(out), "last_spmm_info")
-    return tuple(int(v) for v in out)
+    return _last_info("spmm")
 
 
 class Context:
@@ -746,39 +696,23 @@ class Context:
         return rc
 
     def exspmv(self, A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
-        torch = _torch()
-        crow, col, val, x, m, n, bits, y = _spmv_check(A, x, y)
-        _check(load_library().exblas_exspmv_csr_ctx(self.handle, m, n, bits, C.c_void_p(crow.data_ptr()),
-                                                    C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
-                                                    float(alpha), C.c_void_p(x.data_ptr()), float(beta),
-                                                    C.c_void_p(y.data_ptr()), int(fpe), int(bool(early_exit)),
-                                                    _stream_ptr(torch)), "exspmv_ctx")
+        y, args = _spmv_args(A, x, y, alpha, beta, fpe, early_exit)
+        _check(load_library().exblas_exspmv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmv_ctx")
         return y
 
     def exsptrsv(self, A, x, uplo="L", diag="N", fpe=8, early_exit=True):
-        torch = _torch()
-        crow, col, val, m, bits, u, d = _sptrsv_check(A, x, uplo, diag)
-        _check(load_library().exblas_exsptrsv_csr_ctx(self.handle, u, d, m, bits, C.c_void_p(crow.data_ptr()),
-                                                      C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
-                                                      C.c_void_p(x.data_ptr()), int(fpe), int(bool(early_exit)),
-                                                      _stream_ptr(torch)), "exsptrsv_ctx")
+        args = _sptrsv_args(A, x, uplo, diag, fpe, early_exit)
+        _check(load_library().exblas_exsptrsv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsv_ctx")
         return x
 
     def exsptrsm(self, A, X, uplo="L", diag="N", fpe=8, early_exit=True):
-        torch = _torch()
-        crow, col, val, m, k, ldx, bits, u, d = _sptrsm_check(A, X, uplo, diag)
-        _check(load_library().exblas_exsptrsm_csr_ctx(self.handle, u, d, m, k, bits, C.c_void_p(crow.data_ptr()),
-                                                      C.c_void_p(col.data_ptr()), C.c_void_p(val.data_ptr()),
-                                                      C.c_void_p(X.data_ptr()), ldx, int(fpe), int(bool(early_exit)),
-                                                      _stream_ptr(torch)), "exsptrsm_ctx")
+        args = _sptrsm_args(A, X, uplo, diag, fpe, early_exit)
+        _check(load_library().exblas_exsptrsm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsm_ctx")
         return X
 
     def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
-        torch = _torch()
-        crow, col, val, X, m, n, k, bits, Y = _spmm_check(A, X, Y)
-        _check(load_library().exblas_exspmm_csr_ctx(self.handle, *_spmm_args(crow, col, val, X, m, n, k, bits, Y, alpha,
-                                                                             beta, fpe, early_exit),
-                                                    _stream_ptr(torch)), "exspmm_ctx")
+        Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
+        _check(load_library().exblas_exspmm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmm_ctx")
         return Y
 
     def workspace_bytes(self):
@@ -887,140 +821,93 @@ def exgemm(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe, ea
                                         fpe, int(bool(early_exit)))
 
 
+def _csr_host(who, A, square=False):
+    """The CSR operand of the host routine `who`: a (row_ptr, col_idx, val, shape) tuple of numpy arrays.  Returns
+    (crow, col, val, m, n, index_bits) with the arrays contiguous."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError(f"{who}: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
+    crow, col, val = (np.asarray(a) for a in A[:3])
+    m, n, bits = _csr_rules(who, np, crow, col, val, A[3], square)
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError(f"{who}: row_ptr entries must lie in [0, nnz]")
+    return np.ascontiguousarray(crow), np.ascontiguousarray(col), np.ascontiguousarray(val), m, n, bits
+
+
+def _dense_host(who, name, a, ndim, hint=""):
+    """The dense operand `name` of the host routine `who` as a float64 array of `ndim` dimensions."""
+    a = np.asarray(a)
+    if a.dtype != np.float64:
+        raise TypeError(f"{who}: {name} must be float64")
+    if a.ndim != ndim:
+        raise ValueError(f"{who}: {name} must be {ndim}-D{hint}")
+    return a
+
+
+def _hptr(a):
+    return C.c_void_p(a.ctypes.data) if a.size else None
+
+
 def exspmv(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
     """ExSpMV on host arrays: A = (row_ptr, col_idx, val, (m, n)) as numpy arrays (int32 or int64 indices of one width,
     float64 values), x float64 of at least n entries; returns y (a new float64 array; the y passed in is not changed)."""
-    if not isinstance(A, (tuple, list)) or len(A) != 4:
-        raise ValueError("exspmv: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
-    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
-    if len(shape) != 2:
-        raise ValueError("exspmv: shape must be (m, n)")
-    m, n = int(shape[0]), int(shape[1])
-    x = np.asarray(x)
-    if val.dtype != np.float64 or x.dtype != np.float64:
-        raise TypeError("exspmv: values and x must be float64")
-    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
-        raise TypeError("exspmv: row pointers and column indices must both be int32 or both int64")
-    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or x.ndim != 1:
-        raise ValueError("exspmv: row_ptr, col_idx, val and x must be 1-D")
-    if crow.size != m + 1 or col.size != val.size or x.size < n:
-        raise ValueError("exspmv: inconsistent sizes of row_ptr / col_idx / val / x")
-    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
-        raise ValueError("exspmv: row_ptr entries must lie in [0, nnz]")
+    crow, col, val, m, n, bits = _csr_host("exspmv", A)
+    x = np.ascontiguousarray(_dense_host("exspmv", "x", x, 1))
+    if x.size < n:
+        raise ValueError(f"exspmv: x has {x.size} entries, fewer than n = {n}")
     y = np.zeros(m) if y is None else np.array(y, dtype=np.float64, copy=True)
     if y.ndim != 1 or y.size != m:
         raise ValueError(f"exspmv: y must have m = {m} entries")
     _require_gpu()
-    crow, col, val, x = (np.ascontiguousarray(a) for a in (crow, col, val, x))
-    bits = 32 if crow.dtype == np.int32 else 64
-    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
-    _check(load_library().exblas_exspmv_csr(m, n, bits, p(crow), p(col), p(val), float(alpha), p(x), float(beta),
-                                            p(y), int(fpe), int(bool(early_exit))), "exspmv")
+    _check(load_library().exblas_exspmv_csr(m, n, bits, _hptr(crow), _hptr(col), _hptr(val), float(alpha), _hptr(x),
+                                            float(beta), _hptr(y), int(fpe), int(bool(early_exit))), "exspmv")
     return y
 
 
 def exsptrsv(A, b, uplo="L", diag="N", fpe=8, early_exit=True):
     """ExSpTRSV on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv), b float64 of m entries;
     returns the solution (a new float64 array; b is not changed)."""
-    if not isinstance(A, (tuple, list)) or len(A) != 4:
-        raise ValueError("exsptrsv: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
-    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
-    if len(shape) != 2 or int(shape[0]) != int(shape[1]):
-        raise ValueError("exsptrsv: shape must be (m, m)")
-    m = int(shape[0])
-    u, d = _sptrsv_flags(uplo, diag)
-    b = np.asarray(b)
-    if val.dtype != np.float64 or b.dtype != np.float64:
-        raise TypeError("exsptrsv: values and b must be float64")
-    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
-        raise TypeError("exsptrsv: row pointers and column indices must both be int32 or both int64")
-    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or b.ndim != 1:
-        raise ValueError("exsptrsv: row_ptr, col_idx, val and b must be 1-D")
-    if m < 0 or crow.size != m + 1 or col.size != val.size or b.size != m:
-        raise ValueError("exsptrsv: inconsistent sizes of row_ptr / col_idx / val / b")
-    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
-        raise ValueError("exsptrsv: row_ptr entries must lie in [0, nnz]")
+    crow, col, val, m, _, bits = _csr_host("exsptrsv", A, square=True)
+    u, d = _solve_flags("exsptrsv", uplo, diag)
+    b = _dense_host("exsptrsv", "b", b, 1)
+    if b.size != m:
+        raise ValueError(f"exsptrsv: b must have m = {m} entries")
     x = np.array(b, dtype=np.float64, copy=True)
     _require_gpu()
-    crow, col, val = (np.ascontiguousarray(a) for a in (crow, col, val))
-    bits = 32 if crow.dtype == np.int32 else 64
-    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
-    rc = load_library().exblas_exsptrsv_csr(u, d, m, bits, p(crow), p(col), p(val), p(x), int(fpe), int(bool(early_exit)))
-    if rc == SPTRSV_STALLED:
-        raise RuntimeError("exblas_amd: exsptrsv stalled: a wave gave up waiting for a solved value")
-    _check(rc, "exsptrsv")
+    _check_sparse(load_library().exblas_exsptrsv_csr(u, d, m, bits, _hptr(crow), _hptr(col), _hptr(val), _hptr(x),
+                                                     int(fpe), int(bool(early_exit))), "exsptrsv")
     return x
 
 
 def exsptrsm(A, B, uplo="L", diag="N", fpe=8, early_exit=True):
     """ExSpTRSM on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv), B float64 of shape
     (m, k); returns the solution (a new m x k float64 array; B is not changed)."""
-    if not isinstance(A, (tuple, list)) or len(A) != 4:
-        raise ValueError("exsptrsm: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
-    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
-    if len(shape) != 2 or int(shape[0]) != int(shape[1]):
-        raise ValueError("exsptrsm: shape must be (m, m)")
-    m = int(shape[0])
-    u, d = _sptrsv_flags(uplo, diag)
-    B = np.asarray(B)
-    if val.dtype != np.float64 or B.dtype != np.float64:
-        raise TypeError("exsptrsm: values and B must be float64")
-    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
-        raise TypeError("exsptrsm: row pointers and column indices must both be int32 or both int64")
-    if B.ndim == 1:
-        raise ValueError("exsptrsm: B must be a 2-D block of right-hand sides; for one vector use exsptrsv")
-    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or B.ndim != 2:
-        raise ValueError("exsptrsm: row_ptr, col_idx and val must be 1-D, B 2-D")
-    if m < 0 or crow.size != m + 1 or col.size != val.size or B.shape[0] != m:
-        raise ValueError("exsptrsm: inconsistent sizes of row_ptr / col_idx / val / B")
-    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
-        raise ValueError("exsptrsm: row_ptr entries must lie in [0, nnz]")
+    crow, col, val, m, _, bits = _csr_host("exsptrsm", A, square=True)
+    u, d = _solve_flags("exsptrsm", uplo, diag)
+    B = _dense_host("exsptrsm", "B", B, 2, " (a block of right-hand sides; for one vector use exsptrsv)")
+    if B.shape[0] != m:
+        raise ValueError(f"exsptrsm: B must have m = {m} rows")
     X = np.array(B, dtype=np.float64, copy=True, order="C")
     k = int(X.shape[1])
     _require_gpu()
-    crow, col, val = (np.ascontiguousarray(a) for a in (crow, col, val))
-    bits = 32 if crow.dtype == np.int32 else 64
-    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
-    rc = load_library().exblas_exsptrsm_csr(u, d, m, k, bits, p(crow), p(col), p(val), p(X), max(k, 1), int(fpe),
-                                            int(bool(early_exit)))
-    if rc == SPTRSV_STALLED:
-        raise RuntimeError("exblas_amd: exsptrsm stalled: a wave gave up waiting for a solved value")
-    _check(rc, "exsptrsm")
+    _check_sparse(load_library().exblas_exsptrsm_csr(u, d, m, k, bits, _hptr(crow), _hptr(col), _hptr(val), _hptr(X),
+                                                     max(k, 1), int(fpe), int(bool(early_exit))), "exsptrsm")
     return X
 
 
 def exspmm(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
     """ExSpMM on host arrays: A = (row_ptr, col_idx, val, (m, n)) as numpy arrays (as for exspmv), X float64 of shape
     (rows >= n, k); returns Y (a new m x k float64 array; the Y passed in is not changed)."""
-    if not isinstance(A, (tuple, list)) or len(A) != 4:
-        raise ValueError("exspmm: A must be a (row_ptr, col_idx, val, shape) tuple of numpy arrays")
-    crow, col, val, shape = (np.asarray(A[0]), np.asarray(A[1]), np.asarray(A[2]), A[3])
-    if len(shape) != 2:
-        raise ValueError("exspmm: shape must be (m, n)")
-    m, n = int(shape[0]), int(shape[1])
-    X = np.asarray(X)
-    if val.dtype != np.float64 or X.dtype != np.float64:
-        raise TypeError("exspmm: values and X must be float64")
-    if crow.dtype not in (np.int32, np.int64) or col.dtype != crow.dtype:
-        raise TypeError("exspmm: row pointers and column indices must both be int32 or both int64")
-    if X.ndim == 1:
-        raise ValueError("exspmm: X must be 2-D (n x k); for one vector use exspmv")
-    if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1 or X.ndim != 2:
-        raise ValueError("exspmm: row_ptr, col_idx and val must be 1-D and X 2-D")
-    if crow.size != m + 1 or col.size != val.size or X.shape[0] < n:
-        raise ValueError("exspmm: inconsistent sizes of row_ptr / col_idx / val / X")
-    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
-        raise ValueError("exspmm: row_ptr entries must lie in [0, nnz]")
+    crow, col, val, m, n, bits = _csr_host("exspmm", A)
+    X = np.ascontiguousarray(_dense_host("exspmm", "X", X, 2, " (n x k; for one vector use exspmv)"))
+    if X.shape[0] < n:
+        raise ValueError(f"exspmm: X has {X.shape[0]} rows, fewer than n = {n}")
     k = int(X.shape[1])
     Y = np.zeros((m, k)) if Y is None else np.array(Y, dtype=np.float64, copy=True, order="C")
     if Y.shape != (m, k):
         raise ValueError(f"exspmm: Y must have shape ({m}, {k})")
     _require_gpu()
-    crow, col, val, X = (np.ascontiguousarray(a) for a in (crow, col, val, X))
-    bits = 32 if crow.dtype == np.int32 else 64
-    p = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
-    _check(load_library().exblas_exspmm_csr(m, n, k, bits, p(crow), p(col), p(val), float(alpha), p(X), k, float(beta),
-                                            p(Y), k, int(fpe), int(bool(early_exit))), "exspmm")
+    _check(load_library().exblas_exspmm_csr(m, n, k, bits, _hptr(crow), _hptr(col), _hptr(val), float(alpha), _hptr(X), k,
+                                            float(beta), _hptr(Y), k, int(fpe), int(bool(early_exit))), "exspmm")
     return Y
 
 

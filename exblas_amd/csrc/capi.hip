@@ -447,62 +447,50 @@ static int sparse_path(int mode) { return (mode >= 0 && mode <= 3) ? mode : 0; }
 void exblas_set_spmv_path(int mode) { for_each_layer([&](Ctx &c) { c.spmv_path = sparse_path(mode); }); }
 void exblas_set_spmm_path(int mode) { for_each_layer([&](Ctx &c) { c.spmm_path = sparse_path(mode); }); }
 
-// the four counters of the last sparse call on the last-used layer, from its workspace header (synchronises)
-static int last_sparse_info(const long long *Ctx::*info_dev, int64_t *out4)
+// the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
+static int sparse_header(const long long *info_dev, long long (&h)[8])
+{
+    for (int i = 0; i < 8; ++i) h[i] = 0;
+    if (!info_dev) return 0;
+    if (hipDeviceSynchronize() == hipSuccess && hipMemcpy(h, info_dev, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess)
+        return 0;
+    for (int i = 0; i < 8; ++i) h[i] = 0;
+    return -1;
+}
+
+// The four counters of the last sparse call on the last-used layer.  ExSpMV / ExSpMM: -1 when there was no call.  The two
+// solves (`solve`): a call that launched nothing counts zeros; EXBLAS_SPTRSV_STALLED when that call's watchdog was raised.
+static int last_sparse_info(const long long *Ctx::*info_dev, bool solve, int64_t *out4)
 {
     if (!out4) return (int)hipErrorInvalidValue;
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
     std::lock_guard<std::mutex> lk(c.mu);
-    for (int i = 0; i < 4; ++i) out4[i] = 0;
-    if (!(c.*info_dev)) return -1;
     long long h[8];
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(h, c.*info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    const int rc = sparse_header(c.*info_dev, h);
     for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
-    return 0;
+    if (rc || (!solve && !(c.*info_dev))) return -1;
+    return (solve && h[1]) ? EXBLAS_SPTRSV_STALLED : 0;
 }
 
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows split across workgroups,
 // out[3] chunks of the split rows
-int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&Ctx::spmv_info_dev, out4); }
+int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&Ctx::spmv_info_dev, false, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from an accumulator, out[2] rows split across workgroups,
 // out[3] chunks of the split rows
-int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_info_dev, out4); }
+int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_info_dev, false, out4); }
 
 void exblas_set_sptrsv_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsv_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
 
 void exblas_set_sptrsm_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsm_path = sparse_path(mode); }); }
 
-// the header of a context's last ExSpTRSV or ExSpTRSM (8 words; zeros when that call launched nothing); synchronises
-static int solve_header(const long long *info_dev, long long (&h)[8])
-{
-    for (int i = 0; i < 8; ++i) h[i] = 0;
-    if (!info_dev) return 0;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpy(h, info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return 0;
-}
-
-// the four counters of the last-used layer's last solve; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
-static int last_solve_info(long long *Ctx::*info_dev, int64_t *out4)
-{
-    if (!out4) return (int)hipErrorInvalidValue;
-    Ctx &c = ctx(-1, g_last_layer[current_device()]);
-    std::lock_guard<std::mutex> lk(c.mu);
-    long long h[8];
-    const int rc = solve_header(c.*info_dev, h);
-    for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
-    return rc ? rc : (h[1] ? EXBLAS_SPTRSV_STALLED : 0);
-}
-
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
-int exblas_last_sptrsv_info(int64_t *out4) { return last_solve_info(&Ctx::sptrsv_info_dev, out4); }
+int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&Ctx::sptrsv_info_dev, true, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
-int exblas_last_sptrsm_info(int64_t *out4) { return last_solve_info(&Ctx::sptrsm_info_dev, out4); }
+int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&Ctx::sptrsm_info_dev, true, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -1399,7 +1387,7 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
     Ctx &c = ctx(-1, 1);
     std::lock_guard<std::mutex> lk(c.mu);
     long long h[8];
-    if (int e = solve_header(c.sptrsv_info_dev, h)) return e;
+    if (int e = sparse_header(c.sptrsv_info_dev, h)) return e;
     return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
 }
 
@@ -1417,7 +1405,7 @@ int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, cons
     Ctx &c = ctx(-1, 1);
     std::lock_guard<std::mutex> lk(c.mu);
     long long h[8];
-    if (int e = solve_header(c.sptrsm_info_dev, h)) return e;
+    if (int e = sparse_header(c.sptrsm_info_dev, h)) return e;
     return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
 }
 

@@ -45,10 +45,10 @@ struct Ctx {
     const long long *spmm_info_dev = nullptr;  // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
     int sptrsv_path = 0;     // exblas_set_sptrsv_path: 0 automatic, 1 every row rounded from its integer accumulator,
                              // 2 every row in the one-row-per-wave form
-    long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
+    const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
-    long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
+    const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1

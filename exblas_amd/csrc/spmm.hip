@@ -271,24 +271,15 @@ __device__ __forceinline__ unsigned long long spmm_finish_some(unsigned long lon
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    const unsigned long long f_pinf = __ballot((flags & FLAG_PINF) != 0), f_ninf = __ballot((flags & FLAG_NINF) != 0),
-                             f_nan = __ballot((flags & FLAG_NAN) != 0);
+    sp_wave_sync();
+    const NonFiniteLanes nf(flags);
     for (int s = 0; s < count; ++s) {   // wave-uniform: every lane runs the finish of each output
         const unsigned long long gm = G2 == 64 ? ~0ull : (((1ull << (G2 & 63)) - 1ull) << (s * (G2 & 63)));
-        const unsigned fl = ((f_pinf & gm) ? FLAG_PINF : 0u) | ((f_ninf & gm) ? FLAG_NINF : 0u) |
-                            ((f_nan & gm) ? FLAG_NAN : 0u);
-        long long *a = acc[s];
-        const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
-        const WaveFinish r = finish_wave(v0, v1, fl);
+        const double v = sp_acc_round(acc[s], nf.of(gm), round_mode);
         const long long o_row = __shfl(row, s * G2, 64), o_j = __shfl(j, s * G2, 64);
-        if (lane == 0) y[o_row * ldy + o_j] = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
-        a[lane] = 0;
-        if (lane < NL - 64) a[64 + lane] = 0;
+        if (lane == 0) y[o_row * ldy + o_j] = v;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    sp_wave_sync();
     return bits;
 }
 
@@ -304,8 +295,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_deferred(int m, int n, ItemGe
     __shared__ long long acc[SP_WAVES][NACC][NL];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     for (int t = lane; t < NACC * NL; t += 64) (&acc[w][0][0])[t] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    sp_wave_sync();
     const long long wave0 = (long long)blockIdx.x * SP_WAVES + w, nwaves = (long long)gridDim.x * SP_WAVES;
     // a wave looks at `span` (<= 64) bitmap words per step: 64 when there are items enough for every wave, fewer when not
     for (long long base = wave0 * span; base < nitems; base += nwaves * span) {
@@ -419,7 +409,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int 
             unsigned flags = (g[NL] ? FLAG_PINF : 0u) | (g[NL + 1] ? FLAG_NINF : 0u) | (g[NL + 2] ? FLAG_NAN : 0u);
             sp_wave_add_beta(v0, v1, beta, yp, 0, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
-            if (lane == 0) *yp = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
+            if (lane == 0) *yp = sp_pick(r, round_mode);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[6] = nl;

@@ -125,50 +125,27 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
             sp_absorb_beta(f, valid && sub == 0, beta, y, row, sink);
             // exact tree merge of the group's expansions into its first lane
 #pragma unroll
-            for (int s = 1; s < G; s <<= 1) {
-                const bool take = (sub & (2 * s - 1)) == 0;
-                double q[SP_N];
-#pragma unroll
-                for (int i = 0; i < SP_N; ++i) {
-                    const double t = __shfl_down(f[i], s, 64);
-                    q[i] = take ? t : 0.0;
-                }
-                const unsigned fo = __shfl_down(flags, s, 64);
-                if (take) flags |= fo;
-                fpe_cascade<SP_N, true, SP_N>(f, q, 0, sink);
-            }
+            for (int s = 1; s < G; s <<= 1) sp_cascade_step(f, flags, s, (sub & (2 * s - 1)) == 0, sink);
             const bool leader = valid && sub == 0;
             bool fb = false;
             if (leader) {
                 double r;
-                if (!force_fb && flags == 0 && spmv_round_fast<SP_N>(f, r)) {
-                    y[row] = r;
-                } else {
-                    fb = true;
-#pragma unroll
-                    for (int i = 0; i < SP_N; ++i)
-                        if (f[i] != 0.0) lds_add<1>(acc[w][slot], f[i], flags);
-                }
+                fb = !sp_certify_or_spill(f, flags, force_fb, acc[w][slot], r);
+                if (!fb) y[row] = r;
             }
             n_reg += __popcll(__ballot(leader && !fb));
             unsigned long long fbm = __ballot(fb);
             n_fb += __popcll(fbm);
             if (fbm) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                sp_wave_sync();
                 while (fbm) {   // wave-uniform: every lane runs the finish of each falling-back row
                     const int l = __builtin_ctzll(fbm), sl = l / G;
                     fbm &= fbm - 1ull;
                     const unsigned fl = (unsigned)__shfl((int)flags, l, 64) & FLAG_NONFINITE;
                     const long long r_row = __shfl(row, l, 64);
-                    long long *a = acc[w][sl];
-                    const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
-                    const WaveFinish r = finish_wave(v0, v1, fl);
-                    if (lane == 0) y[r_row] = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
-                    a[lane] = 0;
-                    if (lane < NL - 64) a[64 + lane] = 0;
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
+                    const double v = sp_acc_round(acc[w][sl], fl, round_mode);
+                    if (lane == 0) y[r_row] = v;
+                    sp_wave_sync();
                 }
             }
         }
@@ -233,19 +210,16 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restri
                 fpe_absorb_prod<SP_N, true, U>(f, p, er, sink);
             }
             fpe_flush_sink<SP_N>(f, sink);
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            sp_wave_sync();
             const unsigned long long any = __ballot((flags & SP_SPILL) != 0);
             if (any) {
                 const long long v0 = acc[w][lane], v1 = lane < NL - 64 ? acc[w][64 + lane] : 0;
                 if (v0) atomicAdd((unsigned long long *)&g[lane], (unsigned long long)v0);
                 if (v1) atomicAdd((unsigned long long *)&g[64 + lane], (unsigned long long)v1);
-                acc[w][lane] = 0;
-                if (lane < NL - 64) acc[w][64 + lane] = 0;
+                sp_acc_clear(acc[w]);
                 const unsigned nf = flags & FLAG_NONFINITE;
                 if (nf) atomicOr((unsigned *)&g[SP_ACC_FLAGS], nf);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                sp_wave_sync();
             }
         }
     }
@@ -273,7 +247,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__rest
             unsigned flags = (unsigned)g[SP_ACC_FLAGS] & FLAG_NONFINITE;
             sp_wave_add_beta(v0, v1, beta, y, row, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
-            if (lane == 0) y[row] = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
+            if (lane == 0) y[row] = sp_pick(r, round_mode);
         }
     }
     if (lane == 0 && n_rows) atomicAdd((unsigned long long *)&hdr[6], n_rows);

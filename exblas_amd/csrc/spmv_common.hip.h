@@ -1,6 +1,10 @@
-// spmv_common.hip.h -- what the sparse kernels (spmv.hip: ExSpMV, spmm.hip: ExSpMM, sptrsv.hip: ExSpTRSV) share: geometry
-// constants, the guarded gather of x, the row sink, the certified in-register rounding test, the beta * y term, the chunk-base scan and chunk-owner
-// search of split rows, and the host-side choice of index type, plain / exact kernels and split thresholds.
+// spmv_common.hip.h -- what the four sparse routines (spmv.hip: ExSpMV, spmm.hip: ExSpMM, sptrsv.hip: ExSpTRSV, sptrsm.hip:
+// ExSpTRSM) share.  The row step: the guarded gather of x, the row sink, the beta * y term, one step of the exact merge of
+// lane expansions (sp_cascade_step), the certified in-register rounding test (spmv_round_fast) and the leader's use of it
+// with the spill into the row's accumulator behind it (sp_certify_or_spill), the rounding of an LDS integer accumulator
+// (sp_acc_round, with sp_pick and sp_acc_clear), the union of a lane group's non-finite flags (NonFiniteLanes) and the
+// wave's LDS hand-over (sp_wave_sync).  Split rows: the chunk-base scan and the chunk-owner search.  Host side: geometry
+// constants, the choice of index type and plain / exact kernels, the split thresholds.
 #pragma once
 #include "superacc.hip.h"
 #include "fpe.hip.h"
@@ -88,6 +92,79 @@ __device__ __forceinline__ bool spmv_round_fast(double (&f)[N], double &out)
     out = res;
     return true;
 }
+
+// between a wave's lanes writing LDS and other lanes of it reading (or overwriting) the same words
+__device__ __forceinline__ void sp_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// One step of the exact merge of lane expansions: a lane where `take` holds absorbs the expansion and the flags of the lane
+// `stride` above it.  SKIP leaves the cascade out when no lane of the wave took a non-zero term (wave-uniform).
+template <bool SKIP = false, class Sink>
+__device__ __forceinline__ void sp_cascade_step(double (&f)[SP_N], unsigned &flags, int stride, bool take, Sink &sink)
+{
+    double q[SP_N];
+#pragma unroll
+    for (int i = 0; i < SP_N; ++i) {
+        const double t = __shfl_down(f[i], stride, 64);
+        q[i] = take ? t : 0.0;
+    }
+    const unsigned fo = __shfl_down(flags, stride, 64);
+    if (take) flags |= fo;
+    if (!SKIP || __any(any_nonzero<SP_N>(q))) fpe_cascade<SP_N, true, SP_N>(f, q, 0, sink);
+}
+
+// A row's leader rounds its merged expansion: true with the certified value in `out`, or false after adding the non-zero
+// terms to the row's accumulator `acc`, which the wave then rounds (sp_acc_round)
+__device__ __forceinline__ bool sp_certify_or_spill(double (&f)[SP_N], unsigned &flags, int force_fb, long long *acc,
+                                                    double &out)
+{
+    if (!force_fb && flags == 0 && spmv_round_fast<SP_N>(f, out)) return true;
+#pragma unroll
+    for (int i = 0; i < SP_N; ++i)
+        if (f[i] != 0.0) lds_add<1>(acc, f[i], flags);
+    return false;
+}
+
+// the value of a finished accumulator under the rounding mode (0: nearest even, else the reference's)
+__device__ __forceinline__ double sp_pick(const WaveFinish &r, int round_mode)
+{
+    return round_mode ? r.rf : __longlong_as_double((long long)r.ex);
+}
+
+__device__ __forceinline__ void sp_acc_clear(long long *a)
+{
+    const int lane = threadIdx.x & 63;
+    a[lane] = 0;
+    if (lane < NL - 64) a[64 + lane] = 0;
+}
+
+// Rounds the NL limbs of an LDS accumulator that the whole wave runs through (every lane gets the value) and leaves them
+// zero; `nonfinite` is wave-uniform.  The caller separates it from the lanes' adds, and from the next ones, by sp_wave_sync.
+__device__ __forceinline__ double sp_acc_round(long long *a, unsigned nonfinite, int round_mode)
+{
+    const int lane = threadIdx.x & 63;
+    const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
+    const WaveFinish r = finish_wave(v0, v1, nonfinite);
+    sp_acc_clear(a);
+    return sp_pick(r, round_mode);
+}
+
+// which lanes of the wave hold which non-finite flag; of(group): the union over the lanes of a mask
+struct NonFiniteLanes {
+    unsigned long long pinf, ninf, nan;
+    __device__ __forceinline__ explicit NonFiniteLanes(unsigned flags)
+        : pinf(__ballot((flags & FLAG_PINF) != 0)), ninf(__ballot((flags & FLAG_NINF) != 0)),
+          nan(__ballot((flags & FLAG_NAN) != 0))
+    {
+    }
+    __device__ __forceinline__ unsigned of(unsigned long long group) const
+    {
+        return ((pinf & group) ? FLAG_PINF : 0u) | ((ninf & group) ? FLAG_NINF : 0u) | ((nan & group) ? FLAG_NAN : 0u);
+    }
+};
 
 // beta * y under ExGEMV's rules (beta = 0 ignores y, 1 adds it exactly, else the error-free product), absorbed into a
 // lane's expansion; `take` says whether this lane carries the term (y[at] is read by no other)

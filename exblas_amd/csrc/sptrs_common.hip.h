@@ -1,7 +1,7 @@
 // sptrs_common.hip.h -- what the two sparse triangular solves (sptrsv.hip: ExSpTRSV, sptrsm.hip: ExSpTRSM) share: the
 // workspace header, the mailbox conventions (a reserved "not posted" pattern, the canonical NaN, agent-scope relaxed
-// atomic store and load, a wave-uniform poll loop with a light sleep and the 2 s watchdog), the classification of one
-// stored entry and the counters.
+// atomic store and load, a wave-uniform poll loop with a light sleep and the 2 s watchdog), the preset kernel, the ticket
+// take, the classification of one stored entry, the counters and their flush, and the decoding of uplo / diag.
 #pragma once
 #include "spmv_common.hip.h"
 
@@ -86,35 +86,50 @@ __device__ __forceinline__ int st_classify(long long col, long long k, int m, in
     return 1;
 }
 
-// The same rule from the arrays, as ExSpTRSV's kernels were built with it (kept in this form: their code does not
-// change): the value is loaded for dependencies only.
-template <class I>
-__device__ __forceinline__ int st_entry(long long k, const I *__restrict__ ci, const double *__restrict__ val, int m, int rev,
-                                        long long row, long long pos, long long pos0, double &a, long long &c, int &ds,
-                                        long long &kdiag, unsigned &flags, StCounters &cn)
+// the next work item of a persistent wave (wave-uniform)
+__device__ __forceinline__ long long st_take_ticket(long long *hdr)
 {
-    const long long col = (long long)ld_nt(ci + k);
-    if ((unsigned long long)col >= (unsigned long long)m) {
-        flags |= FLAG_NAN | SP_SPILL;
-        return 0;
+    long long t = 0;
+    if ((threadIdx.x & 63) == 0) t = (long long)atomicAdd((unsigned long long *)&hdr[ST_TICKET], 1ull);
+    return lane_bcast(t, 0);
+}
+
+// a wave's counters, summed over its lanes, into hdr[ST_INFO ..]
+__device__ __forceinline__ void st_flush_counters(const StCounters &cn, long long *hdr)
+{
+    long long tot[4] = {cn.reg, cn.fb, cn.nodiag, cn.skipped};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) tot[i] += __shfl_down(tot[i], o, 64);
+        if ((threadIdx.x & 63) == 0 && tot[i]) atomicAdd((unsigned long long *)&hdr[ST_INFO + i], (unsigned long long)tot[i]);
     }
-    if (col == row) {
-        kdiag = min(kdiag, k);
-        ++cn.skipped;   // (the leader takes the divisor's one back)
-        return 0;
-    }
-    const long long cpos = rev ? (long long)m - 1 - col : col;
-    if (cpos > pos) {
-        ++cn.skipped;
-        return 0;
-    }
-    a = ld_nt(val + k);
-    c = col;
-    if (cpos >= pos0) {
-        ds = (int)(cpos - pos0);
-        return 2;
-    }
-    return 1;
+}
+
+// ticket := 0, mailbox of n values := "not posted" (a kernel, not memset nodes: one node kind in a captured graph); with
+// `first` the whole header is cleared: the counters and the watchdog flag, which add up over the launches that follow
+static __global__ void __launch_bounds__(SP_BLOCK) k_sptrs_preset(long long n, int first, long long *__restrict__ hdr,
+                                                                  long long *__restrict__ xq)
+{
+    const long long i0 = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
+    if (first ? i0 < ST_HDR_BYTES / 8 : i0 == ST_TICKET) hdr[i0] = 0;
+    for (long long i = i0; i < n; i += (long long)gridDim.x * SP_BLOCK) xq[i] = ST_EMPTY;
+}
+
+static inline hipError_t st_preset(const Ctx &c, long long n, int first, long long *hdr, double *xq, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_sptrs_preset, dim3((int)min((long long)c.num_cu * 8, (n + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK),
+                       0, st, n, first, hdr, (long long *)xq);
+    return hipGetLastError();
+}
+
+// 'U' solves in reverse row order; diag 'U' divides by nothing
+struct StOrient {
+    int rev, unit;
+};
+static inline StOrient st_orient(char uplo, char diag)
+{
+    return {(uplo == 'U' || uplo == 'u') ? 1 : 0, (diag == 'U' || diag == 'u') ? 1 : 0};
 }
 
 // ticks of wall_clock64() in the watchdog's 2 s

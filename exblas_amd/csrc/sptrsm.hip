@@ -167,15 +167,7 @@ __device__ __forceinline__ void tm_row(const TmArgs &A, bool count, long long po
             if constexpr (PLAIN) {
                 ps += __shfl_down(ps, st, 64);
             } else {
-                double q[SP_N];
-#pragma unroll
-                for (int i = 0; i < SP_N; ++i) {
-                    const double t = __shfl_down(f[i], st, 64);
-                    q[i] = take ? t : 0.0;
-                }
-                const unsigned fo = __shfl_down(flags, st, 64);
-                if (take) flags |= fo;
-                fpe_cascade<SP_N, true, SP_N>(f, q, 0, sink);
+                sp_cascade_step(f, flags, st, take, sink);
             }
         }
         kdiag = lane_bcast(kdiag, 0);
@@ -256,39 +248,19 @@ __device__ __forceinline__ void tm_row(const TmArgs &A, bool count, long long po
             }
             double *xj = x + row * A.ldx + jj;
             if (lane == 0) lds_add<1>(acc, xs[r * 64 + l], fl);   // b: the row's slot holds it until the row is solved
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const unsigned fu = (__ballot((fl & FLAG_PINF) != 0) ? FLAG_PINF : 0u) |
-                                (__ballot((fl & FLAG_NINF) != 0) ? FLAG_NINF : 0u) |
-                                (__ballot((fl & FLAG_NAN) != 0) ? FLAG_NAN : 0u);
-            const long long v0 = acc[lane], v1 = lane < NL - 64 ? acc[64 + lane] : 0;
-            const WaveFinish wf = finish_wave(v0, v1, fu);
-            double v = A.round_mode ? wf.rf : __longlong_as_double((long long)wf.ex);
+            sp_wave_sync();
+            double v = sp_acc_round(acc, NonFiniteLanes(fl).of(~0ull), A.round_mode);
             if (!A.unit) v = v / d;
             if (lane == 0) {
                 st_post(xq + row * (long long)A.kp + jj, v);
                 *xj = v;
                 xs[r * 64 + l] = v;
             }
-            acc[lane] = 0;
-            if (lane < NL - 64) acc[64 + lane] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            sp_wave_sync();
         }
     }
     // the row is in LDS before the next row of the item reads it
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// ticket := 0, mailbox := "not posted" (a kernel, not memset nodes: one node kind in a captured graph); the first panel
-// of a call also clears the counters and the watchdog flag, which then add up over the panels
-__global__ void __launch_bounds__(SP_BLOCK) k_sptrsm_preset(long long n, int first, long long *__restrict__ hdr,
-                                                            long long *__restrict__ xq)
-{
-    const long long i0 = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
-    if (first ? i0 < ST_HDR_BYTES / 8 : i0 == ST_TICKET) hdr[i0] = 0;
-    for (long long i = i0; i < n; i += (long long)gridDim.x * SP_BLOCK) xq[i] = ST_EMPTY;
+    sp_wave_sync();
 }
 
 template <bool WIDE, bool PLAIN, class I>
@@ -302,15 +274,12 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsm(TmArgs A, int R, const I *_
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if constexpr (!PLAIN) {
         for (int t = lane; t < NL; t += 64) acc[w][t] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        sp_wave_sync();
     }
     const long long nitems = (((long long)A.m + R - 1) / R) * A.tiles;
     StCounters cn;
     for (;;) {
-        long long t = 0;
-        if (lane == 0) t = (long long)atomicAdd((unsigned long long *)&hdr[ST_TICKET], 1ull);
-        t = lane_bcast(t, 0);
+        const long long t = st_take_ticket(hdr);
         if (t >= nitems) break;
         const long long pos0 = (t / A.tiles) * R;
         const int tile = (int)(t % A.tiles);
@@ -328,8 +297,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsm(TmArgs A, int R, const I *_
                 sci[w][e] = (long long)ld_nt(ci + P0 + e);
                 sval[w][e] = ld_nt(val + P0 + e);
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            sp_wave_sync();
         }
         // b of the item's rows, side by side, into the slots that take the solved rows later
         {
@@ -342,8 +310,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsm(TmArgs A, int R, const I *_
                     if (r < nrows) xs[w][r * 64 + (lane & (G - 1))] = x[row * A.ldx + j];
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            __builtin_amdgcn_wave_barrier();
+            sp_wave_sync();
         }
         for (int r = 0; r < nrows; ++r) {
             const int at = A.rev ? nrows - 1 - r : r;
@@ -351,13 +318,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsm(TmArgs A, int R, const I *_
             tm_row<WIDE, PLAIN>(A, count, pos0, r, tile, p0, max(p0, lane_bcast(bnd, at + 1)), E, x, hdr, xq, acc[w], xs[w], cn);
         }
     }
-    long long tot[4] = {cn.reg, cn.fb, cn.nodiag, cn.skipped};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tot[i] += __shfl_down(tot[i], o, 64);
-        if (lane == 0 && tot[i]) atomicAdd((unsigned long long *)&hdr[ST_INFO + i], (unsigned long long)tot[i]);
-    }
+    st_flush_counters(cn, hdr);
 }
 
 }  // namespace
@@ -389,8 +350,9 @@ hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int ind
     const int R = path == 2 ? 1 : TM_R;
     TmArgs A;
     A.m = m;
-    A.rev = (uplo == 'U' || uplo == 'u') ? 1 : 0;
-    A.unit = (diag == 'U' || diag == 'u') ? 1 : 0;
+    const StOrient o = st_orient(uplo, diag);
+    A.rev = o.rev;
+    A.unit = o.unit;
     A.force_fb = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
     A.round_mode = fpe == 1 ? 0 : round_mode;
     A.ldx = ldx;
@@ -405,9 +367,7 @@ hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int ind
             A.tiles = (A.kp + (1 << A.lg) - 1) >> A.lg;
             A.count = j0 == 0;
             const long long n = (long long)m * A.kp, nitems = (((long long)m + R - 1) / R) * A.tiles;
-            hipLaunchKernelGGL(k_sptrsm_preset, dim3((int)min((long long)c.num_cu * 8, (n + SP_BLOCK - 1) / SP_BLOCK)),
-                               dim3(SP_BLOCK), 0, st, n, j0 == 0 ? 1 : 0, hdr, (long long *)xq);
-            if (hipError_t le = hipGetLastError(); le != hipSuccess) return le;
+            if (hipError_t le = st_preset(c, n, j0 == 0 ? 1 : 0, hdr, xq, st); le != hipSuccess) return le;
             c.sptrsm_info_dev = hdr;
             const int grid = (int)min((long long)c.num_cu * 8, (nitems + SP_WAVES - 1) / SP_WAVES);
             if (A.lg == 6)

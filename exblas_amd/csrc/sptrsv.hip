@@ -8,7 +8,8 @@
 // being looked at; a column outside [0, m) makes x_i NaN.  Every path sums the same multiset of doubles exactly, so the
 // bits depend on the data and (uplo, diag, rounding mode) only.
 //
-// Structure: a preset kernel (header zero, mailbox empty) and ONE solve kernel, no host synchronisation, no analysis phase.
+// Structure: the preset kernel (sptrs_common.hip.h: header zero, mailbox empty) and ONE solve kernel, no host
+// synchronisation, no analysis phase.
 //   * Work items are groups of R consecutive rows in substitution order (R = 8; R = 1 on path 2), handed out by an
 //     atomic ticket that a wave takes when it is ready to work on the item (persistent waves, no workgroup barrier).
 //   * Solved values travel through a mailbox of m doubles preset to a reserved NaN pattern (the value is its own ready
@@ -86,7 +87,9 @@ __device__ __forceinline__ void st_rows(long long pos0, int nrows, int m, const 
             want[j] = false;
             if (k[j] < p1) {
                 int ds = 0;
-                const int kind = st_entry(k[j], ci, val, m, rev, row, pos, pos0, a[j], at[j], ds, kdiag, flags, cn);
+                at[j] = (long long)ld_nt(ci + k[j]);
+                const int kind = st_classify(at[j], k[j], m, rev, row, pos, pos0, ds, kdiag, flags, cn);
+                if (kind) a[j] = ld_nt(val + k[j]);   // the value is looked at for dependencies only
                 want[j] = kind == 1;
                 if constexpr (G == 8) {
                     if (kind == 2) {
@@ -160,30 +163,15 @@ __device__ __forceinline__ void st_rows(long long pos0, int nrows, int m, const 
             }
         } else {
 #pragma unroll
-            for (int s = 1; s < G; s <<= 1) {
-                const bool take = (sub & (2 * s - 1)) == 0;
-                double q[SP_N];
-#pragma unroll
-                for (int i = 0; i < SP_N; ++i) {
-                    const double t = __shfl_down(f[i], s, 64);
-                    q[i] = take ? t : 0.0;
-                }
-                const unsigned fo = __shfl_down(flags, s, 64);
-                if (take) flags |= fo;
-                fpe_cascade<SP_N, true, SP_N>(f, q, 0, sink);
-            }
+            for (int s = 1; s < G; s <<= 1) sp_cascade_step(f, flags, s, (sub & (2 * s - 1)) == 0, sink);
             bool fb = false;
             if (leader) {
                 double r;
-                if (!force_fb && flags == 0 && spmv_round_fast<SP_N>(f, r)) {
+                fb = !sp_certify_or_spill(f, flags, force_fb, acc[slot], r);
+                if (!fb) {
                     const double v = unit ? r : r / d;
                     st_post(xq + row, v);
                     x[row] = v;
-                } else {
-                    fb = true;
-#pragma unroll
-                    for (int i = 0; i < SP_N; ++i)
-                        if (f[i] != 0.0) lds_add<1>(acc[slot], f[i], flags);
                 }
             }
             const unsigned long long regm = __ballot(leader && !fb);
@@ -191,27 +179,20 @@ __device__ __forceinline__ void st_rows(long long pos0, int nrows, int m, const 
             unsigned long long fbm = __ballot(fb);
             if (lane == 0) cn.fb += __popcll(fbm);
             if (fbm) {
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                __builtin_amdgcn_wave_barrier();
+                sp_wave_sync();
                 while (fbm) {   // wave-uniform: every lane runs the finish of each falling-back row
                     const int l = __builtin_ctzll(fbm), sl = l / G;
                     fbm &= fbm - 1ull;
                     const unsigned fl = (unsigned)__shfl((int)flags, l, 64) & FLAG_NONFINITE;
                     const long long r_row = __shfl(row, l, 64);
                     const double r_d = __shfl(d, l, 64);
-                    long long *a = acc[sl];
-                    const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
-                    const WaveFinish r = finish_wave(v0, v1, fl);
+                    double v = sp_acc_round(acc[sl], fl, round_mode);
                     if (lane == 0) {
-                        double v = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
                         if (!unit) v = v / r_d;
                         st_post(xq + r_row, v);
                         x[r_row] = v;
                     }
-                    a[lane] = 0;
-                    if (lane < NL - 64) a[64 + lane] = 0;
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
+                    sp_wave_sync();
                 }
             }
         }
@@ -233,41 +214,17 @@ __device__ __forceinline__ void st_rows(long long pos0, int nrows, int m, const 
                 v = __shfl(ps, L, 64);
             } else {
 #pragma unroll
-                for (int st = 1; st < G; st <<= 1) {
-                    const bool take = mine && (sub & (2 * st - 1)) == 0;
-                    double q[SP_N];
-#pragma unroll
-                    for (int i = 0; i < SP_N; ++i) {
-                        const double t = __shfl_down(f[i], st, 64);
-                        q[i] = take ? t : 0.0;
-                    }
-                    const unsigned fo = __shfl_down(flags, st, 64);
-                    if (take) flags |= fo;
-                    if (__any(any_nonzero<SP_N>(q))) fpe_cascade<SP_N, true, SP_N>(f, q, 0, sink);
-                }
+                for (int st = 1; st < G; st <<= 1)
+                    sp_cascade_step<true>(f, flags, st, mine && (sub & (2 * st - 1)) == 0, sink);
                 bool fb = false;
                 double r = 0.0;
-                if (lane == L) {
-                    if (!(!force_fb && flags == 0 && spmv_round_fast<SP_N>(f, r))) {
-                        fb = true;
-#pragma unroll
-                        for (int i = 0; i < SP_N; ++i)
-                            if (f[i] != 0.0) lds_add<1>(acc[slot], f[i], flags);
-                    }
-                }
+                if (lane == L) fb = !sp_certify_or_spill(f, flags, force_fb, acc[slot], r);
                 if (__ballot(fb)) {
                     if (lane == 0) ++cn.fb;
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
+                    sp_wave_sync();
                     const unsigned fl = (unsigned)__shfl((int)flags, L, 64) & FLAG_NONFINITE;
-                    long long *a = acc[s];
-                    const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
-                    const WaveFinish w = finish_wave(v0, v1, fl);
-                    v = round_mode ? w.rf : __longlong_as_double((long long)w.ex);
-                    a[lane] = 0;
-                    if (lane < NL - 64) a[64 + lane] = 0;
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
+                    v = sp_acc_round(acc[s], fl, round_mode);
+                    sp_wave_sync();
                 } else {
                     if (lane == 0) ++cn.reg;
                     v = __shfl(r, L, 64);
@@ -301,14 +258,6 @@ __device__ __forceinline__ void st_rows(long long pos0, int nrows, int m, const 
     }
 }
 
-// header := 0, mailbox := "not posted" (a kernel, not memset nodes: one node kind in a captured graph)
-__global__ void __launch_bounds__(SP_BLOCK) k_sptrsv_preset(int m, long long *__restrict__ hdr, long long *__restrict__ xq)
-{
-    const long long i0 = (long long)blockIdx.x * SP_BLOCK + threadIdx.x;
-    if (i0 < ST_HDR_BYTES / 8) hdr[i0] = 0;
-    for (long long i = i0; i < m; i += (long long)gridDim.x * SP_BLOCK) xq[i] = ST_EMPTY;
-}
-
 template <bool PLAIN, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_sptrsv(int m, const I *__restrict__ rp, const I *__restrict__ ci,
                                                     const double *__restrict__ val, double *x, int rev, int unit, int R,
@@ -322,9 +271,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsv(int m, const I *__restrict_
     const long long nitems = ((long long)m + R - 1) / R;
     StCounters cn;
     for (;;) {
-        long long t = 0;
-        if (lane == 0) t = (long long)atomicAdd((unsigned long long *)&hdr[ST_TICKET], 1ull);
-        t = lane_bcast(t, 0);
+        const long long t = st_take_ticket(hdr);
         if (t >= nitems) break;
         const long long pos0 = t * R;
         const int nrows = (int)min((long long)R, (long long)m - pos0);
@@ -344,13 +291,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsv(int m, const I *__restrict_
             st_rows<8, PLAIN>(pos0, nrows, m, rp, ci, val, x, rev, unit, force_fb, round_mode, limit, hdr, xq, acc[w], cn);
         }
     }
-    long long tot[4] = {cn.reg, cn.fb, cn.nodiag, cn.skipped};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) tot[i] += __shfl_down(tot[i], o, 64);
-        if (lane == 0 && tot[i]) atomicAdd((unsigned long long *)&hdr[ST_INFO + i], (unsigned long long)tot[i]);
-    }
+    st_flush_counters(cn, hdr);
 }
 
 }  // namespace
@@ -361,16 +302,14 @@ hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
     c.sptrsv_info_dev = nullptr;
     if (m == 0) return hipSuccess;
-    const int rev = (uplo == 'U' || uplo == 'u') ? 1 : 0, unit = (diag == 'U' || diag == 'u') ? 1 : 0;
+    const StOrient o = st_orient(uplo, diag);
     // workspace: the header, then the mailbox of m doubles
     hipError_t e;
     char *base = (char *)workspace(c, ST_HDR_BYTES + (size_t)m * sizeof(double), st, &e);
     if (!base) return e;
     long long *hdr = (long long *)base;
     double *xq = (double *)(base + ST_HDR_BYTES);
-    hipLaunchKernelGGL(k_sptrsv_preset, dim3((int)min((long long)c.num_cu * 8, ((long long)m + SP_BLOCK - 1) / SP_BLOCK)),
-                       dim3(SP_BLOCK), 0, st, m, hdr, (long long *)xq);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = st_preset(c, m, 1, hdr, xq, st)) != hipSuccess) return e;
     c.sptrsv_info_dev = hdr;
     const int R = c.sptrsv_path == 2 ? 1 : ST_R;
     const int force_fb = (fpe == 0 || c.sptrsv_path == 1 || round_mode) ? 1 : 0;
@@ -379,7 +318,7 @@ hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits
     return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
         constexpr bool PLAIN = decltype(plain)::value;
         using I = std::remove_cv_t<std::remove_pointer_t<decltype(rp)>>;
-        hipLaunchKernelGGL((k_sptrsv<PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, rp, ci, val, x, rev, unit, R,
+        hipLaunchKernelGGL((k_sptrsv<PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, rp, ci, val, x, o.rev, o.unit, R,
                            PLAIN ? 0 : force_fb, PLAIN ? 0 : round_mode, limit, hdr, xq);
         return hipGetLastError();
     });

@@ -59,8 +59,9 @@ def test_exspmm_dev_rejects_bad_arguments(bad):
         A = torch.zeros(4, 5, dtype=torch.float64)
     if A is None:
         A = (crow, col, val, shape)
-    with pytest.raises((TypeError, ValueError)):   # before any GPU check: RuntimeError would mean it came too late
+    with pytest.raises((TypeError, ValueError)) as err:   # before any GPU check: RuntimeError would mean it came too late
         exblas_amd.exspmm_dev(A, x, 1.0, 0.0, y)
+    assert str(err.value).startswith("exspmm:")   # the routine that was called, whichever helper refused
 
 
 def test_one_dimensional_x_points_to_exspmv():

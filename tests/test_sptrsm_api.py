@@ -94,12 +94,14 @@ def test_exsptrsm_dev_rejects_bad_arguments(bad):
         A = (crow, col, val, shape)
     with pytest.raises((TypeError, ValueError)) as err:
         exblas_amd.exsptrsm_dev(A, x, uplo, diag)
+    assert str(err.value).startswith("exsptrsm:")               # the routine that was called, whichever helper refused
     if bad == "x_1d":
         assert "exsptrsv_dev" in str(err.value)                  # one vector: the message names the routine for it
     ctx = object.__new__(exblas_amd.Context)     # the method validates before it touches the handle
     ctx.handle = None
-    with pytest.raises((TypeError, ValueError)):
+    with pytest.raises((TypeError, ValueError)) as err:
         exblas_amd.Context.exsptrsm(ctx, A, x, uplo, diag)
+    assert str(err.value).startswith("exsptrsm:")
 
 
 def test_an_overlapping_block_with_stride_one_less_than_k_is_refused():

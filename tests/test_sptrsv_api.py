@@ -78,12 +78,14 @@ def test_exsptrsv_dev_rejects_bad_arguments(bad):
         x = np.ones(4)
     if A is None:
         A = (crow, col, val, shape)
-    with pytest.raises((TypeError, ValueError)):
+    with pytest.raises((TypeError, ValueError)) as err:
         exblas_amd.exsptrsv_dev(A, x, uplo, diag)
+    assert str(err.value).startswith("exsptrsv:")   # the routine that was called, whichever helper refused
     ctx = object.__new__(exblas_amd.Context)     # the method validates before it touches the handle
     ctx.handle = None
-    with pytest.raises((TypeError, ValueError)):
+    with pytest.raises((TypeError, ValueError)) as err:
         exblas_amd.Context.exsptrsv(ctx, A, x, uplo, diag)
+    assert str(err.value).startswith("exsptrsv:")
 
 
 def test_host_exsptrsv_rejects_bad_arguments():
