@@ -191,7 +191,9 @@ int exblas_set_accumulator_slot(int slot);
 int exblas_set_launch_events(void *ev_start, void *ev_stop);
 /* Sum `nsets` digit sets (EXBLAS_SET_WORDS int64 each = words [48,120) of a record, e.g. the
  * all-reduced payloads of several GPUs), carry-propagate once and round: the "single global
- * carry-propagated normalise".  d_out may alias d_digit_sets - EXBLAS_OUT_DIGITS (in-place).
+ * carry-propagated normalise".  The sets need not be normalised: any words below 2^63 in magnitude are
+ * accepted (it is the kernel that reads the raw group accumulators) as long as the sum of the top words
+ * does and the total fits the 68 digits.  d_out may alias d_digit_sets - EXBLAS_OUT_DIGITS (in-place).
  * Plays the role of MPI_Reduce + Round in cpu:ExSUM.cpp:142-156. flags_or: OR of the ranks' flags. */
 int exblas_finalize_dev(const int64_t *d_digit_sets, int nsets, uint32_t flags_or, void *stream,
                         int64_t *d_out);
