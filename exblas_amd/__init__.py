@@ -50,6 +50,7 @@ C_ABI_SYMBOLS = [
     "exblas_last_sptrsv_info",
     "exblas_exsptrsm_csr_dev", "exblas_exsptrsm_csr_ctx", "exblas_exsptrsm_csr", "exblas_set_sptrsm_path",
     "exblas_last_sptrsm_info",
+    "exblas_exbdot_dev", "exblas_exbdot_ctx", "exblas_exbdot", "exblas_set_bdot_path",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -193,6 +194,11 @@ def load_library():
     L.exblas_set_sptrsm_path.argtypes = [i32]
     L.exblas_set_sptrsm_path.restype = None
     L.exblas_last_sptrsm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exbdot_dev.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32, vp]
+    L.exblas_exbdot_ctx.argtypes = [vp] + L.exblas_exbdot_dev.argtypes
+    L.exblas_exbdot.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32]
+    L.exblas_set_bdot_path.argtypes = [i32]
+    L.exblas_set_bdot_path.restype = None
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -617,6 +623,72 @@ def last_spmm_info():
     return _last_info("spmm")
 
 
+def _bdot_mode(mode):
+    if not isinstance(mode, str) or mode not in ("G", "g", "D", "d"):
+        raise ValueError(f"exbdot: mode must be 'G' (Gram) or 'D' (diagonal), not {mode!r}")
+    return mode.upper()
+
+
+def _bdot_sizes(mode, n, p, q, fpe):
+    if mode == "D" and p != q:
+        raise ValueError(f"exbdot: mode 'D' needs as many columns in X as in Y, not {p} and {q}")
+    if n > 0x7fffffff:
+        raise ValueError(f"exbdot: n = {n} rows exceed INT_MAX")
+    if int(fpe) < 0:
+        raise ValueError("exbdot: fpe must be >= 0")
+
+
+def _bdot_args(X, Y, mode, out, fpe, early_exit):
+    """Validates a device ExBDOT call before anything is launched; returns (out, the C arguments up to the stream)."""
+    torch = _torch()
+    mode = _bdot_mode(mode)
+    if getattr(X, "ndim", 2) == 1:
+        raise ValueError("exbdot: X must be 2-D (n x p); for two vectors use exdot_dev")
+    if Y is None:
+        Y = X
+    for name, t in (("X", X), ("Y", Y)):
+        _dense_dev("exbdot", name, t, 2)
+        if t.shape[0] > 0 and ((t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+            raise ValueError(f"exbdot: {name} must be row-major with stride(1) == 1 and stride(0) >= its column count "
+                             "(a block is never copied)")
+    if X.shape[0] != Y.shape[0]:
+        raise ValueError(f"exbdot: X has {X.shape[0]} rows and Y has {Y.shape[0]}")
+    n, p, q = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1])
+    _bdot_sizes(mode, n, p, q, fpe)
+    shape = (p, q) if mode == "G" else (p,)
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != shape:
+            raise ValueError(f"exbdot: out must be a float64 tensor of shape {shape}")
+        if mode == "G" and p > 0 and ((q > 1 and out.stride(1) != 1) or (p > 1 and out.stride(0) < q)):
+            raise ValueError("exbdot: out needs stride(1) == 1 and stride(0) >= q")
+        if mode == "D" and p > 1 and out.stride(0) != 1:
+            raise ValueError("exbdot: out must be contiguous in mode 'D'")
+    _on_gpu("exbdot", X=X, Y=Y, **({} if out is None else {"out": out}))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=X.device)
+    ldc = _ld(out, q) if mode == "G" else 1
+    return out, (mode.encode(), n, p, q, _ptr(X), _ld(X, p), _ptr(Y), _ld(Y, q), _ptr(out), ldc, int(fpe),
+                 int(bool(early_exit)))
+
+
+def exbdot_dev(X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
+    """ExBDOT: exact, reproducible inner products of the columns of two row-major blocks, stream-ordered on the current
+    stream, both blocks read once.  mode 'G': out[i, j] = Round(sum_r X[r, i] Y[r, j]) (p x q); mode 'D' (p == q):
+    out[j] = Round(sum_r X[r, j] Y[r, j]).  Every output is bit for bit what exdot_dev gives for the two columns.  X and
+    Y are 2-D float64 tensors with stride(1) == 1 and stride(0) >= their column count (a view [:, :k] of a wider block is
+    fine; anything else is refused, not copied) and equal row counts; Y=None means Y = X.  `out` is allocated when None,
+    otherwise checked; it is returned."""
+    out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
+    _check(load_library().exblas_exbdot_dev(*args, _stream_ptr(_torch())), "exbdot_dev")
+    return out
+
+
+def set_bdot_path(mode):
+    """Test hook: 0 automatic, 1 the smallest row slab per workgroup, 2 column panels and output tiles of width 4.
+    Same bits on every path."""
+    load_library().exblas_set_bdot_path(int(mode))
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Methods mirror the ``*_dev``
@@ -714,6 +786,11 @@ class Context:
         Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
         _check(load_library().exblas_exspmm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmm_ctx")
         return Y
+
+    def exbdot(self, X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
+        out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
+        _check(load_library().exblas_exbdot_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_ctx")
+        return out
 
     def workspace_bytes(self):
         return load_library().exblas_workspace_bytes_ctx(self.handle)
@@ -909,6 +986,24 @@ def exspmm(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
     _check(load_library().exblas_exspmm_csr(m, n, k, bits, _hptr(crow), _hptr(col), _hptr(val), float(alpha), _hptr(X), k,
                                             float(beta), _hptr(Y), k, int(fpe), int(bool(early_exit))), "exspmm")
     return Y
+
+
+def exbdot(X, Y=None, mode="G", fpe=8, early_exit=True):
+    """ExBDOT on host arrays: X (n x p) and Y (n x q, None: Y = X) float64; returns a new p x q array (mode 'G') or a new
+    array of p entries (mode 'D', p == q)."""
+    mode = _bdot_mode(mode)
+    hint = " (n x p; for two vectors use exdot)"
+    X = np.ascontiguousarray(_dense_host("exbdot", "X", X, 2, hint))
+    Y = X if Y is None else np.ascontiguousarray(_dense_host("exbdot", "Y", Y, 2, hint))
+    if X.shape[0] != Y.shape[0]:
+        raise ValueError(f"exbdot: X has {X.shape[0]} rows and Y has {Y.shape[0]}")
+    n, p, q = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1])
+    _bdot_sizes(mode, n, p, q, fpe)
+    out = np.zeros((p, q) if mode == "G" else (p,))
+    _require_gpu()
+    _check(load_library().exblas_exbdot(mode.encode(), n, p, q, _hptr(X), max(p, 1), _hptr(Y), max(q, 1), _hptr(out),
+                                        max(q, 1), int(fpe), int(bool(early_exit))), "exbdot")
+    return out
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

@@ -98,6 +98,7 @@ static void init_ctx(Ctx &c, int device, int layer)
         c.spmm_path = z.spmm_path;
         c.sptrsv_path = z.sptrsv_path;
         c.sptrsm_path = z.sptrsm_path;
+        c.bdot_path = z.bdot_path;
         c.gemm_max_slices = z.gemm_max_slices;
         c.gemm_max_moduli = z.gemm_max_moduli;
     }
@@ -484,6 +485,8 @@ void exblas_set_sptrsv_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsv_pa
 
 void exblas_set_sptrsm_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsm_path = sparse_path(mode); }); }
 
+void exblas_set_bdot_path(int mode) { for_each_layer([&](Ctx &c) { c.bdot_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
+
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
 int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&Ctx::sptrsv_info_dev, true, out4); }
@@ -565,6 +568,30 @@ static int exspmm_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_
 }
 
 static bool one_of(char ch, const char *set) { return ch != 0 && strchr(set, ch) != nullptr; }
+
+// The argument checks of ExBDOT, on host or device pointers alike.  *empty: nothing to compute (p == 0 or q == 0), which
+// is decided before the pointers are looked at.
+static int bdot_check_args(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                           const double *c, int64_t ldc, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(mode, "GgDd") || n < 0 || n > 0x7fffffffll || p < 0 || q < 0 || fpe < 0) return (int)hipErrorInvalidValue;
+    const bool diag = mode == 'D' || mode == 'd';
+    if (ldx < p || ldy < q || (diag ? p != q : ldc < q)) return (int)hipErrorInvalidValue;
+    *empty = p == 0 || q == 0;
+    if (!*empty && (!c || (n > 0 && (!x || !y)))) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int exbdot_on(Ctx &c, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
+                     int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;
+    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
+    if (rc || empty) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    return (int)exbdot_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, round_mode(), st);
+}
 
 static int exsptrsv_on(Ctx &c, char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                        const double *d_val, double *d_x, int fpe, int early_exit, hipStream_t st)
@@ -677,6 +704,15 @@ int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row
 {
     return exspmm_on(ctx(-1), m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
                      early_exit, (hipStream_t)stream);
+}
+
+int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                      double *d_c, int64_t ldc, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // refused, or nothing to do, before a context (and with it a device) is needed
+    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
+    if (rc || empty) return rc;
+    return exbdot_on(ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
 }
 
 int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
@@ -846,6 +882,13 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, 
     EXB_HANDLE(h);
     return exspmm_on(*cp, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
                      early_exit, (hipStream_t)stream);
+}
+
+int exblas_exbdot_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
+                      const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return exbdot_on(*cp, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
 }
 
 int exblas_exsptrsv_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
@@ -1407,6 +1450,37 @@ int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, cons
     long long h[8];
     if (int e = sparse_header(c.sptrsm_info_dev, h)) return e;
     return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
+}
+
+// whole rows travel, padding included (the last row only up to its last entry); C comes back the same way, so that its
+// padding returns as it went
+int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                  double *cm, int64_t ldc, int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = bdot_check_args(mode, n, p, q, x, ldx, y, ldy, cm, ldc, fpe, &empty);
+    if (bad || empty) return bad;
+    const bool diag = mode == 'D' || mode == 'd';
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)p : 0;
+    const size_t yspan = n > 0 ? (size_t)(n - 1) * (size_t)ldy + (size_t)q : 0;
+    const size_t cspan = diag ? (size_t)p : (size_t)(p - 1) * (size_t)ldc + (size_t)q;
+    double *d_x, *d_y, *d_c;
+    {
+        std::lock_guard<std::mutex> lk(c.mu);
+        d_x = (double *)stage_buf(c, 0, xspan * 8 + 8);
+        d_y = (double *)stage_buf(c, 1, yspan * 8 + 8);
+        d_c = (double *)stage_buf(c, 2, cspan * 8);
+        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d_x, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
+        if (yspan > 0) EXB_CHECK(hipMemcpyAsync(d_y, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
+        EXB_CHECK(hipMemcpyAsync(d_c, cm, cspan * 8, hipMemcpyHostToDevice, c.stream));
+    }
+    const int rc = exbdot_on(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, c.stream);
+    if (rc) die("exblas_exbdot", (hipError_t)rc, __FILE__, __LINE__);
+    EXB_CHECK(hipMemcpyAsync(cm, d_c, cspan * 8, hipMemcpyDeviceToHost, c.stream));
+    EXB_CHECK(hipStreamSynchronize(c.stream));
+    return 0;
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

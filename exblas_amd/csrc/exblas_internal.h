@@ -49,6 +49,8 @@ struct Ctx {
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
+    int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
+                             // of width 4
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -168,6 +170,11 @@ hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits
 hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *row_ptr,
                              const void *col_idx, const double *val, double *x, long long ldx, int fpe, int early_exit,
                              int round_mode, hipStream_t st);
+
+// bdot.hip
+hipError_t exbdot_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                           long long ldy, double *out, long long ldc, int fpe, int early_exit, int round_mode,
+                           hipStream_t st);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

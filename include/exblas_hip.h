@@ -137,7 +137,8 @@ int exblas_reserve_workspace(size_t bytes);
  * outputs), L = min(m, floor(32 MiB / (576 k))) accumulator slots for split rows: at most 32 MiB whatever k is; rows
  * past L run whole.  ExSpTRSV: 256 + 8 m bytes (the header and the mailbox of m doubles).  ExSpTRSM: 256 + 8 m min(k, P)
  * bytes (the header and the mailbox of one column panel), P = max(64, 64 floor(EXBLAS_SPTRSM_MAILBOX_BYTES / (8 m) / 64))
- * columns per panel: at most 64 MiB (EXBLAS_SPTRSM_MAILBOX_BYTES) unless 512 m exceeds it. */
+ * columns per panel: at most 64 MiB (EXBLAS_SPTRSM_MAILBOX_BYTES) unless 512 m exceeds it.  ExBDOT:
+ * EXBLAS_BDOT_WORKSPACE_BYTES (2.25 MiB: 4096 accumulator sets of 576 bytes) whatever n, p and q are. */
 size_t exblas_workspace_bytes(void);
 /* Frees the workspace blocks that later, larger calls replaced.  Synchronises the device; only call it when no graph
  * captured before the growth will be replayed again. */
@@ -340,6 +341,41 @@ void exblas_set_sptrsm_path(int mode);
  * the device; valid until the next call that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as
  * exblas_last_sptrsv_info does. */
 int exblas_last_sptrsm_info(int64_t *out4);
+/* ExBDOT: exact, reproducible inner products of two dense ROW-MAJOR blocks on device pointers, both read once.  X is
+ * n x p with leading dimension ldx >= p, Y is n x q with ldy >= q.
+ *   mode 'G' (Gram):      C[i * ldc + j] = Round( sum_r X[r, i] * Y[r, j] ),  C p x q row-major, ldc >= q
+ *   mode 'D' (diagonal):  c[j] = Round( sum_r X[r, j] * Y[r, j] ),  p == q, c a contiguous vector of p doubles (ldc ignored)
+ * The sum is exact and rounded once: to nearest even, or by the reference rule under exblas_set_round_mode(1).  Every
+ * output is, bit for bit, the `exact` word (rounding mode 0) or the `refmode` word (mode 1) of the record that
+ * exblas_exdot_dev(X + i, ldx, Y + j, ldy, n, ...) returns, whenever that record carries none of the product-domain flag
+ * bits 3..6: the domain is ExGEMV's product domain with its non-finite rules, as for the sparse routines (the outputs
+ * are plain doubles without a flag channel; products below 2^-968 or beyond the double range are outside it).
+ * The bits depend on the data only: not on p, q, the column panel or output tile, ldx / ldy / ldc, the alignment of X and
+ * Y, fpe (0 or >= 2), early_exit, the grid, the row slab or the internal path (exblas_set_bdot_path).  fpe == 1 is the
+ * plain, non-reproducible fp64 computation on the same structure.  early_exit with fpe > 8 is ExGEMV's (the reference's)
+ * silent return: nothing is launched and the outputs keep their values.
+ * Columns are independent: a NaN or Inf in column i of X changes only row i of C ('G') or c[i] ('D'), and likewise for Y
+ * and the columns of C; 0 * Inf is NaN, as in ExDOT.  X and Y are only read and may be the same block or overlap; with
+ * X == Y in 'G', C is bit for bit symmetric.  C must not overlap X or Y.  The padding between q and ldc is never
+ * written; the padding of X and Y is never read.  All offsets (r * ld) are 64-bit.  Any p and q are served (outputs
+ * beyond 4096, or a Gram matrix beyond 64 x 64, in batches that each read their columns again); the design range is up to
+ * 64 each.
+ * n == 0 writes +0.0 to every output; p == 0 or q == 0: success, nothing is launched.  n < 0 or n > INT_MAX, p < 0,
+ * q < 0, ldx < p, ldy < q, ldc < q in 'G', p != q in 'D', a mode other than G/g/D/d or fpe < 0: hipErrorInvalidValue.
+ * Stream-ordered launches only (per batch a memset, the accumulate kernel and the finalize kernel; no host
+ * synchronisation): the accumulators -- one 68-limb set of 576 bytes per output and accumulator group -- live in the
+ * context workspace, EXBLAS_BDOT_WORKSPACE_BYTES whatever the sizes, are zeroed before use (other routines leave scratch
+ * in the workspace) and are left zeroed.  Capturable into a hipGraph after exblas_reserve_workspace or one call.
+ * Returns 0 or a hipError_t.
+ * Not provided: products outside the domain (no per-output low / high accumulators), a row-sharded form, column-major
+ * blocks, fp32, alpha / beta. */
+#define EXBLAS_BDOT_WORKSPACE_BYTES ((size_t)4096 * 576)
+int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                      double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
+/* Test hook for ExBDOT (same bits on every path): 0 automatic, 1 the row slab of a workgroup forced to the smallest the
+ * kernel supports (4 waves x 64 / T rows, T the outputs of a tile: a few hundred rows are already merged from many
+ * workgroups per output), 2 column panels ('D') and output tiles ('G') of width 4 (p, q = 5 then cross an edge). */
+void exblas_set_bdot_path(int mode);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -396,6 +432,8 @@ int exblas_exsptrsm_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int 
 int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
+int exblas_exbdot_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
+                      const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
 int exblas_reserve_workspace_ctx(exblas_ctx_t *ctx, size_t bytes);
 size_t exblas_workspace_bytes_ctx(exblas_ctx_t *ctx);
 int exblas_last_gemm_info_ctx(exblas_ctx_t *ctx, int *out8);
@@ -534,6 +572,10 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
  * (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see exblas_last_sptrsm_info). */
 int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, const void *row_ptr, const void *col_idx,
                         const double *val, double *x, int64_t ldx, int fpe, int early_exit);
+/* exblas_exbdot_dev on host arrays (X: n rows of ldx, Y: n rows of ldy, C: p rows of ldc in 'G', p doubles in 'D'; the
+ * padding of C keeps its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue. */
+int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                  double *c, int64_t ldc, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
