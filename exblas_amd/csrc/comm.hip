@@ -3,12 +3,14 @@
 // What the reference does inside its library call (src/cpu/blas/blas1/ExSUM.cpp): rank 0 scatters slices (:33-63),
 // every rank reduces its slice to a normalised superaccumulator, MPI_Reduce(MPI_LONG, MPI_SUM) adds the limbs
 // (:142-152, :266-273) and the root rounds.  Here the same three steps run on the GPUs:
-//   * every rank reduces its shard with the streaming kernels and normalises (k_finalize) -> 72 int64 words
-//     (68 digits < 2^32 + 3 non-finite indicators) that never leave HBM;
+//   * every rank reduces its shard with the streaming kernels and normalises (k_finalize) -> 72 int64 words that never
+//     leave HBM: 67 digits in [0, 2^32) under a signed top digit (a rank's partial total may be negative: -1 over a run
+//     of 0xffffffff digits), 3 non-finite indicators (0 or 1) and one word that counts 1 for a rank with a product below
+//     2^-968 and 65536 for one with a finite overflowing product;
 //   * ONE int64-sum all-reduce launch over those 576 bytes and the 2 x 576 bytes of the LOW and HIGH digit sets (ExDOT
 //     products below 2^-968 / beyond the double range; all zero otherwise) (RCCL over xGMI: a group of two
 //     ncclAllReduce(ncclInt64, ncclSum) on the caller's stream).  Integer addition is associative and commutative, so ring/tree order, GPU count and shard boundaries
-//     cannot change a bit; digits < 2^32 leave room for 2^31 ranks;
+//     cannot change a bit; digits < 2^32 leave room for 2^31 ranks (the counter word for 65535);
 //   * every rank runs the same carry-propagation + rounding kernel on the summed digits.
 // ExGEMV / ExGEMM shard the OUTPUT (rows of A and y resp. C): no reduction collective at all, only data movement --
 // x resp. B replicated by one broadcast, y resp. C completed by an all-gather that overlaps the remaining compute.

@@ -423,12 +423,15 @@ def _dot_case(kind, pairs, **kw):
     return c
 
 
-def family_f_low():
+def family_f_low(positions=None):
     """H + f: (case list).  H from Family A (kinds exact, tie, tie-1; the three mantissas; 64 positions: every
-    leading-zero count in limbs 3 and 40) and from the positive totals of Family B"""
-    hs = [c for c in family_a(a_positions_for_limbs(F_LIMBS), kinds=("exact", "tie", "tie-1"), signs=(1,))]
+    leading-zero count in limbs 3 and 40 -- or the given positions, for a small batch) and from the positive totals of
+    Family B"""
+    hs = [c for c in family_a(a_positions_for_limbs(F_LIMBS) if positions is None else positions,
+                              kinds=("exact", "tie", "tie-1"), signs=(1,))]
     hs += [c for c in family_b() if c.T >= 0]
-    assert len(a_positions_for_limbs(F_LIMBS)) == 64 and any(c.T == (1 << 53) - 1 for c in hs)
+    assert positions is not None or len(a_positions_for_limbs(F_LIMBS)) == 64
+    assert any(c.T == (1 << 53) - 1 for c in hs)
     out = []
     for h in hs:
         for fname, pairs in F_PARTS.items():

@@ -65,3 +65,33 @@ def exact_sum_int(a):
     tot *= 2**1074
     assert tot.denominator == 1
     return tot.numerator
+
+
+def bits(a):
+    """the int64 bit patterns of doubles"""
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
+
+
+def same_bits(got, want):
+    """element-wise same_double on int64 views: equal bits, or both zero"""
+    g, w = np.asarray(got, dtype=np.int64), np.asarray(want, dtype=np.int64)
+    return (g == w) | (((g << 1) == 0) & ((w << 1) == 0))
+
+
+def expected_fields(cases):
+    """(want bits, reference-mode bits, canon [n, 41], digits [n, 68], canon-fits mask) of blas1_cases cases with an
+    integer total T, from Python integers alone (the reference mode: the oracle's restatement of the reference's Round()
+    on those canonical limbs).  Where the mask is False the total does not fit the canonical limbs: canon and the
+    reference-mode double are undefined there (zeros here) and must not be compared."""
+    import blas1_cases as B
+    from oracle import pyoracle
+    pyoracle.build()
+    n = len(cases)
+    want = bits([c.want for c in cases])
+    fits = np.array([B.canon_fits(c.T) for c in cases], dtype=bool)
+    canon = np.zeros((n, 41), dtype=np.int64)
+    if fits.any():
+        canon[fits] = B.canon_matrix([c.T for c, ok in zip(cases, fits) if ok])
+    ref = np.array([pyoracle.round_limbs(canon[i], pyoracle.ROUND_REFERENCE) if fits[i] else 0.0 for i in range(n)])
+    digits = B.digits_matrix([c.T for c in cases]) if n else np.zeros((0, 68), dtype=np.int64)
+    return want, bits(ref), canon, digits, fits

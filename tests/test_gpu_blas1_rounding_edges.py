@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 import blas1_cases as B
-from helpers import FPE_VARIANTS_DOT, FPE_VARIANTS_SUM
+from helpers import FPE_VARIANTS_DOT, FPE_VARIANTS_SUM, expected_fields
+from helpers import bits as _bits, same_bits as _same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -40,32 +41,13 @@ def ex():
     exblas_amd.load_library().exblas_set_round_mode(0)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same_bits(got, want):
-    """element-wise same_double on int64 views: equal bits, or both zero"""
-    g, w = np.asarray(got, dtype=np.int64), np.asarray(want, dtype=np.int64)
-    return (g == w) | (((g << 1) == 0) & ((w << 1) == 0))
-
-
 @functools.lru_cache(maxsize=None)
 def _expected(which):
     """(cases, want bits, reference-mode bits or None, canon [n, 41], digits [n, 68], canon-fits mask) -- computed once"""
-    from oracle import pyoracle
-    pyoracle.build()
     cases = {"sum": B.sum_cases, "bcd": lambda: tuple(c for c in B.sum_cases() if c.family != "A"),
              "a_subset": lambda: tuple(c for c in B.sum_cases() if c.family == "A" and (c.p >> 5) in A_LIMBS),
              "e": lambda: tuple(B.family_e())}[which]()
-    n = len(cases)
-    want = _bits([c.want for c in cases])
-    fits = np.array([B.canon_fits(c.T) for c in cases])
-    canon = np.zeros((n, 41), dtype=np.int64)
-    canon[fits] = B.canon_matrix([c.T for c, ok in zip(cases, fits) if ok])
-    ref = np.array([pyoracle.round_limbs(canon[i], pyoracle.ROUND_REFERENCE) if fits[i] else 0.0 for i in range(n)])
-    digits = B.digits_matrix([c.T for c in cases])
-    return cases, want, _bits(ref), canon, digits, fits
+    return (cases,) + expected_fields(cases)
 
 
 def _report(what, bad, cases, got, want):

@@ -39,6 +39,26 @@ def _inputs(ex):
     return x, y, a_cm, xv, yv, A, B, C0
 
 
+def _rank_cases_batch(ex, torch, comm, rank, world):
+    """60 constructed cases (tests/rank_cases.py: ExSUM and ExDOT, by_sign and last_alone, with ballast) dealt over the
+    actual world; every rank checks the double against the case's expectation from Python integers, and the flags"""
+    import rank_cases as RC
+    from helpers import same_double
+    got = []
+    for job in RC.real_rank_batch(world):
+        sh = job.shards
+        a = torch.from_numpy(sh.a[rank]).cuda()
+        b = torch.from_numpy(sh.b[rank]).cuda() if sh.is_dot else None
+        if comm is None:
+            r = ex.exdot_dev(a, b, job.fpe, job.ee, n=len(sh.a[rank])) if sh.is_dot else ex.exsum_dev(a, job.fpe, job.ee, n=len(sh.a[rank]))
+        else:
+            r = ex.exdot_allreduce(comm, a, b, job.fpe, job.ee) if sh.is_dot else ex.exsum_allreduce(comm, a, job.fpe, job.ee)
+        rec = ex.read_record(r)
+        assert same_double(rec.exact, sh.want) and rec.flags == sh.flags, (world, rank, sh, rec.exact, sh.want, rec.flags, sh.flags)
+        got.append((rec.words[0:1].view(np.float64).view(np.int64).item(), rec.flags))
+    return got
+
+
 def _run_all(ex, torch, comm, rank, world):
     """what one rank does; world == 1 with comm None computes the single-rank reference through the plain *_dev calls"""
     x, y, a_cm, xv, yv, A, B, C0 = _inputs(ex)
@@ -157,6 +177,7 @@ def _run_all(ex, torch, comm, rank, world):
         want = torch.zeros(m2 * N, dtype=torch.float64, device="cuda")
         ex.exgemm_dev("N", "N", m2, N, K, 1.0, A, K, B, N, 0.0, want, N, 8, True)
         assert torch.equal(C3.view(torch.int64), want.view(torch.int64))
+    out["rank_cases"] = _rank_cases_batch(ex, torch, comm, rank, world)
     torch.cuda.synchronize()
     return out
 
@@ -177,6 +198,10 @@ def _worker(rank, world, port, q):
         assert comm.size == world and comm.rank == rank
         q.put((rank, _run_all(ex, torch, comm, rank, world)))
         comm.destroy()
+    except BaseException:
+        import traceback
+        q.put((rank, {"error": traceback.format_exc()}))      # the parent fails at once, not when its queue times out
+        raise
     finally:
         dist.destroy_process_group()
 
@@ -194,6 +219,8 @@ def test_shared_gpu_ranks_bit_identical(world):
     for p in procs:
         p.start()
     res = [q.get(timeout=400) for _ in range(world)]
+    for rank, out in res:
+        assert "error" not in out, (world, rank, out["error"])
     for p in procs:
         p.join(60)
         assert p.exitcode == 0
