@@ -51,6 +51,8 @@ C_ABI_SYMBOLS = [
     "exblas_exsptrsm_csr_dev", "exblas_exsptrsm_csr_ctx", "exblas_exsptrsm_csr", "exblas_set_sptrsm_path",
     "exblas_last_sptrsm_info",
     "exblas_exbdot_dev", "exblas_exbdot_ctx", "exblas_exbdot", "exblas_set_bdot_path",
+    "exblas_exbdot_export_dev", "exblas_exbdot_export_ctx", "exblas_exbdot_round_dev", "exblas_exbdot_round_ctx",
+    "exblas_exbdot_allreduce_dev",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -199,6 +201,11 @@ def load_library():
     L.exblas_exbdot.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32]
     L.exblas_set_bdot_path.argtypes = [i32]
     L.exblas_set_bdot_path.restype = None
+    L.exblas_exbdot_export_dev.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i32, i32, vp]
+    L.exblas_exbdot_export_ctx.argtypes = [vp] + L.exblas_exbdot_export_dev.argtypes
+    L.exblas_exbdot_round_dev.argtypes = [C.c_char, i32, i32, vp, i32, vp, i64, vp]
+    L.exblas_exbdot_round_ctx.argtypes = [vp] + L.exblas_exbdot_round_dev.argtypes
+    L.exblas_exbdot_allreduce_dev.argtypes = [vp, C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32, vp]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -638,9 +645,8 @@ def _bdot_sizes(mode, n, p, q, fpe):
         raise ValueError("exbdot: fpe must be >= 0")
 
 
-def _bdot_args(X, Y, mode, out, fpe, early_exit):
-    """Validates a device ExBDOT call before anything is launched; returns (out, the C arguments up to the stream)."""
-    torch = _torch()
+def _bdot_blocks(X, Y, mode, fpe):
+    """The rules of the two blocks of a device ExBDOT call; returns (X, Y, mode, n, p, q)."""
     mode = _bdot_mode(mode)
     if getattr(X, "ndim", 2) == 1:
         raise ValueError("exbdot: X must be 2-D (n x p); for two vectors use exdot_dev")
@@ -655,6 +661,12 @@ def _bdot_args(X, Y, mode, out, fpe, early_exit):
         raise ValueError(f"exbdot: X has {X.shape[0]} rows and Y has {Y.shape[0]}")
     n, p, q = int(X.shape[0]), int(X.shape[1]), int(Y.shape[1])
     _bdot_sizes(mode, n, p, q, fpe)
+    return X, Y, mode, n, p, q
+
+
+def _bdot_out(mode, p, q, out, device, **others):
+    """The rules of C (checked, or allocated on `device` when None) once `others` lie on the GPU; returns (out, ldc)."""
+    torch = _torch()
     shape = (p, q) if mode == "G" else (p,)
     if out is not None:
         if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != shape:
@@ -663,12 +675,63 @@ def _bdot_args(X, Y, mode, out, fpe, early_exit):
             raise ValueError("exbdot: out needs stride(1) == 1 and stride(0) >= q")
         if mode == "D" and p > 1 and out.stride(0) != 1:
             raise ValueError("exbdot: out must be contiguous in mode 'D'")
-    _on_gpu("exbdot", X=X, Y=Y, **({} if out is None else {"out": out}))
+    _on_gpu("exbdot", **others, **({} if out is None else {"out": out}))
     if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=X.device)
-    ldc = _ld(out, q) if mode == "G" else 1
+        out = torch.empty(shape, dtype=torch.float64, device=device)
+    return out, (_ld(out, q) if mode == "G" else 1)
+
+
+def _bdot_args(X, Y, mode, out, fpe, early_exit):
+    """Validates a device ExBDOT call before anything is launched; returns (out, the C arguments up to the stream)."""
+    X, Y, mode, n, p, q = _bdot_blocks(X, Y, mode, fpe)
+    out, ldc = _bdot_out(mode, p, q, out, X.device, X=X, Y=Y)
     return out, (mode.encode(), n, p, q, _ptr(X), _ld(X, p), _ptr(Y), _ld(Y, q), _ptr(out), ldc, int(fpe),
                  int(bool(early_exit)))
+
+
+def _bdot_sets(sets, outputs, stacked):
+    """`sets`: a contiguous int64 tensor [outputs, SET_WORDS], or, where `stacked`, also [nsets >= 1, outputs, SET_WORDS]"""
+    torch = _torch()
+    if not isinstance(sets, torch.Tensor):
+        raise TypeError("exbdot: sets must be a torch tensor")
+    if sets.dtype != torch.int64:
+        raise TypeError("exbdot: sets must be int64")
+    one = (outputs, SET_WORDS)
+    if tuple(sets.shape) != one and not (stacked and sets.dim() == 3 and sets.shape[0] >= 1 and tuple(sets.shape[1:]) == one):
+        raise ValueError(f"exbdot: sets must have shape {one}" + (f" or (nsets >= 1, {outputs}, {SET_WORDS})" if stacked else "")
+                         + f", not {tuple(sets.shape)}")
+    if not sets.is_contiguous():
+        raise ValueError("exbdot: sets must be contiguous")
+
+
+def _bdot_export_args(X, Y, mode, sets, fpe, early_exit):
+    """Validates a device ExBDOT export before anything is launched; returns (sets, the C arguments up to the stream)."""
+    X, Y, mode, n, p, q = _bdot_blocks(X, Y, mode, fpe)
+    if int(fpe) == 1:
+        raise ValueError("exbdot: fpe == 1 (plain fp64 sums) has no digit sets to export")
+    if early_exit and int(fpe) > 8:
+        raise ValueError("exbdot: early_exit with fpe > 8 computes nothing: there are no digit sets to export")
+    outputs = p * q if mode == "G" else p
+    if sets is not None:
+        _bdot_sets(sets, outputs, False)
+    _on_gpu("exbdot", X=X, Y=Y, **({} if sets is None else {"sets": sets}))
+    if sets is None:
+        sets = _torch().empty((outputs, SET_WORDS), dtype=_torch().int64, device=X.device)
+    return sets, (mode.encode(), n, p, q, _ptr(X), _ld(X, p), _ptr(Y), _ld(Y, q), _ptr(sets), int(fpe),
+                  int(bool(early_exit)))
+
+
+def _bdot_round_args(sets, mode, p, q, out):
+    """Validates a device ExBDOT round before anything is launched; returns (out, the C arguments up to the stream)."""
+    mode = _bdot_mode(mode)
+    p, q = int(p), int(q)
+    if p < 0 or q < 0:
+        raise ValueError("exbdot: p and q must be >= 0")
+    _bdot_sizes(mode, 0, p, q, 0)
+    _bdot_sets(sets, p * q if mode == "G" else p, True)
+    nsets = int(sets.shape[0]) if sets.dim() == 3 else 1
+    out, ldc = _bdot_out(mode, p, q, out, sets.device, sets=sets)
+    return out, (mode.encode(), p, q, _ptr(sets), nsets, _ptr(out), ldc)
 
 
 def exbdot_dev(X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
@@ -680,6 +743,27 @@ def exbdot_dev(X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
     otherwise checked; it is returned."""
     out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
     _check(load_library().exblas_exbdot_dev(*args, _stream_ptr(_torch())), "exbdot_dev")
+    return out
+
+
+def exbdot_export_dev(X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
+    """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
+    [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
+    shard's products as 68 normalised base-2^32 digits under a signed top digit, three 0 / 1 indicators (+Inf, -Inf, NaN
+    seen) and a zero word.  Sets of different shards add as plain int64; exbdot_round_dev rounds the sum.  fpe == 1 and
+    early_exit with fpe > 8 are refused: they have no digit sets."""
+    sets, args = _bdot_export_args(X, Y, mode, sets, fpe, early_exit)
+    _check(load_library().exblas_exbdot_export_dev(*args, _stream_ptr(_torch())), "exbdot_export_dev")
+    return sets
+
+
+def exbdot_round_dev(sets, mode, p, q, out=None):
+    """Second half: `sets` is a contiguous int64 tensor [outputs, 72] or [nsets, outputs, 72] (the exports of nsets shards
+    stacked, or a sum of exports); the nsets copies of every output are added and rounded once, under the current
+    rounding mode, into `out` (as for exbdot_dev: p x q in mode 'G', p in mode 'D'; allocated when None).  Bit for bit
+    exbdot_dev on the rows of all shards together.  `sets` is only read."""
+    out, args = _bdot_round_args(sets, mode, p, q, out)
+    _check(load_library().exblas_exbdot_round_dev(*args, _stream_ptr(_torch())), "exbdot_round_dev")
     return out
 
 
@@ -790,6 +874,16 @@ class Context:
     def exbdot(self, X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
         out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
         _check(load_library().exblas_exbdot_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_ctx")
+        return out
+
+    def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
+        sets, args = _bdot_export_args(X, Y, mode, sets, fpe, early_exit)
+        _check(load_library().exblas_exbdot_export_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_export_ctx")
+        return sets
+
+    def exbdot_round(self, sets, mode, p, q, out=None):
+        out, args = _bdot_round_args(sets, mode, p, q, out)
+        _check(load_library().exblas_exbdot_round_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_round_ctx")
         return out
 
     def workspace_bytes(self):
@@ -1008,4 +1102,4 @@ def exbdot(X, Y=None, mode="G", fpe=8, early_exit=True):
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401
                    shard_range, row_block, exgemv_sharded, exgemm_sharded, exsum_allreduce_pipelined,
-                   exdot_allreduce_pipelined, pipeline_drain)
+                   exdot_allreduce_pipelined, pipeline_drain, exbdot_allreduce)

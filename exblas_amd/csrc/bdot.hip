@@ -16,8 +16,12 @@
 //                    and the expansion at the end of the slab, goes to the output's 68 limbs in LDS (ds_add_u64, shared
 //                    by the waves).  Epilogue: the non-zero limbs are added to the output's set of one of `ngroups` group
 //                    accumulators with int64 atomics (exact, order-free); non-finite products count in words 68..70
-//   k_bdot_finalize  one wave per output: sums the groups (low and high halves apart, so that the sum cannot overflow),
-//                    finish_wave, stores the double of the rounding mode, leaves the sets zero
+//   k_bdot_finalize  one wave per output: sums the copies of its set (the groups; or the sets of several shards, read
+//                    only) with low and high halves apart, so that the sum cannot overflow, finish_wave, stores the
+//                    double of the rounding mode, leaves the groups zero
+//   k_bdot_export    the row-sharded form's first half: the same sum of the groups, finish_wave<false>, and the normalised
+//                    digits (67 in [0, 2^32) under a signed top digit, three non-finite indicators) go out instead of the
+//                    double -- 72 int64 per output that add across ranks as plain integers; k_bdot_finalize rounds the sum
 // Outputs beyond 4096 (more than 64 x 64 in 'G') are served batch by batch with the same workspace.
 // fpe == 1 runs the same structure on plain fp64 sums (fp64 atomics: not reproducible).
 #include "superacc.hip.h"
@@ -137,9 +141,53 @@ __global__ void __launch_bounds__(BD_BLOCK) k_bdot_acc(BdotGeom g, long long n, 
     }
 }
 
-template <bool PLAIN>
-__global__ void __launch_bounds__(BD_BLOCK) k_bdot_finalize(BdotGeom g, long long *__restrict__ sets,
-                                                           double *__restrict__ out, long long ldc, int round_mode)
+// One wave sums the `ncopies` copies of an output's set, `stride` words apart (the accumulator groups, or the exported
+// sets of the shards): the low 32 bits and the signed high parts of the limbs are summed apart and the high parts enter
+// one limb up (as in k_finalize), so the sum cannot overflow however many adds the copies hold -- nor can 2^31 copies of
+// normalised digits.  ZERO: the copies are left zero.  v0: limb `lane`, v1: limb 64 + lane (lane < 4); a non-zero word
+// 68 / 69 / 70 in any copy raises FLAG_PINF / FLAG_NINF / FLAG_NAN.
+template <bool ZERO>
+__device__ __forceinline__ void bd_sum_copies(std::conditional_t<ZERO, long long, const long long> *p, long long stride,
+                                              int ncopies, long long &v0, long long &v1, unsigned &flags)
+{
+    const int lane = threadIdx.x & 63;
+    long long lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+    flags = 0;
+    for (int k = 0; k < ncopies; ++k, p += stride) {
+        const long long t0 = p[lane], t1 = lane < SET_WORDS - 64 ? p[64 + lane] : 0;
+        if constexpr (ZERO) {
+            p[lane] = 0;
+            if (lane < SET_WORDS - 64) p[64 + lane] = 0;
+        }
+        lo0 += t0 & 0xffffffffll;
+        hi0 += t0 >> 32;
+        if (lane < NL - 65) {
+            lo1 += t1 & 0xffffffffll;
+            hi1 += t1 >> 32;
+        } else if (lane == NL - 65) {   // the top limb is never split
+            lo1 += t1;
+        } else if (lane < NL - 64 + 3 && t1 != 0) {   // words 68..70: +Inf, -Inf, NaN seen
+            flags |= 1u << (lane - (NL - 64));
+        }
+    }
+    flags = (__ballot(flags & FLAG_PINF) ? FLAG_PINF : 0u) | (__ballot(flags & FLAG_NINF) ? FLAG_NINF : 0u) |
+            (__ballot(flags & FLAG_NAN) ? FLAG_NAN : 0u);
+    long long in0 = __shfl_up(hi0, 1), in1 = __shfl_up(hi1, 1);
+    const long long h63 = __shfl(hi0, 63);
+    if (lane == 0) {
+        in0 = 0;
+        in1 = h63;
+    }
+    v0 = lo0 + in0;
+    v1 = lane < NL - 64 ? lo1 + in1 : 0;
+}
+
+// output o of the batch rounds the copies at sets + o * SET_WORDS + k * stride, k < ncopies
+template <bool PLAIN, bool ZERO>
+__global__ void __launch_bounds__(BD_BLOCK) k_bdot_finalize(BdotGeom g,
+                                                           std::conditional_t<ZERO, long long, const long long> *__restrict__ sets,
+                                                           long long stride, int ncopies, double *__restrict__ out,
+                                                           long long ldc, int round_mode)
 {
     const int lane = threadIdx.x & 63;
     const long long nout = (long long)g.ni * g.nj;
@@ -147,58 +195,64 @@ __global__ void __launch_bounds__(BD_BLOCK) k_bdot_finalize(BdotGeom g, long lon
     if (o >= nout) return;   // (the whole wave)
     double *dst = g.diag ? out + g.i0 + o : out + (g.i0 + o / g.nj) * ldc + g.j0 + o % g.nj;
     if constexpr (PLAIN) {
+        static_assert(ZERO, "the plain sums live in the groups only");
         if (lane == 0) {
             double s = 0.0;
-            for (int k = 0; k < g.ngroups; ++k) {
-                long long *p = sets + ((long long)k * nout + o) * SET_WORDS;
+            for (int k = 0; k < ncopies; ++k) {
+                long long *p = sets + k * stride + o * SET_WORDS;
                 s += __longlong_as_double(p[0]);
                 p[0] = 0;
             }
             *dst = s;
         }
     } else {
-        // the low 32 bits and the signed high parts of the groups' limbs are summed apart and the high parts enter one limb
-        // up (as in k_finalize): the sum cannot overflow however many adds the groups hold
-        long long lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
-        unsigned flags = 0;
-        for (int k = 0; k < g.ngroups; ++k) {
-            long long *p = sets + ((long long)k * nout + o) * SET_WORDS;
-            const long long t0 = p[lane], t1 = lane < SET_WORDS - 64 ? p[64 + lane] : 0;
-            p[lane] = 0;
-            if (lane < SET_WORDS - 64) p[64 + lane] = 0;
-            lo0 += t0 & 0xffffffffll;
-            hi0 += t0 >> 32;
-            if (lane < NL - 65) {
-                lo1 += t1 & 0xffffffffll;
-                hi1 += t1 >> 32;
-            } else if (lane == NL - 65) {   // the top limb is never split
-                lo1 += t1;
-            } else if (lane < NL - 64 + 3 && t1 != 0) {   // words 68..70: +Inf, -Inf, NaN seen
-                flags |= 1u << (lane - (NL - 64));
-            }
-        }
-        flags = (__ballot(flags & FLAG_PINF) ? FLAG_PINF : 0u) | (__ballot(flags & FLAG_NINF) ? FLAG_NINF : 0u) |
-                (__ballot(flags & FLAG_NAN) ? FLAG_NAN : 0u);
-        long long in0 = __shfl_up(hi0, 1), in1 = __shfl_up(hi1, 1);
-        const long long h63 = __shfl(hi0, 63);
-        if (lane == 0) {
-            in0 = 0;
-            in1 = h63;
-        }
-        const long long v0 = lo0 + in0, v1 = lane < NL - 64 ? lo1 + in1 : 0;
+        long long v0, v1;
+        unsigned flags;
+        bd_sum_copies<ZERO>(sets + o * SET_WORDS, stride, ncopies, v0, v1, flags);
         const WaveFinish r = finish_wave(v0, v1, flags);
         if (lane == 0) *dst = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
     }
 }
 
+// output o of the batch: the groups summed and left zero, the normalised set stored at dst + (row * dst_ld + column) *
+// SET_WORDS, row and column those of the output in the whole result (dst_i0, dst_j0: the batch's corner there; 'D': the
+// output's index).  dst may be the groups' own block with the batch's outputs in order (dst_ld == g.nj, corner 0): a wave
+// has read, and zeroed, all it owns in every group before it stores into group 0's set of its own output.
+__global__ void __launch_bounds__(BD_BLOCK) k_bdot_export(BdotGeom g, long long *sets, long long *dst, long long dst_i0,
+                                                         long long dst_j0, long long dst_ld)
+{
+    const int lane = threadIdx.x & 63;
+    const long long nout = (long long)g.ni * g.nj;
+    const long long o = (long long)blockIdx.x * BD_WAVES + (threadIdx.x >> 6);
+    if (o >= nout) return;   // (the whole wave)
+    long long v0, v1;
+    unsigned flags;
+    bd_sum_copies<true>(sets + o * SET_WORDS, nout * SET_WORDS, g.ngroups, v0, v1, flags);
+    const WaveFinish r = finish_wave<false>(v0, v1, flags);
+    long long *d = dst + (g.diag ? dst_i0 + o : (dst_i0 + o / g.nj) * dst_ld + dst_j0 + o % g.nj) * SET_WORDS;
+    d[lane] = r.d0;
+    // limbs 64..67, then +Inf / -Inf / NaN seen as 0 or 1, then a zero word
+    if (lane < SET_WORDS - 64) d[64 + lane] = lane < NL - 64 ? r.d1 : (lane < NL - 64 + 3 ? (long long)((flags >> (lane - (NL - 64))) & 1u) : 0ll);
+}
+
+// where the outputs of a launch go: doubles (`sets_out` and `merge` null), the exported sets of the whole result in output
+// order (`sets_out`), or doubles rounded from the sets that `merge` has summed over the ranks, batch by batch
+struct BdotSink {
+    double *out = nullptr;
+    long long ldc = 0;
+    int round_mode = 0;
+    long long *sets_out = nullptr;
+    const BdotMerge *merge = nullptr;
+};
+
 template <int N, bool EE, bool PLAIN>
-static hipError_t bdot_launch(Ctx &c, bool diag, long long n, int p, int q, const double *x, long long ldx,
-                              const double *y, long long ldy, double *out, long long ldc, int round_mode, hipStream_t st)
+static int bdot_launch(Ctx &c, bool diag, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                       long long ldy, const BdotSink &sink, hipStream_t st)
 {
     hipError_t err;
     // the footprint depends on nothing: a captured call replays into the block any earlier call (or a reservation) left
     long long *sets = (long long *)workspace(c, (size_t)BD_BATCH * SET_WORDS * 8, st, &err);
-    if (!sets) return err;
+    if (!sets) return (int)err;
     const int narrow = c.bdot_path == 2;
     const int bi = diag ? BD_BATCH : BD_EDGE;
     for (int i0 = 0; i0 < p; i0 += bi) {
@@ -233,14 +287,53 @@ static hipError_t bdot_launch(Ctx &c, bool diag, long long n, int p, int q, cons
             const long long nslabs = max(1ll, (total + g.steps - 1) / g.steps);
             // the workspace is shared with routines that leave scratch in it: the sets are zeroed here as well
             err = hipMemsetAsync(sets, 0, (size_t)g.ngroups * nout * SET_WORDS * 8, st);
-            if (err != hipSuccess) return err;
+            if (err != hipSuccess) return (int)err;
             hipLaunchKernelGGL((k_bdot_acc<N, EE, PLAIN>), dim3((unsigned)(nslabs * g.ntiles)), dim3(BD_BLOCK), 0, st, g, n,
                                x, ldx, y, ldy, sets);
-            hipLaunchKernelGGL((k_bdot_finalize<PLAIN>), dim3((unsigned)((nout + BD_WAVES - 1) / BD_WAVES)),
-                               dim3(BD_BLOCK), 0, st, g, sets, out, ldc, round_mode);
+            const dim3 waves((unsigned)((nout + BD_WAVES - 1) / BD_WAVES));
+            if constexpr (!PLAIN) {
+                if (sink.sets_out) {
+                    hipLaunchKernelGGL(k_bdot_export, waves, dim3(BD_BLOCK), 0, st, g, sets, sink.sets_out, (long long)g.i0,
+                                       (long long)g.j0, (long long)q);
+                    continue;
+                }
+                if (sink.merge) {
+                    // in place: the batch's normalised sets land in group 0's block, contiguous over the batch; ONE
+                    // all-reduce over them, and the sum is rounded as one copy (and left zero)
+                    hipLaunchKernelGGL(k_bdot_export, waves, dim3(BD_BLOCK), 0, st, g, sets, sets, 0ll, 0ll, (long long)g.nj);
+                    if ((err = hipGetLastError()) != hipSuccess) return (int)err;
+                    if (int rc = sink.merge->allreduce(sink.merge->user, sets, (size_t)nout * SET_WORDS, st)) return rc;
+                    hipLaunchKernelGGL((k_bdot_finalize<false, true>), waves, dim3(BD_BLOCK), 0, st, g, sets, 0ll, 1, sink.out,
+                                       sink.ldc, sink.round_mode);
+                    continue;
+                }
+            }
+            hipLaunchKernelGGL((k_bdot_finalize<PLAIN, true>), waves, dim3(BD_BLOCK), 0, st, g, sets, nout * SET_WORDS,
+                               g.ngroups, sink.out, sink.ldc, sink.round_mode);
         }
     }
-    return hipGetLastError();
+    return (int)hipGetLastError();
+}
+
+template <bool PLAIN_OK>
+static int bdot_variant(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                        long long ldy, const BdotSink &sink, int fpe, int early_exit, hipStream_t st)
+{
+    const bool diag = mode == 'D' || mode == 'd';
+    if (p == 0 || q == 0) return 0;
+    if constexpr (PLAIN_OK) {
+        if (fpe == 1) {
+            BdotSink plain = sink;
+            plain.round_mode = 0;
+            return bdot_launch<0, false, true>(c, diag, n, p, q, x, ldx, y, ldy, plain, st);
+        }
+    }
+    if (fpe < 3) return bdot_launch<0, false, false>(c, diag, n, p, q, x, ldx, y, ldy, sink, st);
+    int e = 0;
+    select_variant<3>(fpe, early_exit, [&](auto N, auto EE) {
+        e = bdot_launch<N(), EE(), false>(c, diag, n, p, q, x, ldx, y, ldy, sink, st);
+    });
+    return e;
 }
 
 // fpe == 1: plain fp64; fpe < 3: superaccumulators only, as ExDOT; early exit with fpe > 8: nothing is launched and the
@@ -249,15 +342,51 @@ hipError_t exbdot_dispatch(Ctx &c, char mode, long long n, int p, int q, const d
                            long long ldy, double *out, long long ldc, int fpe, int early_exit, int round_mode,
                            hipStream_t st)
 {
-    const bool diag = mode == 'D' || mode == 'd';
-    if (p == 0 || q == 0) return hipSuccess;
-    if (fpe == 1) return bdot_launch<0, false, true>(c, diag, n, p, q, x, ldx, y, ldy, out, ldc, 0, st);
-    if (fpe < 3) return bdot_launch<0, false, false>(c, diag, n, p, q, x, ldx, y, ldy, out, ldc, round_mode, st);
-    hipError_t e = hipSuccess;
-    select_variant<3>(fpe, early_exit, [&](auto N, auto EE) {
-        e = bdot_launch<N(), EE(), false>(c, diag, n, p, q, x, ldx, y, ldy, out, ldc, round_mode, st);
-    });
-    return e;
+    BdotSink sink;
+    sink.out = out;
+    sink.ldc = ldc;
+    sink.round_mode = round_mode;
+    return (hipError_t)bdot_variant<true>(c, mode, n, p, q, x, ldx, y, ldy, sink, fpe, early_exit, st);
+}
+
+// The row-sharded forms: fpe == 1 (no digit sets) and early exit with fpe > 8 (no variant) are the caller's to refuse.
+// d_sets: the [outputs][SET_WORDS] sets of the whole result in output order.
+int exbdot_export_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                           long long ldy, long long *d_sets, int fpe, int early_exit, hipStream_t st)
+{
+    BdotSink sink;
+    sink.sets_out = d_sets;
+    return bdot_variant<false>(c, mode, n, p, q, x, ldx, y, ldy, sink, fpe, early_exit, st);
+}
+
+// per batch: export in place, merge->allreduce over the batch's outputs * SET_WORDS words, round.  The calls of
+// merge->allreduce depend on (mode, p, q) only.
+int exbdot_merge_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                          long long ldy, double *out, long long ldc, int fpe, int early_exit, int round_mode,
+                          const BdotMerge *merge, hipStream_t st)
+{
+    BdotSink sink;
+    sink.out = out;
+    sink.ldc = ldc;
+    sink.round_mode = round_mode;
+    sink.merge = merge;
+    return bdot_variant<false>(c, mode, n, p, q, x, ldx, y, ldy, sink, fpe, early_exit, st);
+}
+
+// d_sets: [nsets][outputs][SET_WORDS], read only; no workspace, one launch over the whole result
+hipError_t exbdot_round_dispatch(char mode, int p, int q, const long long *d_sets, int nsets, double *out, long long ldc,
+                                 int round_mode, hipStream_t st)
+{
+    BdotGeom g = {};
+    g.diag = mode == 'D' || mode == 'd';
+    g.ni = p;
+    g.nj = g.diag ? 1 : q;
+    const long long nout = (long long)g.ni * g.nj;
+    if (nout == 0) return hipSuccess;
+    if (nout > (long long)0x7fffffff * BD_WAVES) return hipErrorInvalidValue;   // (beyond any memory: a grid of 2^31 workgroups)
+    hipLaunchKernelGGL((k_bdot_finalize<false, false>), dim3((unsigned)((nout + BD_WAVES - 1) / BD_WAVES)), dim3(BD_BLOCK), 0,
+                       st, g, d_sets, nout * SET_WORDS, nsets, out, ldc, round_mode);
+    return hipGetLastError();
 }
 
 }  // namespace exb

@@ -593,6 +593,38 @@ static int exbdot_on(Ctx &c, char mode, int64_t n, int p, int q, const double *d
     return (int)exbdot_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, round_mode(), st);
 }
 
+// The row-sharded forms of ExBDOT.  Export: bdot_check_args' rules with the sets in C's place, and the two combinations
+// that have no digit sets to give -- plain fp64 sums (fpe == 1) and the silent return (early exit with fpe > 8), which
+// would leave the caller's sets undefined.
+static int bdot_export_check(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
+                             const int64_t *sets, int fpe, int early_exit, bool *empty)
+{
+    const int rc = bdot_check_args(mode, n, p, q, x, ldx, y, ldy, (const double *)sets, q, fpe, empty);
+    if (rc) return rc;
+    return (fpe == 1 || (early_exit && fpe > 8)) ? (int)hipErrorInvalidValue : 0;
+}
+
+static int exbdot_export_on(Ctx &c, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
+                            int64_t ldy, int64_t *d_sets, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;
+    const int rc = bdot_export_check(mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, &empty);
+    if (rc || empty) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    return exbdot_export_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, (long long *)d_sets, fpe, early_exit, st);
+}
+
+static int bdot_round_check(char mode, int p, int q, const int64_t *sets, int nsets, const double *c, int64_t ldc, bool *empty)
+{
+    *empty = false;
+    if (!one_of(mode, "GgDd") || p < 0 || q < 0 || nsets < 1) return (int)hipErrorInvalidValue;
+    const bool diag = mode == 'D' || mode == 'd';
+    if (diag ? p != q : ldc < q) return (int)hipErrorInvalidValue;
+    *empty = p == 0 || q == 0;
+    if (!*empty && (!c || !sets)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
 static int exsptrsv_on(Ctx &c, char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                        const double *d_val, double *d_x, int fpe, int early_exit, hipStream_t st)
 {
@@ -715,6 +747,26 @@ int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int
     return exbdot_on(ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_exbdot_export_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
+                             int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // refused, or nothing to do, before a context (and with it a device) is needed
+    const int rc = bdot_export_check(mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, &empty);
+    if (rc || empty) return rc;
+    return exbdot_export_on(ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_exbdot_round_dev(char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c, int64_t ldc,
+                            void *stream)
+{
+    bool empty;
+    const int rc = bdot_round_check(mode, p, q, d_sets, nsets, d_c, ldc, &empty);
+    if (rc || empty) return rc;
+    ctx(-1);
+    return (int)exbdot_round_dispatch(mode, p, q, (const long long *)d_sets, nsets, d_c, ldc, round_mode(),
+                                      (hipStream_t)stream);
+}
+
 int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                             const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
 {
@@ -756,6 +808,18 @@ int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alph
 }
 
 }  // extern "C"
+int exb::exbdot_merged_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                           double *d_c, int64_t ldc, int fpe, int early_exit, hipStream_t st, const BdotMerge *merge)
+{
+    bool empty;
+    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
+    if (rc) return rc;
+    if (fpe == 1) return (int)hipErrorInvalidValue;   // plain fp64 sums have no digit sets to merge
+    if (empty || (early_exit && fpe > 8)) return 0;    // (the silent return of exblas_exbdot_dev)
+    Ctx &c = ctx(-1);
+    std::lock_guard<std::mutex> lk(c.mu);
+    return exbdot_merge_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, round_mode(), merge, st);
+}
 int exb::exgemm_chunked_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
                             const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                             hipStream_t st, const GemmChunks *chunks)
@@ -889,6 +953,25 @@ int exblas_exbdot_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const
 {
     EXB_HANDLE(h);
     return exbdot_on(*cp, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_exbdot_export_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
+                             const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return exbdot_export_on(*cp, mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, (hipStream_t)stream);
+}
+
+// (the round uses nothing of the context: the handle is checked, and the form is there for symmetry with the export)
+int exblas_exbdot_round_ctx(exblas_ctx_t *h, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
+                            int64_t ldc, void *stream)
+{
+    EXB_HANDLE(h);
+    bool empty;
+    const int rc = bdot_round_check(mode, p, q, d_sets, nsets, d_c, ldc, &empty);
+    if (rc || empty) return rc;
+    return (int)exbdot_round_dispatch(mode, p, q, (const long long *)d_sets, nsets, d_c, ldc, round_mode(),
+                                      (hipStream_t)stream);
 }
 
 int exblas_exsptrsv_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,

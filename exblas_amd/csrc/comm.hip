@@ -549,6 +549,24 @@ int exblas_exdot_allreduce_dev(exblas_comm_t *cm, const double *d_a_local, int64
     return rc ? rc : exblas_allreduce_finish_dev(cm, stream, d_out);
 }
 
+// ExBDOT with the rows sharded: per batch of outputs the rank's normalised sets, ONE all-reduce over them, the round.
+// Refusals and the silent return come before the first collective (exbdot_merged_dev), the same way on every rank, and
+// the collectives depend on (mode, p, q) only: a rank without rows exports zero sets and posts them all.
+int exblas_exbdot_allreduce_dev(exblas_comm_t *cm, char mode, int64_t n_local, int p, int q, const double *d_x_local,
+                                int64_t ldx, const double *d_y_local, int64_t ldy, double *d_c, int64_t ldc, int fpe,
+                                int early_exit, void *stream)
+{
+    if (!cm) return (int)hipErrorInvalidValue;
+    std::lock_guard<std::mutex> lk(cm->mu);
+    BdotMerge merge;
+    merge.allreduce = [](void *u, long long *d_words, size_t count, hipStream_t st) {
+        return comm_allreduce_i64((exblas_comm *)u, d_words, count, st);
+    };
+    merge.user = cm;
+    return exbdot_merged_dev(mode, n_local, p, q, d_x_local, ldx, d_y_local, ldy, d_c, ldc, fpe, early_exit,
+                             (hipStream_t)stream, &merge);
+}
+
 int exblas_exgemv_sharded_dev(exblas_comm_t *cm, char transa, int m, int n, double alpha, const double *d_a_local,
                               int lda, double *d_x, int incx, int x_root, double beta, double *d_y, int incy, int gather,
                               int fpe, int early_exit, void *stream)

@@ -175,6 +175,23 @@ hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int ind
 hipError_t exbdot_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
                            long long ldy, double *out, long long ldc, int fpe, int early_exit, int round_mode,
                            hipStream_t st);
+// the row-sharded forms.  BdotMerge: the int64-sum all-reduce of one batch's exported sets (comm.hip), 0 or an error of
+// the comm layer; the three below return that, or a hipError_t
+struct BdotMerge {
+    int (*allreduce)(void *user, long long *d_words, size_t count, hipStream_t st) = nullptr;
+    void *user = nullptr;
+};
+int exbdot_export_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                           long long ldy, long long *d_sets, int fpe, int early_exit, hipStream_t st);
+int exbdot_merge_dispatch(Ctx &c, char mode, long long n, int p, int q, const double *x, long long ldx, const double *y,
+                          long long ldy, double *out, long long ldc, int fpe, int early_exit, int round_mode,
+                          const BdotMerge *merge, hipStream_t st);
+hipError_t exbdot_round_dispatch(char mode, int p, int q, const long long *d_sets, int nsets, double *out, long long ldc,
+                                 int round_mode, hipStream_t st);
+// capi.hip: exblas_exbdot_dev on the default context with the batches' sets summed by `merge` before they are rounded;
+// everything that can be refused, and the silent return, is decided before the first merge call
+int exbdot_merged_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                      double *d_c, int64_t ldc, int fpe, int early_exit, hipStream_t st, const BdotMerge *merge);
 
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,

@@ -62,7 +62,8 @@ class Comm:
     @staticmethod
     def host(rank, size, allreduce, bcast, allgatherv):
         """Host-callback transport.  The three callables get numpy views of the library's host buffer:
-        allreduce(int64 array) in-place sum; bcast(uint8 array, root); allgatherv(uint8 array, offsets list)."""
+        allreduce(int64 array) in-place sum; bcast(uint8 array, root); allgatherv(uint8 array, offsets list).
+        A communicator of one rank may pass None for all three: it has no transport and its collectives are skipped."""
         from . import load_library, _check, HOST_ALLREDUCE_FN, HOST_BCAST_FN, HOST_ALLGATHERV_FN
 
         def view(ptr, nbytes, dtype):
@@ -97,6 +98,8 @@ class Comm:
                 return 1
 
         cbs = (HOST_ALLREDUCE_FN(_ar), HOST_BCAST_FN(_bc), HOST_ALLGATHERV_FN(_ag))
+        if size == 1 and allreduce is None and bcast is None and allgatherv is None:
+            cbs = (HOST_ALLREDUCE_FN(0), HOST_BCAST_FN(0), HOST_ALLGATHERV_FN(0))   # null pointers
         h = C.c_void_p()
         _check(load_library().exblas_comm_init_host(C.byref(h), size, rank, cbs[0], cbs[1], cbs[2], None),
                "comm_init_host")
@@ -235,6 +238,21 @@ def allreduce_finish(comm, out=None):
         out = new_record_buffer()
     _check(load_library().exblas_allreduce_finish_dev(comm.handle, _args(torch), C.c_void_p(out.data_ptr())),
            "allreduce_finish_dev")
+    return out
+
+
+def exbdot_allreduce(comm, X_local, Y_local=None, mode="G", out=None, fpe=8, early_exit=True):
+    """ExBDOT of the blocks of all ranks stacked: X_local and Y_local (as for exbdot_dev; Y_local=None means X_local) hold
+    this rank's rows -- any number, none included; p, q and mode are the same on every rank.  Every rank receives the
+    same `out`, bit for bit exbdot_dev on all rows together: per batch of outputs the rank's digit sets, one int64-sum
+    all-reduce over them, one rounding (``exblas_exbdot_allreduce_dev``).  fpe == 1 is refused; early_exit with
+    fpe > 8 does nothing, on any rank."""
+    from . import load_library, _check, _bdot_args
+    if int(fpe) == 1:
+        raise ValueError("exbdot: fpe == 1 (plain fp64 sums) has no digit sets to all-reduce")
+    out, args = _bdot_args(X_local, Y_local, mode, out, fpe, early_exit)
+    import torch
+    _check(load_library().exblas_exbdot_allreduce_dev(comm.handle, *args, _args(torch)), "exbdot_allreduce_dev")
     return out
 
 

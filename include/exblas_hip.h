@@ -367,11 +367,38 @@ int exblas_last_sptrsm_info(int64_t *out4);
  * context workspace, EXBLAS_BDOT_WORKSPACE_BYTES whatever the sizes, are zeroed before use (other routines leave scratch
  * in the workspace) and are left zeroed.  Capturable into a hipGraph after exblas_reserve_workspace or one call.
  * Returns 0 or a hipError_t.
- * Not provided: products outside the domain (no per-output low / high accumulators), a row-sharded form, column-major
- * blocks, fp32, alpha / beta. */
+ * Not provided: products outside the domain (no per-output low / high accumulators), column-major blocks, fp32,
+ * alpha / beta.  Rows sharded over ranks or calls: exblas_exbdot_export_dev / _round_dev / _allreduce_dev below. */
 #define EXBLAS_BDOT_WORKSPACE_BYTES ((size_t)4096 * 576)
 int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
                       double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
+/* Row-sharded ExBDOT, first half: the rows of one shard go through the accumulate kernel as in exblas_exbdot_dev, and
+ * instead of a double every output leaves its NORMALISED DIGIT SET: EXBLAS_SET_WORDS int64 -- words 0..67 the exact sum
+ * of the shard's products in base 2^32 (67 digits in [0, 2^32) under a signed top digit: a negative total is -1 over a
+ * run of 0xffffffff digits), words 68 / 69 / 70 are 1 where a +Inf / -Inf / NaN product was seen and 0 otherwise, word 71
+ * is 0.  d_sets is [outputs][EXBLAS_SET_WORDS] in output order -- 'G': output i * q + j, p * q sets; 'D': output j, p sets
+ * -- whatever the batches: every word of every set is written, nothing beyond them.  Sets add as plain int64 (digits
+ * below 2^32: 2^31 of them cannot overflow), which is what an all-reduce of them does.
+ * The set of an output depends on the data of the shard only: not on the path, the tile, the grid, fpe (0 or >= 2) or
+ * early_exit.  n == 0 writes all-zero sets; p == 0 or q == 0 launches nothing.  fpe == 1 (plain fp64 sums have no digit
+ * sets) and early_exit with fpe > 8 (a silent return would leave the sets undefined) are hipErrorInvalidValue; every
+ * other argument rule is exblas_exbdot_dev's (d_sets in C's place, no ldc).  Workspace, launches and capture as
+ * exblas_exbdot_dev (the export kernel in the finalize kernel's place); the context's accumulators are left zero. */
+int exblas_exbdot_export_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
+                             int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
+/* Second half: d_sets is [nsets][outputs][EXBLAS_SET_WORDS] (nsets >= 1, else hipErrorInvalidValue), e.g. the exports
+ * of nsets shards stacked, or one set per output that an int64-sum all-reduce has already added.  One wave per output
+ * adds the nsets copies (low and high halves of the words apart: no overflow up to 2^31 sets of normalised digits or of
+ * sums of them), ORs the indicators (a non-zero word 68 / 69 / 70 counts: +Inf on one shard and -Inf on another give
+ * NaN), propagates the carries and stores the double of the current rounding mode at C's position (ldc in 'G', a
+ * contiguous vector in 'D').  d_sets is only read; the padding of C is never written.  One launch, no workspace,
+ * capturable.
+ * CONTRACT of export + round, and of exblas_exbdot_allreduce_dev: the result is bit for bit what exblas_exbdot_dev gives
+ * on the blocks of all shards stacked in any order -- for any number of shards, any shard sizes (empty ones included) and
+ * any mix of paths and fpe between them -- inside ExGEMV's product domain (there are still no per-output low / high
+ * sets).  A shard's PARTIAL total may be negative under a positive total, or beyond 2^1024 under a finite one. */
+int exblas_exbdot_round_dev(char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c, int64_t ldc,
+                            void *stream);
 /* Test hook for ExBDOT (same bits on every path): 0 automatic, 1 the row slab of a workgroup forced to the smallest the
  * kernel supports (4 waves x 64 / T rows, T the outputs of a tile: a few hundred rows are already merged from many
  * workgroups per output), 2 column panels ('D') and output tiles ('G') of width 4 (p, q = 5 then cross an edge). */
@@ -434,6 +461,10 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
 int exblas_exbdot_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                       const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
+int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
+                             const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
+int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
+                            int64_t ldc, void *stream);
 int exblas_reserve_workspace_ctx(exblas_ctx_t *ctx, size_t bytes);
 size_t exblas_workspace_bytes_ctx(exblas_ctx_t *ctx);
 int exblas_last_gemm_info_ctx(exblas_ctx_t *ctx, int *out8);
@@ -506,6 +537,18 @@ int exblas_exdot_allreduce_pipelined_dev(exblas_comm_t *comm, const double *d_a_
                                          const double *d_b_local, int64_t incb, int64_t n_local, int fpe, int early_exit,
                                          void *stream, int64_t *d_out, void *ev_kernel_start, void *ev_kernel_end);
 int exblas_pipeline_drain_dev(exblas_comm_t *comm, void *stream);
+/* Row-sharded ExBDOT: every rank holds n_local rows of X and Y (any split of the rows, n_local == 0 included; p, q, mode
+ * the same on every rank) and receives the same C -- bit for bit exblas_exbdot_dev on the blocks of all ranks stacked in
+ * any order (the contract at exblas_exbdot_round_dev).  Per batch of outputs (one up to 4096 outputs in 'D' or 64 x 64 in
+ * 'G'): the rank's normalised sets (exblas_exbdot_export_dev, in the workspace), ONE int64-sum all-reduce over
+ * outputs_of_batch * EXBLAS_SET_WORDS words, the round.  Number, order and length of the collectives depend on
+ * (mode, p, q) only -- never on n_local, the path or fpe.  Decided before the first collective, the same way on every
+ * rank: the argument rules of exblas_exbdot_dev, fpe == 1 (hipErrorInvalidValue: nothing to all-reduce), and early_exit
+ * with fpe > 8 (returns 0: no collective, C untouched, as exblas_exgemv_sharded_dev).  A one-rank host communicator
+ * without callbacks skips the collective.  Uses the device's default context. */
+int exblas_exbdot_allreduce_dev(exblas_comm_t *comm, char mode, int64_t n_local, int p, int q, const double *d_x_local,
+                                int64_t ldx, const double *d_y_local, int64_t ldy, double *d_c, int64_t ldc, int fpe,
+                                int early_exit, void *stream);
 /* Row-sharded ExGEMV.  transa 'N': rank r owns rows [first, last) = exblas_shard_range(m, r, size) of A and y;
  * d_a_local is that row block (column-major, leading dimension lda >= last - first).  transa 'T': rank r owns the
  * OUTPUTS [first, last) of n, i.e. columns first..last-1 of A; d_a_local points at column `first`.  d_x is the full
