@@ -259,50 +259,6 @@ def new_record_buffer():
     return torch.zeros(OUT_WORDS, dtype=torch.int64, device="cuda")
 
 
-def exsum_dev(x, fpe=8, early_exit=True, inca=1, n=None, out=None):
-    """ExSUM of a CUDA float64 tensor, stream-ordered; returns the int64 record tensor (on device)."""
-    torch = _require_gpu()
-    assert x.is_cuda and x.dtype == torch.float64
-    if n is None:
-        n = (x.numel() + inca - 1) // inca
-    if out is None:
-        out = new_record_buffer()
-    _check(load_library().exblas_exsum_dev(C.c_void_p(x.data_ptr()), n, inca, fpe, int(early_exit),
-                                           _stream_ptr(torch), C.c_void_p(out.data_ptr())), "exsum_dev")
-    return out
-
-
-def exdot_dev(x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None, out=None):
-    torch = _require_gpu()
-    assert x.is_cuda and y.is_cuda and x.dtype == torch.float64 and y.dtype == torch.float64
-    if n is None:
-        n = (x.numel() + incx - 1) // incx
-    if out is None:
-        out = new_record_buffer()
-    _check(load_library().exblas_exdot_dev(C.c_void_p(x.data_ptr()), incx, C.c_void_p(y.data_ptr()), incy, n, fpe,
-                                           int(early_exit), _stream_ptr(torch), C.c_void_p(out.data_ptr())),
-           "exdot_dev")
-    return out
-
-
-def exsum_accumulate_dev(x, fpe=8, early_exit=True, inca=1, n=None):
-    """Phase 1 only: stream x into the context accumulators (several calls fold into one exact sum)."""
-    torch = _require_gpu()
-    if n is None:
-        n = (x.numel() + inca - 1) // inca
-    _check(load_library().exblas_exsum_accumulate_dev(C.c_void_p(x.data_ptr()), n, inca, fpe, int(early_exit),
-                                                      _stream_ptr(torch)), "exsum_accumulate_dev")
-
-
-def exdot_accumulate_dev(x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None):
-    torch = _require_gpu()
-    if n is None:
-        n = (x.numel() + incx - 1) // incx
-    _check(load_library().exblas_exdot_accumulate_dev(C.c_void_p(x.data_ptr()), incx, C.c_void_p(y.data_ptr()), incy,
-                                                      n, fpe, int(early_exit), _stream_ptr(torch)),
-           "exdot_accumulate_dev")
-
-
 def set_launch_events(ev_start, ev_stop):
     """The next exsum / exdot accumulate call attaches these torch events (already recorded once, so that they own a
     handle; either may be None) to its streaming kernel's dispatch packet: kernel start / stop timestamps, no packets."""
@@ -313,15 +269,6 @@ def set_launch_events(ev_start, ev_stop):
 def set_accumulator_slot(slot):
     """Select which of the context's two accumulator sets the next accumulate/finish calls use (pipelining)."""
     _check(load_library().exblas_set_accumulator_slot(int(slot)), "set_accumulator_slot")
-
-
-def finish_dev(out=None):
-    """Phase 2: carry-propagate + round the context accumulators into a record; zeroes them."""
-    torch = _require_gpu()
-    if out is None:
-        out = new_record_buffer()
-    _check(load_library().exblas_finish_dev(_stream_ptr(torch), C.c_void_p(out.data_ptr())), "finish_dev")
-    return out
 
 
 def exsum_segmented_dev(values, offsets, fpe=8, early_exit=True, out=None):
@@ -347,34 +294,6 @@ def finalize_dev(digit_sets, flags_or=0, out=None):
     _check(load_library().exblas_finalize_dev(C.c_void_p(digit_sets.data_ptr()), nsets, flags_or, _stream_ptr(torch),
                                               C.c_void_p(out.data_ptr())), "finalize_dev")
     return out
-
-
-def exgemv_dev(trans, m, n, alpha, a, lda, x, beta, y, fpe=0, early_exit=False, incx=1, incy=1):
-    torch = _require_gpu()
-    _check(load_library().exblas_exgemv_dev(trans.encode(), m, n, alpha, C.c_void_p(a.data_ptr()), lda,
-                                            C.c_void_p(x.data_ptr()), incx, beta, C.c_void_p(y.data_ptr()), incy,
-                                            fpe, int(early_exit), _stream_ptr(torch)), "exgemv_dev")
-    return y
-
-
-def extrsv_dev(uplo, trans, diag, n, a, lda, x, fpe=0, early_exit=False, incx=1):
-    """x := A^-1 x (or A^-T x) in place on device tensors; returns 0, or -1 for the unsupported fpe >= 9."""
-    torch = _require_gpu()
-    rc = load_library().exblas_extrsv_dev(uplo.encode(), trans.encode(), diag.encode(), n, C.c_void_p(a.data_ptr()),
-                                          lda, C.c_void_p(x.data_ptr()), incx, fpe, int(early_exit),
-                                          _stream_ptr(torch))
-    if rc != -1:
-        _check(rc, "extrsv_dev")
-    return rc
-
-
-def exgemm_dev(transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe=0, early_exit=False):
-    torch = _require_gpu()
-    _check(load_library().exblas_exgemm_dev(transa.encode(), transb.encode(), m, n, k, alpha,
-                                            C.c_void_p(a.data_ptr()), lda, C.c_void_p(b.data_ptr()), ldb, beta,
-                                            C.c_void_p(c.data_ptr()), ldc, fpe, int(early_exit), _stream_ptr(torch)),
-           "exgemm_dev")
-    return c
 
 
 def _csr_rules(who, xp, crow, col, val, shape, square):
@@ -477,15 +396,6 @@ def _spmv_args(A, x, y, alpha, beta, fpe, early_exit):
                int(bool(early_exit)))
 
 
-def exspmv_dev(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
-    """ExSpMV: y = Round(alpha A x + beta y) row by row, exact and reproducible, stream-ordered on the current stream.
-    A: torch.sparse_csr_tensor (float64 values, int32 or int64 indices) or (crow, col, val, (m, n)) on the GPU; x a
-    float64 vector of at least n entries; y (m entries) is updated in place, or allocated (zeros) when None."""
-    y, args = _spmv_args(A, x, y, alpha, beta, fpe, early_exit)
-    _check(load_library().exblas_exspmv_csr_dev(*args, _stream_ptr(_torch())), "exspmv_dev")
-    return y
-
-
 def set_spmv_path(mode):
     """Test hook: 0 automatic, 1 accumulator finish for every row, 2 in-register rounding wherever certified (no row
     split), 3 every row split at a small chunk.  Same bits on every path."""
@@ -514,16 +424,6 @@ def _sptrsv_args(A, x, uplo, diag, fpe, early_exit):
         raise ValueError(f"exsptrsv: x must be a contiguous vector of m = {m} entries (it is solved in place)")
     _on_gpu("exsptrsv", crow=crow, col=col, val=val, x=x)
     return (u, d, m, bits, _ptr(crow), _ptr(col), _ptr(val), _ptr(x), int(fpe), int(bool(early_exit)))
-
-
-def exsptrsv_dev(A, x, uplo="L", diag="N", fpe=8, early_exit=True):
-    """ExSpTRSV: solves A x = b in place on x (b on entry), exact and reproducible, stream-ordered on the current stream:
-    x_i = Round(b_i - sum of the stored val * x_j before the diagonal) / d_i in substitution order (diag 'U': no division),
-    bit for bit what extrsv_dev gives on the densified matrix.  A: square torch.sparse_csr_tensor or (crow, col, val,
-    (m, m)) on the GPU (float64 values, int32 or int64 indices); entries of the other triangle are skipped.  Returns x."""
-    args = _sptrsv_args(A, x, uplo, diag, fpe, early_exit)
-    _check(load_library().exblas_exsptrsv_csr_dev(*args, _stream_ptr(_torch())), "exsptrsv_dev")
-    return x
 
 
 def set_sptrsv_path(mode):
@@ -555,17 +455,6 @@ def _sptrsm_args(A, X, uplo, diag, fpe, early_exit):
         raise ValueError(f"exsptrsm: the rows of X overlap: stride(0) = {X.stride(0)} < k = {k}")
     _on_gpu("exsptrsm", crow=crow, col=col, val=val, X=X)
     return (u, d, m, k, bits, _ptr(crow), _ptr(col), _ptr(val), _ptr(X), int(X.stride(0)), int(fpe), int(bool(early_exit)))
-
-
-def exsptrsm_dev(A, X, uplo="L", diag="N", fpe=8, early_exit=True):
-    """ExSpTRSM: solves A X = B in place on the m x k block X (B on entry) for k right-hand sides at once, exact and
-    reproducible, stream-ordered on the current stream: column j is bit for bit what exsptrsv_dev gives on B[:, j], and
-    the matrix is paid for once per row, not once per row and column.  A as for exsptrsv_dev; X a 2-D float64 tensor
-    with stride(1) == 1 and stride(0) >= k (a view [:, :k] of a wider block is fine: its padding is not touched).
-    Returns X."""
-    args = _sptrsm_args(A, X, uplo, diag, fpe, early_exit)
-    _check(load_library().exblas_exsptrsm_csr_dev(*args, _stream_ptr(_torch())), "exsptrsm_dev")
-    return X
 
 
 def set_sptrsm_path(mode):
@@ -607,16 +496,6 @@ def _spmm_args(A, X, Y, alpha, beta, fpe, early_exit):
         Y = _torch().zeros((m, k), dtype=X.dtype, device=X.device)
     return Y, (m, n, k, bits, _ptr(crow), _ptr(col), _ptr(val), float(alpha), _ptr(X), _ld(X, k), float(beta), _ptr(Y),
                _ld(Y, k), int(fpe), int(bool(early_exit)))
-
-
-def exspmm_dev(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
-    """ExSpMM: Y = Round(alpha A X + beta Y) output by output, exact and reproducible, stream-ordered on the current
-    stream; column j is bit for bit exspmv_dev(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_dev; X a 2-D float64
-    tensor with at least n rows (row-major: a copy is made when X.stride(1) != 1, otherwise ldx = X.stride(0)); Y (m x k,
-    stride(1) == 1, stride(0) >= k) is updated in place, or allocated (zeros) when None."""
-    Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
-    _check(load_library().exblas_exspmm_csr_dev(*args, _stream_ptr(_torch())), "exspmm_dev")
-    return Y
 
 
 def set_spmm_path(mode):
@@ -734,39 +613,6 @@ def _bdot_round_args(sets, mode, p, q, out):
     return out, (mode.encode(), p, q, _ptr(sets), nsets, _ptr(out), ldc)
 
 
-def exbdot_dev(X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
-    """ExBDOT: exact, reproducible inner products of the columns of two row-major blocks, stream-ordered on the current
-    stream, both blocks read once.  mode 'G': out[i, j] = Round(sum_r X[r, i] Y[r, j]) (p x q); mode 'D' (p == q):
-    out[j] = Round(sum_r X[r, j] Y[r, j]).  Every output is bit for bit what exdot_dev gives for the two columns.  X and
-    Y are 2-D float64 tensors with stride(1) == 1 and stride(0) >= their column count (a view [:, :k] of a wider block is
-    fine; anything else is refused, not copied) and equal row counts; Y=None means Y = X.  `out` is allocated when None,
-    otherwise checked; it is returned."""
-    out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
-    _check(load_library().exblas_exbdot_dev(*args, _stream_ptr(_torch())), "exbdot_dev")
-    return out
-
-
-def exbdot_export_dev(X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
-    """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
-    [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
-    shard's products as 68 normalised base-2^32 digits under a signed top digit, three 0 / 1 indicators (+Inf, -Inf, NaN
-    seen) and a zero word.  Sets of different shards add as plain int64; exbdot_round_dev rounds the sum.  fpe == 1 and
-    early_exit with fpe > 8 are refused: they have no digit sets."""
-    sets, args = _bdot_export_args(X, Y, mode, sets, fpe, early_exit)
-    _check(load_library().exblas_exbdot_export_dev(*args, _stream_ptr(_torch())), "exbdot_export_dev")
-    return sets
-
-
-def exbdot_round_dev(sets, mode, p, q, out=None):
-    """Second half: `sets` is a contiguous int64 tensor [outputs, 72] or [nsets, outputs, 72] (the exports of nsets shards
-    stacked, or a sum of exports); the nsets copies of every output are added and rounded once, under the current
-    rounding mode, into `out` (as for exbdot_dev: p x q in mode 'G', p in mode 'D'; allocated when None).  Bit for bit
-    exbdot_dev on the rows of all shards together.  `sets` is only read."""
-    out, args = _bdot_round_args(sets, mode, p, q, out)
-    _check(load_library().exblas_exbdot_round_dev(*args, _stream_ptr(_torch())), "exbdot_round_dev")
-    return out
-
-
 def set_bdot_path(mode):
     """Test hook: 0 automatic, 1 the smallest row slab per workgroup, 2 column panels and output tiles of width 4.
     Same bits on every path."""
@@ -775,8 +621,10 @@ def set_bdot_path(mode):
 
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
-    enqueued through different contexts (on different streams) needs no ordering.  Methods mirror the ``*_dev``
-    functions; tensors are CUDA float64 / int64 on the context's device, calls go to the CURRENT torch stream."""
+    enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
+    the context's device, calls go to the CURRENT torch stream.  Every routine with a handle form is implemented here,
+    once; the module's ``*_dev`` functions are these methods bound to the context whose handle is None, the device's
+    default context (``exblas_X_ctx(NULL, ...)`` is exactly ``exblas_X_dev(...)``)."""
 
     def __init__(self):
         _require_gpu()
@@ -796,98 +644,156 @@ class Context:
             pass
 
     def exsum(self, x, fpe=8, early_exit=True, inca=1, n=None, out=None):
+        """ExSUM of a CUDA float64 tensor, stream-ordered; returns the int64 record tensor (on device)."""
         torch = _require_gpu()
+        assert x.is_cuda and x.dtype == torch.float64
         if n is None:
             n = (x.numel() + inca - 1) // inca
         if out is None:
             out = new_record_buffer()
         _check(load_library().exblas_exsum_ctx(self.handle, C.c_void_p(x.data_ptr()), n, inca, fpe, int(early_exit),
-                                               _stream_ptr(torch), C.c_void_p(out.data_ptr())), "exsum_ctx")
+                                               _stream_ptr(torch), C.c_void_p(out.data_ptr())), "exsum")
         return out
 
-    def exdot(self, x, y, fpe=8, early_exit=True, out=None):
+    def exdot(self, x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None, out=None):
         torch = _require_gpu()
+        assert x.is_cuda and y.is_cuda and x.dtype == torch.float64 and y.dtype == torch.float64
+        if n is None:
+            n = (x.numel() + incx - 1) // incx
         if out is None:
             out = new_record_buffer()
-        _check(load_library().exblas_exdot_ctx(self.handle, C.c_void_p(x.data_ptr()), 1, C.c_void_p(y.data_ptr()), 1,
-                                               x.numel(), fpe, int(early_exit), _stream_ptr(torch),
-                                               C.c_void_p(out.data_ptr())), "exdot_ctx")
+        _check(load_library().exblas_exdot_ctx(self.handle, C.c_void_p(x.data_ptr()), incx, C.c_void_p(y.data_ptr()), incy,
+                                               n, fpe, int(early_exit), _stream_ptr(torch), C.c_void_p(out.data_ptr())),
+               "exdot")
         return out
 
-    def exsum_accumulate(self, x, fpe=8, early_exit=True):
+    def exsum_accumulate(self, x, fpe=8, early_exit=True, inca=1, n=None):
+        """Phase 1 only: stream x into the context accumulators (several calls fold into one exact sum)."""
         torch = _require_gpu()
-        _check(load_library().exblas_exsum_accumulate_ctx(self.handle, C.c_void_p(x.data_ptr()), x.numel(), 1, fpe,
-                                                          int(early_exit), _stream_ptr(torch)), "exsum_accumulate_ctx")
+        if n is None:
+            n = (x.numel() + inca - 1) // inca
+        _check(load_library().exblas_exsum_accumulate_ctx(self.handle, C.c_void_p(x.data_ptr()), n, inca, fpe,
+                                                          int(early_exit), _stream_ptr(torch)), "exsum_accumulate")
+
+    def exdot_accumulate(self, x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None):
+        torch = _require_gpu()
+        if n is None:
+            n = (x.numel() + incx - 1) // incx
+        _check(load_library().exblas_exdot_accumulate_ctx(self.handle, C.c_void_p(x.data_ptr()), incx,
+                                                          C.c_void_p(y.data_ptr()), incy, n, fpe, int(early_exit),
+                                                          _stream_ptr(torch)), "exdot_accumulate")
 
     def finish(self, out=None):
+        """Phase 2: carry-propagate + round the context accumulators into a record; zeroes them."""
         torch = _require_gpu()
         if out is None:
             out = new_record_buffer()
-        _check(load_library().exblas_finish_ctx(self.handle, _stream_ptr(torch), C.c_void_p(out.data_ptr())),
-               "finish_ctx")
+        _check(load_library().exblas_finish_ctx(self.handle, _stream_ptr(torch), C.c_void_p(out.data_ptr())), "finish")
         return out
 
     def exgemv(self, trans, m, n, alpha, a, lda, x, beta, y, fpe=0, early_exit=False, incx=1, incy=1):
         torch = _require_gpu()
         _check(load_library().exblas_exgemv_ctx(self.handle, trans.encode(), m, n, alpha, C.c_void_p(a.data_ptr()), lda,
                                                 C.c_void_p(x.data_ptr()), incx, beta, C.c_void_p(y.data_ptr()), incy,
-                                                fpe, int(early_exit), _stream_ptr(torch)), "exgemv_ctx")
+                                                fpe, int(early_exit), _stream_ptr(torch)), "exgemv")
         return y
+
+    def extrsv(self, uplo, trans, diag, n, a, lda, x, fpe=0, early_exit=False, incx=1):
+        """x := A^-1 x (or A^-T x) in place on device tensors; returns 0, or -1 for the unsupported fpe >= 9."""
+        torch = _require_gpu()
+        rc = load_library().exblas_extrsv_ctx(self.handle, uplo.encode(), trans.encode(), diag.encode(), n,
+                                              C.c_void_p(a.data_ptr()), lda, C.c_void_p(x.data_ptr()), incx, fpe,
+                                              int(early_exit), _stream_ptr(torch))
+        if rc != -1:
+            _check(rc, "extrsv")
+        return rc
 
     def exgemm(self, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe=0, early_exit=False):
         torch = _require_gpu()
         _check(load_library().exblas_exgemm_ctx(self.handle, transa.encode(), transb.encode(), m, n, k, alpha,
                                                 C.c_void_p(a.data_ptr()), lda, C.c_void_p(b.data_ptr()), ldb, beta,
                                                 C.c_void_p(c.data_ptr()), ldc, fpe, int(early_exit),
-                                                _stream_ptr(torch)), "exgemm_ctx")
+                                                _stream_ptr(torch)), "exgemm")
         return c
 
-    def extrsv(self, uplo, trans, diag, n, a, lda, x, fpe=0, early_exit=False, incx=1):
-        torch = _require_gpu()
-        rc = load_library().exblas_extrsv_ctx(self.handle, uplo.encode(), trans.encode(), diag.encode(), n,
-                                              C.c_void_p(a.data_ptr()), lda, C.c_void_p(x.data_ptr()), incx, fpe,
-                                              int(early_exit), _stream_ptr(torch))
-        if rc != -1:
-            _check(rc, "extrsv_ctx")
-        return rc
-
     def exspmv(self, A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+        """ExSpMV: y = Round(alpha A x + beta y) row by row, exact and reproducible, stream-ordered on the current stream.
+        A: torch.sparse_csr_tensor (float64 values, int32 or int64 indices) or (crow, col, val, (m, n)) on the GPU; x a
+        float64 vector of at least n entries; y (m entries) is updated in place, or allocated (zeros) when None."""
         y, args = _spmv_args(A, x, y, alpha, beta, fpe, early_exit)
-        _check(load_library().exblas_exspmv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmv_ctx")
+        _check(load_library().exblas_exspmv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmv")
         return y
 
+    def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+        """ExSpMM: Y = Round(alpha A X + beta Y) output by output, exact and reproducible, stream-ordered on the current
+        stream; column j is bit for bit exspmv_dev(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_dev; X a 2-D float64
+        tensor with at least n rows (row-major: a copy is made when X.stride(1) != 1, otherwise ldx = X.stride(0)); Y (m x k,
+        stride(1) == 1, stride(0) >= k) is updated in place, or allocated (zeros) when None."""
+        Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
+        _check(load_library().exblas_exspmm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmm")
+        return Y
+
     def exsptrsv(self, A, x, uplo="L", diag="N", fpe=8, early_exit=True):
+        """ExSpTRSV: solves A x = b in place on x (b on entry), exact and reproducible, stream-ordered on the current stream:
+        x_i = Round(b_i - sum of the stored val * x_j before the diagonal) / d_i in substitution order (diag 'U': no division),
+        bit for bit what extrsv_dev gives on the densified matrix.  A: square torch.sparse_csr_tensor or (crow, col, val,
+        (m, m)) on the GPU (float64 values, int32 or int64 indices); entries of the other triangle are skipped.  Returns x."""
         args = _sptrsv_args(A, x, uplo, diag, fpe, early_exit)
-        _check(load_library().exblas_exsptrsv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsv_ctx")
+        _check(load_library().exblas_exsptrsv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsv")
         return x
 
     def exsptrsm(self, A, X, uplo="L", diag="N", fpe=8, early_exit=True):
+        """ExSpTRSM: solves A X = B in place on the m x k block X (B on entry) for k right-hand sides at once, exact and
+        reproducible, stream-ordered on the current stream: column j is bit for bit what exsptrsv_dev gives on B[:, j], and
+        the matrix is paid for once per row, not once per row and column.  A as for exsptrsv_dev; X a 2-D float64 tensor
+        with stride(1) == 1 and stride(0) >= k (a view [:, :k] of a wider block is fine: its padding is not touched).
+        Returns X."""
         args = _sptrsm_args(A, X, uplo, diag, fpe, early_exit)
-        _check(load_library().exblas_exsptrsm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsm_ctx")
+        _check(load_library().exblas_exsptrsm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exsptrsm")
         return X
 
-    def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
-        Y, args = _spmm_args(A, X, Y, alpha, beta, fpe, early_exit)
-        _check(load_library().exblas_exspmm_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmm_ctx")
-        return Y
-
     def exbdot(self, X, Y=None, mode="G", out=None, fpe=8, early_exit=True):
+        """ExBDOT: exact, reproducible inner products of the columns of two row-major blocks, stream-ordered on the current
+        stream, both blocks read once.  mode 'G': out[i, j] = Round(sum_r X[r, i] Y[r, j]) (p x q); mode 'D' (p == q):
+        out[j] = Round(sum_r X[r, j] Y[r, j]).  Every output is bit for bit what exdot_dev gives for the two columns.  X and
+        Y are 2-D float64 tensors with stride(1) == 1 and stride(0) >= their column count (a view [:, :k] of a wider block is
+        fine; anything else is refused, not copied) and equal row counts; Y=None means Y = X.  `out` is allocated when None,
+        otherwise checked; it is returned."""
         out, args = _bdot_args(X, Y, mode, out, fpe, early_exit)
-        _check(load_library().exblas_exbdot_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_ctx")
+        _check(load_library().exblas_exbdot_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot")
         return out
 
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
+        """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
+        [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
+        shard's products as 68 normalised base-2^32 digits under a signed top digit, three 0 / 1 indicators (+Inf, -Inf, NaN
+        seen) and a zero word.  Sets of different shards add as plain int64; exbdot_round_dev rounds the sum.  fpe == 1 and
+        early_exit with fpe > 8 are refused: they have no digit sets."""
         sets, args = _bdot_export_args(X, Y, mode, sets, fpe, early_exit)
-        _check(load_library().exblas_exbdot_export_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_export_ctx")
+        _check(load_library().exblas_exbdot_export_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_export")
         return sets
 
     def exbdot_round(self, sets, mode, p, q, out=None):
+        """Second half: `sets` is a contiguous int64 tensor [outputs, 72] or [nsets, outputs, 72] (the exports of nsets shards
+        stacked, or a sum of exports); the nsets copies of every output are added and rounded once, under the current
+        rounding mode, into `out` (as for exbdot_dev: p x q in mode 'G', p in mode 'D'; allocated when None).  Bit for bit
+        exbdot_dev on the rows of all shards together.  `sets` is only read."""
         out, args = _bdot_round_args(sets, mode, p, q, out)
-        _check(load_library().exblas_exbdot_round_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_round_ctx")
+        _check(load_library().exblas_exbdot_round_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot_round")
         return out
 
     def workspace_bytes(self):
         return load_library().exblas_workspace_bytes_ctx(self.handle)
+
+
+# The device's default context: no handle, so nothing is created (importing needs no GPU) and destroy() does nothing.
+_default = object.__new__(Context)
+_default.handle = None
+exsum_dev, exdot_dev, finish_dev = _default.exsum, _default.exdot, _default.finish
+exsum_accumulate_dev, exdot_accumulate_dev = _default.exsum_accumulate, _default.exdot_accumulate
+exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.exgemm
+exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
+exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
 
 
 def gen_dev(kind, n, seed=1, p0=0.0, p1=0.0, first=0, count=None, n_total=None, out=None):

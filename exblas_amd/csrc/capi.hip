@@ -1,13 +1,17 @@
-// capi.hip -- context, generators and the C ABI / C++ API of libexblas.so (see include/exblas_hip.h).
-//
-// The C++ functions exsum/exdot/exgemv/exgemm at the bottom carry the exact signatures of the
-// reference's public headers (include/blas1.hpp:48,74; blas2.hpp:57,95; blas3.hpp:56) and replace
-// src/gpu/blas/blas{1,2,3}/Ex*.cpp: same argument meaning, same variant dispatch, same error
-// behaviour (print + exit on fpe < 0 or device failure, 0.0 for Ng <= 0 / unsupported variants).
-//
-// Each routine has one implementation on an explicit context (the *_on functions); the *_dev, *_ctx and host-pointer
-// entry points are thin layers over it.  The two CSR routines share their argument checks (csr_check_args) and their
-// host-pointer path (csr_host_call); the per-device knobs and the workspace release go through for_each_layer.
+// capi.hip -- the contexts and everything of the C ABI / C++ API of libexblas.so (include/exblas_hip.h) that runs on one:
+//   1. context lifecycle: the static per-device contexts (layer 0 for the device-pointer entries, layers 1.. for the
+//      host-pointer layer), caller-owned handles, staging buffers and the workspace, the knobs and the last_*_info queries;
+//   2. one implementation per routine on an explicit context (the *_on functions: argument checks, the context's lock,
+//      the dispatch of blas1.hip ... bdot.hip);
+//   3. the device-pointer ABI: exblas_X_ctx(handle, ...) resolves the handle (NULL: the device's default context) and
+//      calls X_on; exblas_X_dev(...) is exblas_X_ctx(NULL, ...);
+//   4. the host-pointer layer: ExSUM / ExDOT spread over the GPUs of the node (host_reduce), every other routine staged
+//      through one private context (HostCall: copy in, one X_on call, copy out);
+//   5. the C++ functions exsum/exdot/exgemv/extrsv/exgemm with the exact signatures of the reference's public headers
+//      (include/blas1.hpp:48,74; blas2.hpp:57,95; blas3.hpp:56), which replace src/gpu/blas/blas{1,2,3}/Ex*.cpp: same
+//      argument meaning, same variant dispatch, same error behaviour (print + exit on fpe < 0 or device failure, 0.0
+//      for Ng <= 0 / unsupported variants).
+// The generator and the bandwidth probes are in probes.hip, the multi-rank forms in comm.hip.
 #include "../../include/exblas_hip.h"
 #include "../../include/blas1.hpp"
 #include "../../include/blas2.hpp"
@@ -68,6 +72,15 @@ static int current_device()
     return d < MAX_DEV ? d : 0;
 }
 
+// (re)allocates the two accumulator sets of a context for its c.ngroups, zeroed; the caller has set the device
+static void alloc_accumulators(Ctx &c)
+{
+    if (c.gacc_all) EXB_CHECK(hipFree(c.gacc_all));
+    EXB_CHECK(hipMalloc(&c.gacc_all, 2 * sizeof(long long) * NL * c.ngroups));
+    EXB_CHECK(hipMemset(c.gacc_all, 0, 2 * sizeof(long long) * NL * c.ngroups));
+    c.gacc = c.gacc_all + (size_t)c.slot * NL * c.ngroups;
+}
+
 // creates the device objects of a context (accumulators, flags, record buffers, stream) on `device`; knobs come from the
 // environment, then from the device's layer-0 context when that exists (what the API has set so far)
 static void init_ctx(Ctx &c, int device, int layer)
@@ -88,29 +101,15 @@ static void init_ctx(Ctx &c, int device, int layer)
     c.grid_adj = env_int("EXBLAS_GRID_ADJ", 0);
     if (c.ngroups < 1) c.ngroups = 1;
     c.gemm_path = env_int("EXBLAS_GEMM_PATH", 0);
-    if (layer > 0 && g_ctx[0][device].device >= 0) {  // knobs set through the API so far apply to every layer
-        const Ctx &z = g_ctx[0][device];
-        c.blocks_per_cu = z.blocks_per_cu; c.bpc_sum = z.bpc_sum; c.bpc_dot = z.bpc_dot; c.bpc_sa = z.bpc_sa;
-        c.bpc_heavy = z.bpc_heavy;
-        c.grid_adj = z.grid_adj;
-        c.ngroups = z.ngroups; c.gemm_path = z.gemm_path;
-        c.spmv_path = z.spmv_path;
-        c.spmm_path = z.spmm_path;
-        c.sptrsv_path = z.sptrsv_path;
-        c.sptrsm_path = z.sptrsm_path;
-        c.bdot_path = z.bdot_path;
-        c.gemm_max_slices = z.gemm_max_slices;
-        c.gemm_max_moduli = z.gemm_max_moduli;
-    }
+    // knobs set through the API so far apply to every layer
+    if (layer > 0 && g_ctx[0][device].device >= 0) static_cast<CtxKnobs &>(c) = g_ctx[0][device];
     EXB_CHECK(crt_tables_upload());
-    EXB_CHECK(hipMalloc(&c.gacc_all, 2 * sizeof(long long) * NL * c.ngroups));
-    EXB_CHECK(hipMemset(c.gacc_all, 0, 2 * sizeof(long long) * NL * c.ngroups));
+    c.slot = 0;
+    alloc_accumulators(c);
     // per slot: the flag word (own 64-byte line) + the low and high accumulators of ExDOT (superacc.hip.h: low_acc_of, high_acc_of)
     EXB_CHECK(hipMalloc(&c.gflags_all, 2 * FLAG_BLOCK_BYTES));
     EXB_CHECK(hipMemset(c.gflags_all, 0, 2 * FLAG_BLOCK_BYTES));
-    c.gacc = c.gacc_all;
     c.gflags = c.gflags_all;
-    c.slot = 0;
     EXB_CHECK(hipMalloc(&c.d_record, sizeof(long long) * OUT_WORDS));
     // portable: the record of one device's part is copied to the first device when a host call spans several
     EXB_CHECK(hipHostMalloc(&c.h_record, sizeof(long long) * OUT_WORDS, hipHostMallocPortable));
@@ -204,137 +203,6 @@ void *workspace(Ctx &c, size_t bytes, hipStream_t st, hipError_t *err)
     return c.ws;
 }
 
-// ---------------------------------------------------------------------------------------------
-// counter-based generators: the device twin of oracle/exblas_oracle.c:orc_gen_one (integer math,
-// exact conversions and power-of-two scalings only, so the bits are identical on CPU and GPU)
-// ---------------------------------------------------------------------------------------------
-__host__ __device__ inline unsigned long long mix64(unsigned long long z)
-{
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline unsigned long long rnd(unsigned long long seed, unsigned long long i, unsigned long long k)
-{
-    return mix64(seed * 0xD1342543DE82EF95ull + (2 * i + k + 1) * 0x9E3779B97F4A7C15ull);
-}
-__device__ inline double pow2i(int e) { return __longlong_as_double((long long)(e + 1023) << 52); }
-__device__ inline double mant12(unsigned long long r)
-{
-    return __longlong_as_double((long long)(0x3FF0000000000000ull | (r >> 12)));
-}
-__device__ inline double mant_signed(unsigned long long r)
-{
-    long long k = (long long)(r >> 11);
-    return (double)(2 * k - (1ll << 53)) * 0x1p-53;
-}
-__device__ inline unsigned uni(unsigned long long r, unsigned range)
-{
-    return (unsigned)(((r >> 32) * (unsigned long long)range) >> 32);
-}
-
-__global__ void __launch_bounds__(256) k_gen(int kind, unsigned long long seed, long long first, long long count,
-                                             long long n, int i0, int i1, double dscale, double *out)
-{
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < count;
-         t += (long long)gridDim.x * blockDim.x) {
-        const long long i = first + t;
-        const unsigned long long r0 = rnd(seed, (unsigned long long)i, 0), r1 = rnd(seed, (unsigned long long)i, 1);
-        double v = 0.0;
-        switch (kind) {
-        case EXBLAS_GEN_NAIVE: v = 1.1; break;
-        case EXBLAS_GEN_FPUNIFORM:
-        case EXBLAS_GEN_FPUNIFORM_SIGNED: {
-            int e = i1 - i0 + (i0 > 0 ? (int)uni(r1, (unsigned)i0) : 0);
-            v = mant12(r0) * pow2i(e);
-            if (kind == EXBLAS_GEN_FPUNIFORM_SIGNED && (r1 & 1)) v = -v;
-            break;
-        }
-        case EXBLAS_GEN_LOGNORMAL: {
-            long long z = (long long)(r1 & 0xffff) + (long long)((r1 >> 16) & 0xffff) +
-                          (long long)((r1 >> 32) & 0xffff) + (long long)((r1 >> 48) & 0xffff) - 2 * 65535;
-            int e = (int)rint((double)z * dscale) + i0;
-            e = e > 1000 ? 1000 : (e < -1000 ? -1000 : e);
-            v = mant12(r0) * pow2i(e);
-            break;
-        }
-        case EXBLAS_GEN_ILLCOND: {
-            const int bh = i0;
-            const long long n2 = n / 2;
-            int e;
-            if (i < n2) e = (i == 0) ? bh + 1 : (int)uni(r1, (unsigned)(bh + 1));
-            else e = (n - n2 > 0) ? (int)(((i - n2) * (long long)bh) / (n - n2)) : 0;
-            v = mant_signed(r0) * pow2i(e);
-            break;
-        }
-        case EXBLAS_GEN_CANCEL: {
-            const long long h = n / 2;
-            if (i >= 2 * h) v = 0.0;
-            else if (i == h - 1) v = 1.0;
-            else if (i == 2 * h - 1) v = 0x1p-60;
-            else {
-                const long long j = (i < h) ? i : i - h;
-                const unsigned long long q0 = rnd(seed, (unsigned long long)j, 0),
-                                         q1 = rnd(seed, (unsigned long long)j, 1);
-                double w = mant_signed(q0) * pow2i(i0 > 0 ? (int)uni(q1, (unsigned)i0) : 0);
-                v = (i < h) ? w : -w;
-            }
-            break;
-        }
-        default: break;
-        }
-        out[t] = v;
-    }
-}
-
-// plain (inexact) streaming sum: read-bandwidth probe
-typedef double d2_t __attribute__((ext_vector_type(2)));
-__global__ void __launch_bounds__(256) k_stream_read(const double *a, long long n, double *sink)
-{
-    const d2_t *v = (const d2_t *)a;
-    const long long nv = n >> 1;
-    double s0 = 0, s1 = 0;
-    constexpr int U = 4;
-    const long long tile = 256ll * U, ntiles = nv / tile;
-    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const d2_t *p = v + t * tile + threadIdx.x;
-        d2_t r[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) r[u] = __builtin_nontemporal_load(p + u * 256);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            s0 += r[u].x;
-            s1 += r[u].y;
-        }
-    }
-    if (s0 + s1 == 0x1.23456789abcdep-333) *sink = s0;  // keeps the loads alive, never true in practice
-}
-
-// plain (inexact) two-stream dot: read-bandwidth probe for the ExDOT access pattern
-__global__ void __launch_bounds__(256) k_stream_read2(const double *a, const double *b, long long n, double *sink)
-{
-    const d2_t *va = (const d2_t *)a, *vb = (const d2_t *)b;
-    const long long nv = n >> 1;
-    double s0 = 0, s1 = 0;
-    constexpr int U = 4;
-    const long long tile = 256ll * U, ntiles = nv / tile;
-    for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
-        const long long base = t * tile + threadIdx.x;
-        d2_t r[U], q[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            r[u] = __builtin_nontemporal_load(va + base + u * 256);
-            q[u] = __builtin_nontemporal_load(vb + base + u * 256);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            s0 += r[u].x * q[u].x;
-            s1 += r[u].y * q[u].y;
-        }
-    }
-    if (s0 + s1 == 0x1.23456789abcdep-333) *sink = s0;
-}
-
 }  // namespace exb
 
 using namespace exb;
@@ -370,11 +238,8 @@ int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant)
         if (blocks_per_cu > 0) c.blocks_per_cu = c.bpc_sum = c.bpc_dot = c.bpc_sa = c.bpc_heavy = blocks_per_cu;
         if (ngroups > 0 && ngroups != c.ngroups) {
             EXB_CHECK(hipDeviceSynchronize());
-            EXB_CHECK(hipFree(c.gacc_all));
             c.ngroups = ngroups;
-            EXB_CHECK(hipMalloc(&c.gacc_all, 2 * sizeof(long long) * NL * c.ngroups));
-            EXB_CHECK(hipMemset(c.gacc_all, 0, 2 * sizeof(long long) * NL * c.ngroups));
-            c.gacc = c.gacc_all + (size_t)c.slot * NL * c.ngroups;
+            alloc_accumulators(c);
             EXB_CHECK(hipDeviceSynchronize());
         }
     });
@@ -444,9 +309,16 @@ void exblas_set_gemm_max_slices(int s) { for_each_layer([&](Ctx &c) { c.gemm_max
 void exblas_set_gemm_max_moduli(int l) { for_each_layer([&](Ctx &c) { c.gemm_max_moduli = l; }); }
 void exblas_set_gemm_path(int mode) { for_each_layer([&](Ctx &c) { c.gemm_path = mode; }); }
 
-static int sparse_path(int mode) { return (mode >= 0 && mode <= 3) ? mode : 0; }
-void exblas_set_spmv_path(int mode) { for_each_layer([&](Ctx &c) { c.spmv_path = sparse_path(mode); }); }
-void exblas_set_spmm_path(int mode) { for_each_layer([&](Ctx &c) { c.spmm_path = sparse_path(mode); }); }
+// a path knob of every context of the device: `mode` in [0, largest], anything else means 0 (automatic)
+static void set_path(int CtxKnobs::*knob, int mode, int largest)
+{
+    for_each_layer([&](Ctx &c) { c.*knob = (mode >= 0 && mode <= largest) ? mode : 0; });
+}
+void exblas_set_spmv_path(int mode) { set_path(&CtxKnobs::spmv_path, mode, 3); }
+void exblas_set_spmm_path(int mode) { set_path(&CtxKnobs::spmm_path, mode, 3); }
+void exblas_set_sptrsv_path(int mode) { set_path(&CtxKnobs::sptrsv_path, mode, 2); }
+void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3); }
+void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -459,41 +331,42 @@ static int sparse_header(const long long *info_dev, long long (&h)[8])
     return -1;
 }
 
+// what the last solve of a context (its lock held) has to report, h receiving its header: 0, EXBLAS_SPTRSV_STALLED when
+// that call's watchdog was raised, or the error of reading the header
+static int solve_status(const long long *info_dev, long long (&h)[8])
+{
+    if (int e = sparse_header(info_dev, h)) return e;
+    return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
+}
+
 // The four counters of the last sparse call on the last-used layer.  ExSpMV / ExSpMM: -1 when there was no call.  The two
 // solves (`solve`): a call that launched nothing counts zeros; EXBLAS_SPTRSV_STALLED when that call's watchdog was raised.
-static int last_sparse_info(const long long *Ctx::*info_dev, bool solve, int64_t *out4)
+static int last_sparse_info(const long long *CtxWsPtrs::*info_dev, bool solve, int64_t *out4)
 {
     if (!out4) return (int)hipErrorInvalidValue;
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
     std::lock_guard<std::mutex> lk(c.mu);
     long long h[8];
-    const int rc = sparse_header(c.*info_dev, h);
+    const int rc = solve ? solve_status(c.*info_dev, h) : sparse_header(c.*info_dev, h);
     for (int i = 0; i < 4; ++i) out4[i] = h[4 + i];
-    if (rc || (!solve && !(c.*info_dev))) return -1;
-    return (solve && h[1]) ? EXBLAS_SPTRSV_STALLED : 0;
+    return (!solve && !(c.*info_dev)) ? -1 : rc;   // (rc: 0, -1 when the header could not be read, or the solve's status)
 }
 
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows split across workgroups,
 // out[3] chunks of the split rows
-int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&Ctx::spmv_info_dev, false, out4); }
+int exblas_last_spmv_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::spmv_info_dev, false, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from an accumulator, out[2] rows split across workgroups,
 // out[3] chunks of the split rows
-int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&Ctx::spmm_info_dev, false, out4); }
-
-void exblas_set_sptrsv_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsv_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
-
-void exblas_set_sptrsm_path(int mode) { for_each_layer([&](Ctx &c) { c.sptrsm_path = sparse_path(mode); }); }
-
-void exblas_set_bdot_path(int mode) { for_each_layer([&](Ctx &c) { c.bdot_path = (mode >= 0 && mode <= 2) ? mode : 0; }); }
+int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::spmm_info_dev, false, out4); }
 
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
-int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&Ctx::sptrsv_info_dev, true, out4); }
+int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::sptrsv_info_dev, true, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
-int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&Ctx::sptrsm_info_dev, true, out4); }
+int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::sptrsm_info_dev, true, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -583,12 +456,10 @@ static int bdot_check_args(char mode, int64_t n, int p, int q, const double *x, 
     return 0;
 }
 
+// (the arguments of the two below were checked by their callers, before those needed a context)
 static int exbdot_on(Ctx &c, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
                      int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, hipStream_t st)
 {
-    bool empty;
-    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
-    if (rc || empty) return rc;
     std::lock_guard<std::mutex> lk(c.mu);
     return (int)exbdot_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, round_mode(), st);
 }
@@ -607,9 +478,6 @@ static int bdot_export_check(char mode, int64_t n, int p, int q, const double *x
 static int exbdot_export_on(Ctx &c, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
                             int64_t ldy, int64_t *d_sets, int fpe, int early_exit, hipStream_t st)
 {
-    bool empty;
-    const int rc = bdot_export_check(mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, &empty);
-    if (rc || empty) return rc;
     std::lock_guard<std::mutex> lk(c.mu);
     return exbdot_export_dispatch(c, mode, n, p, q, d_x, ldx, d_y, ldy, (long long *)d_sets, fpe, early_exit, st);
 }
@@ -672,33 +540,6 @@ static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, doub
                                 early_exit, round_mode(), st, chunks);
 }
 
-int exblas_exsum_accumulate_dev(const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream)
-{
-    return exsum_accumulate_on(ctx(-1), d_a, n, inca, fpe, early_exit, (hipStream_t)stream);
-}
-
-int exblas_exdot_accumulate_dev(const double *d_a, int64_t inca, const double *d_b, int64_t incb, int64_t n, int fpe,
-                                int early_exit, void *stream)
-{
-    return exdot_accumulate_on(ctx(-1), d_a, inca, d_b, incb, n, fpe, early_exit, (hipStream_t)stream);
-}
-
-int exblas_finish_dev(void *stream, int64_t *d_out) { return finish_on(ctx(-1), (hipStream_t)stream, d_out); }
-
-int exblas_exsum_dev(const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream,
-                     int64_t *d_out)
-{
-    int rc = exblas_exsum_accumulate_dev(d_a, n, inca, fpe, early_exit, stream);
-    return rc ? rc : exblas_finish_dev(stream, d_out);
-}
-
-int exblas_exdot_dev(const double *d_a, int64_t inca, const double *d_b, int64_t incb, int64_t n, int fpe,
-                     int early_exit, void *stream, int64_t *d_out)
-{
-    int rc = exblas_exdot_accumulate_dev(d_a, inca, d_b, incb, n, fpe, early_exit, stream);
-    return rc ? rc : exblas_finish_dev(stream, d_out);
-}
-
 int exblas_exsum_segmented_dev(const double *d_values, const int64_t *d_offsets, int64_t nseg, int fpe, int early_exit,
                                void *stream, double *d_out)
 {
@@ -715,79 +556,6 @@ int exblas_finalize_dev(const int64_t *d_digit_sets, int nsets, uint32_t flags_o
                               (long long *)d_out);
 }
 
-int exblas_exgemv_dev(char transa, int m, int n, double alpha, const double *d_a, int lda, const double *d_x,
-                      int incx, double beta, double *d_y, int incy, int fpe, int early_exit, void *stream)
-{
-    return exgemv_on(ctx(-1), transa, m, n, alpha, d_a, lda, d_x, incx, beta, d_y, incy, fpe, early_exit,
-                     (hipStream_t)stream);
-}
-
-int exblas_exspmv_csr_dev(int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx,
-                          const double *d_val, double alpha, const double *d_x, double beta, double *d_y, int fpe,
-                          int early_exit, void *stream)
-{
-    return exspmv_on(ctx(-1), m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe, early_exit,
-                     (hipStream_t)stream);
-}
-
-int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
-                          const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
-                          int64_t ldy, int fpe, int early_exit, void *stream)
-{
-    return exspmm_on(ctx(-1), m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
-                     early_exit, (hipStream_t)stream);
-}
-
-int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
-                      double *d_c, int64_t ldc, int fpe, int early_exit, void *stream)
-{
-    bool empty;   // refused, or nothing to do, before a context (and with it a device) is needed
-    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
-    if (rc || empty) return rc;
-    return exbdot_on(ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
-}
-
-int exblas_exbdot_export_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
-                             int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream)
-{
-    bool empty;   // refused, or nothing to do, before a context (and with it a device) is needed
-    const int rc = bdot_export_check(mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, &empty);
-    if (rc || empty) return rc;
-    return exbdot_export_on(ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, (hipStream_t)stream);
-}
-
-int exblas_exbdot_round_dev(char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c, int64_t ldc,
-                            void *stream)
-{
-    bool empty;
-    const int rc = bdot_round_check(mode, p, q, d_sets, nsets, d_c, ldc, &empty);
-    if (rc || empty) return rc;
-    ctx(-1);
-    return (int)exbdot_round_dispatch(mode, p, q, (const long long *)d_sets, nsets, d_c, ldc, round_mode(),
-                                      (hipStream_t)stream);
-}
-
-int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
-                            const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
-{
-    return exsptrsv_on(ctx(-1), uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
-                       (hipStream_t)stream);
-}
-
-int exblas_exsptrsm_csr_dev(char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
-                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
-                            void *stream)
-{
-    return exsptrsm_on(ctx(-1), uplo, diag, m, k, index_bits, d_row_ptr, d_col_idx, d_val, d_x, ldx, fpe, early_exit,
-                       (hipStream_t)stream);
-}
-
-int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x, int incx,
-                      int fpe, int early_exit, void *stream)
-{
-    return extrsv_on(ctx(-1), uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, (hipStream_t)stream);
-}
-
 int exblas_extrsv_last_slow_rows(void)
 {
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
@@ -797,14 +565,6 @@ int exblas_extrsv_last_slow_rows(void)
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     if (hipMemcpy(v, c.ws, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return v[2];
-}
-
-int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
-                      const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
-                      void *stream)
-{
-    return exgemm_on(ctx(-1), transa, transb, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, fpe, early_exit,
-                     (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -827,18 +587,18 @@ int exb::exgemm_chunked_dev(char transa, char transb, int m, int n, int k, doubl
     return exgemm_on(ctx(-1), transa, transb, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, fpe, early_exit, st,
                      chunks);
 }
-extern "C" {
 
 // ---- context handles: independent accumulators, flags and workspace per caller-owned handle --------------------
-}  // extern "C"
 struct exblas_ctx {
     exb::Ctx c;
 };
-// the handle's context; the calling thread must be on the handle's device (like any stream or buffer of that device)
+// the calling thread must be on the handle's device (like any stream or buffer of that device)
+static bool wrong_device(exblas_ctx *h) { return h && current_device() != h->c.device; }
+// the handle's context; NULL: the device's default context, created if need be
 static Ctx *handle_ctx(exblas_ctx *h)
 {
     if (!h) return &ctx(-1);
-    return current_device() == h->c.device ? &h->c : nullptr;
+    return wrong_device(h) ? nullptr : &h->c;
 }
 extern "C" {
 
@@ -948,28 +708,39 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, 
                      early_exit, (hipStream_t)stream);
 }
 
+// The three ExBDOT entries refuse bad arguments, or return 0 for an empty problem, before they need a device: the check
+// comes before the default context is created (a handle on the wrong device is still refused first).
 int exblas_exbdot_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                       const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream)
 {
-    EXB_HANDLE(h);
-    return exbdot_on(*cp, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
+    if (wrong_device(h)) return (int)hipErrorInvalidDevice;
+    bool empty;
+    const int rc = bdot_check_args(mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, &empty);
+    if (rc || empty) return rc;
+    return exbdot_on(h ? h->c : ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, (hipStream_t)stream);
 }
 
 int exblas_exbdot_export_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream)
 {
-    EXB_HANDLE(h);
-    return exbdot_export_on(*cp, mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, (hipStream_t)stream);
+    if (wrong_device(h)) return (int)hipErrorInvalidDevice;
+    bool empty;
+    const int rc = bdot_export_check(mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, &empty);
+    if (rc || empty) return rc;
+    return exbdot_export_on(h ? h->c : ctx(-1), mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit,
+                            (hipStream_t)stream);
 }
 
-// (the round uses nothing of the context: the handle is checked, and the form is there for symmetry with the export)
+// (the round uses nothing of the context: the handle is checked, and the form is there for symmetry with the export;
+// without a handle the default context is still created, so that a process without a device ends as everywhere else)
 int exblas_exbdot_round_ctx(exblas_ctx_t *h, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
                             int64_t ldc, void *stream)
 {
-    EXB_HANDLE(h);
+    if (wrong_device(h)) return (int)hipErrorInvalidDevice;
     bool empty;
     const int rc = bdot_round_check(mode, p, q, d_sets, nsets, d_c, ldc, &empty);
     if (rc || empty) return rc;
+    if (!h) ctx(-1);
     return (int)exbdot_round_dispatch(mode, p, q, (const long long *)d_sets, nsets, d_c, ldc, round_mode(),
                                       (hipStream_t)stream);
 }
@@ -1031,6 +802,85 @@ int exblas_last_gemm_info_ctx(exblas_ctx_t *h, int *out8)
 }
 #undef EXB_HANDLE
 
+// ---- the *_dev entries: the same call on the NULL handle, the device's default context -------------------------
+int exblas_exsum_accumulate_dev(const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream)
+{
+    return exblas_exsum_accumulate_ctx(nullptr, d_a, n, inca, fpe, early_exit, stream);
+}
+int exblas_exdot_accumulate_dev(const double *d_a, int64_t inca, const double *d_b, int64_t incb, int64_t n, int fpe,
+                                int early_exit, void *stream)
+{
+    return exblas_exdot_accumulate_ctx(nullptr, d_a, inca, d_b, incb, n, fpe, early_exit, stream);
+}
+int exblas_finish_dev(void *stream, int64_t *d_out) { return exblas_finish_ctx(nullptr, stream, d_out); }
+int exblas_exsum_dev(const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream, int64_t *d_out)
+{
+    return exblas_exsum_ctx(nullptr, d_a, n, inca, fpe, early_exit, stream, d_out);
+}
+int exblas_exdot_dev(const double *d_a, int64_t inca, const double *d_b, int64_t incb, int64_t n, int fpe,
+                     int early_exit, void *stream, int64_t *d_out)
+{
+    return exblas_exdot_ctx(nullptr, d_a, inca, d_b, incb, n, fpe, early_exit, stream, d_out);
+}
+int exblas_exgemv_dev(char transa, int m, int n, double alpha, const double *d_a, int lda, const double *d_x,
+                      int incx, double beta, double *d_y, int incy, int fpe, int early_exit, void *stream)
+{
+    return exblas_exgemv_ctx(nullptr, transa, m, n, alpha, d_a, lda, d_x, incx, beta, d_y, incy, fpe, early_exit, stream);
+}
+int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_a, int lda, double *d_x, int incx,
+                      int fpe, int early_exit, void *stream)
+{
+    return exblas_extrsv_ctx(nullptr, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, stream);
+}
+int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
+                      const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
+                      void *stream)
+{
+    return exblas_exgemm_ctx(nullptr, transa, transb, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, fpe, early_exit,
+                             stream);
+}
+int exblas_exspmv_csr_dev(int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                          const double *d_val, double alpha, const double *d_x, double beta, double *d_y, int fpe,
+                          int early_exit, void *stream)
+{
+    return exblas_exspmv_csr_ctx(nullptr, m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe,
+                                 early_exit, stream);
+}
+int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                          const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
+                          int64_t ldy, int fpe, int early_exit, void *stream)
+{
+    return exblas_exspmm_csr_ctx(nullptr, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy,
+                                 fpe, early_exit, stream);
+}
+int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                            const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
+{
+    return exblas_exsptrsv_csr_ctx(nullptr, uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                                   stream);
+}
+int exblas_exsptrsm_csr_dev(char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
+                            const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
+                            void *stream)
+{
+    return exblas_exsptrsm_csr_ctx(nullptr, uplo, diag, m, k, index_bits, d_row_ptr, d_col_idx, d_val, d_x, ldx, fpe,
+                                   early_exit, stream);
+}
+int exblas_exbdot_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y, int64_t ldy,
+                      double *d_c, int64_t ldc, int fpe, int early_exit, void *stream)
+{
+    return exblas_exbdot_ctx(nullptr, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, stream);
+}
+int exblas_exbdot_export_dev(char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx, const double *d_y,
+                             int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream)
+{
+    return exblas_exbdot_export_ctx(nullptr, mode, n, p, q, d_x, ldx, d_y, ldy, d_sets, fpe, early_exit, stream);
+}
+int exblas_exbdot_round_dev(char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c, int64_t ldc,
+                            void *stream)
+{
+    return exblas_exbdot_round_ctx(nullptr, mode, p, q, d_sets, nsets, d_c, ldc, stream);
+}
 int exblas_reserve_workspace(size_t bytes) { return exblas_reserve_workspace_ctx(nullptr, bytes); }
 size_t exblas_workspace_bytes(void) { return exblas_workspace_bytes_ctx(nullptr); }
 
@@ -1064,60 +914,9 @@ int exblas_release_workspace(void)
         }
         c.ws = nullptr;
         c.ws_bytes = 0;
-        c.gemm_info_dev = nullptr;  // it pointed into the workspace
-        c.spmv_info_dev = nullptr;
-        c.spmm_info_dev = nullptr;
-        c.sptrsv_info_dev = nullptr;
-        c.sptrsm_info_dev = nullptr;
+        static_cast<CtxWsPtrs &>(c) = CtxWsPtrs();  // they pointed into the workspace
     });
     return (int)first;
-}
-
-int exblas_gen_dev(int kind, uint64_t seed, int64_t first, int64_t count, int64_t n_total, double p0, double p1,
-                   double *d_out, void *stream)
-{
-    Ctx &c = ctx(-1);
-    if (count <= 0) return 0;
-    int i0 = 0, i1 = 0;
-    double dscale = 0.0;
-    switch (kind) {
-    case EXBLAS_GEN_FPUNIFORM:
-    case EXBLAS_GEN_FPUNIFORM_SIGNED: i0 = (int)p0; i1 = (int)p1; break;
-    case EXBLAS_GEN_LOGNORMAL:
-        // same expressions as orc_gen_one, evaluated on the host in IEEE double
-        dscale = p1 * (1.0 / (0.6931471805599453 * 37837.22690659431));
-        i0 = (int)rint(p0 * (1.0 / 0.6931471805599453));
-        break;
-    case EXBLAS_GEN_ILLCOND: i0 = (int)rint(log2(p0) * 0.5); break;
-    case EXBLAS_GEN_CANCEL: i0 = (int)p0; break;
-    default: break;
-    }
-    long long blocks = (count + 255) / 256;
-    long long cap = (long long)c.num_cu * 16;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(k_gen, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, kind,
-                       (unsigned long long)seed, (long long)first, (long long)count, (long long)n_total, i0, i1,
-                       dscale, d_out);
-    return (int)hipGetLastError();
-}
-
-int exblas_stream_read_dev(const double *d_a, int64_t n, void *stream, double *d_sink)
-{
-    Ctx &c = ctx(-1);
-    long long blocks = (long long)c.num_cu * c.blocks_per_cu;
-    hipLaunchKernelGGL(k_stream_read, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_a, (long long)n,
-                       d_sink);
-    return (int)hipGetLastError();
-}
-
-int exblas_stream_read2_dev(const double *d_a, const double *d_b, int64_t n, int blocks_per_cu, void *stream,
-                            double *d_sink)
-{
-    Ctx &c = ctx(-1);
-    long long blocks = (long long)c.num_cu * (blocks_per_cu > 0 ? blocks_per_cu : c.bpc_dot);
-    hipLaunchKernelGGL(k_stream_read2, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_a, d_b, (long long)n,
-                       d_sink);
-    return (int)hipGetLastError();
 }
 
 // ---- host-pointer layer ---------------------------------------------------------------------
@@ -1313,6 +1112,39 @@ static int host_reduce(long long n, const double *a, long long inca, const doubl
     return nv;
 }
 
+}  // extern "C"
+
+// One call of the host-pointer layer below (everything but ExSUM / ExDOT): the layer-1 context of the current device,
+// the process-wide lock of the layer, and the traffic around the one *_on call, which runs on the context's stream.
+struct HostCall {
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> api_lock{g_host_mu};
+    const char *who;
+    explicit HostCall(const char *name) : who(name) {}
+    void h2d(void *d, const void *h, size_t bytes)
+    {
+        if (bytes > 0) EXB_CHECK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c.stream));
+    }
+    // staging slot `slot` with room for `bytes`, the first `copy` bytes of `h` on their way into it
+    double *in(int slot, size_t bytes, const void *h, size_t copy)
+    {
+        std::lock_guard<std::mutex> lk(c.mu);
+        void *d = stage_buf(c, slot, bytes);
+        h2d(d, h, copy);
+        return (double *)d;
+    }
+    // the end of the call: dies when the routine returned rc != 0, else brings `bytes` at d back to h and waits for them
+    int out(int rc, void *h, const void *d, size_t bytes)
+    {
+        if (rc) die(who, (hipError_t)rc, __FILE__, __LINE__);
+        EXB_CHECK(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c.stream));
+        EXB_CHECK(hipStreamSynchronize(c.stream));
+        return 0;
+    }
+};
+
+extern "C" {
+
 int exblas_set_host_devices(int count, const int *devices)
 {
     std::lock_guard<std::mutex> host_lock(g_host_mu);
@@ -1370,28 +1202,17 @@ int exblas_exgemv(char transa, int m, int n, double alpha, const double *a, int 
 {
     check_fpe(fpe);
     if (m <= 0 || n <= 0) return 0;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    HostCall hc("exblas_exgemv");
     const bool trans = (transa == 'T' || transa == 't');
     const int rows = trans ? n : m, inner = trans ? m : n;
-    double *d_a, *d_x, *d_y;
-    size_t abytes = (size_t)lda * (size_t)n * sizeof(double);  // column-major: n columns of lda
-    size_t xspan = (size_t)(inner - 1) * (size_t)incx + 1, yspan = (size_t)(rows - 1) * (size_t)incy + 1;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d_a = (double *)stage_buf(c, 0, abytes);
-        d_x = (double *)stage_buf(c, 1, xspan * sizeof(double));
-        d_y = (double *)stage_buf(c, 2, yspan * sizeof(double));
-        EXB_CHECK(hipMemcpyAsync(d_a, a + offseta, abytes - (size_t)(lda - m) * sizeof(double), hipMemcpyHostToDevice,
-                                 c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_x, x + offsetx, xspan * sizeof(double), hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_y, y + offsety, yspan * sizeof(double), hipMemcpyHostToDevice, c.stream));
-    }
-    int rc = exgemv_on(c, transa, m, n, alpha, d_a, lda, d_x, incx, beta, d_y, incy, fpe, early_exit, c.stream);
-    if (rc) die("exblas_exgemv", (hipError_t)rc, __FILE__, __LINE__);
-    EXB_CHECK(hipMemcpyAsync(y + offsety, d_y, yspan * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
+    const size_t abytes = (size_t)lda * (size_t)n * sizeof(double);  // column-major: n columns of lda
+    const size_t xbytes = ((size_t)(inner - 1) * (size_t)incx + 1) * sizeof(double),
+                 ybytes = ((size_t)(rows - 1) * (size_t)incy + 1) * sizeof(double);
+    double *d_a = hc.in(0, abytes, a + offseta, abytes - (size_t)(lda - m) * sizeof(double));
+    double *d_x = hc.in(1, xbytes, x + offsetx, xbytes);
+    double *d_y = hc.in(2, ybytes, y + offsety, ybytes);
+    return hc.out(exgemv_on(hc.c, transa, m, n, alpha, d_a, lda, d_x, incx, beta, d_y, incy, fpe, early_exit, hc.c.stream),
+                  y + offsety, d_y, ybytes);
 }
 
 int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int lda, int offseta, double *x,
@@ -1404,23 +1225,13 @@ int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int
         return -1;
     }
     if (n <= 0) return 0;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
-    double *d_a, *d_x;
+    HostCall hc("exblas_extrsv");
     const size_t abytes = ((size_t)lda * (size_t)(n - 1) + (size_t)n) * sizeof(double);  // n columns of lda
-    const size_t xspan = (size_t)(n - 1) * (size_t)incx + 1;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d_a = (double *)stage_buf(c, 0, abytes);
-        d_x = (double *)stage_buf(c, 1, xspan * sizeof(double));
-        EXB_CHECK(hipMemcpyAsync(d_a, a + offseta, abytes, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_x, x + offsetx, xspan * sizeof(double), hipMemcpyHostToDevice, c.stream));
-    }
-    int rc = extrsv_on(c, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, c.stream);
-    if (rc) die("exblas_extrsv", (hipError_t)rc, __FILE__, __LINE__);
-    EXB_CHECK(hipMemcpyAsync(x + offsetx, d_x, xspan * sizeof(double), hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
+    const size_t xbytes = ((size_t)(n - 1) * (size_t)incx + 1) * sizeof(double);
+    double *d_a = hc.in(0, abytes, a + offseta, abytes);
+    double *d_x = hc.in(1, xbytes, x + offsetx, xbytes);
+    return hc.out(extrsv_on(hc.c, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, hc.c.stream), x + offsetx,
+                  d_x, xbytes);
 }
 
 }  // extern "C"
@@ -1445,35 +1256,31 @@ static int csr_host_call(const char *who, int m, int n, int k, int index_bits, c
         if (v > nnz) nnz = v;
     }
     if (nnz > 0 && (!col_idx || !val)) return (int)hipErrorInvalidValue;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    HostCall hc(who);
     // whole rows of X and Y travel, padding included (the last row only up to its k-th entry)
     const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)k : 0;
     const size_t yspan = (size_t)(m - 1) * (size_t)ldy + (size_t)k;
     const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
                  b_val = align_up((size_t)nnz * 8), b_x = align_up(xspan * 8), b_y = align_up(yspan * 8);
-    char *d, *d_val, *d_x, *d_y;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d = (char *)stage_buf(c, 0, b_rp + b_ci + b_val + b_x + b_y);
-        d_val = d + b_rp + b_ci;
-        d_x = d_val + b_val;
-        d_y = d_x + b_x;
-        EXB_CHECK(hipMemcpyAsync(d, row_ptr, (size_t)(m + 1) * isz, hipMemcpyHostToDevice, c.stream));
-        if (nnz > 0) {
-            EXB_CHECK(hipMemcpyAsync(d + b_rp, col_idx, (size_t)nnz * isz, hipMemcpyHostToDevice, c.stream));
-            EXB_CHECK(hipMemcpyAsync(d_val, val, (size_t)nnz * 8, hipMemcpyHostToDevice, c.stream));
-        }
-        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d_x, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_y, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    const int rc = launch(c, (const void *)d, (const void *)(d + b_rp), (const double *)d_val, (const double *)d_x,
-                          (double *)d_y);
-    if (rc) die(who, (hipError_t)rc, __FILE__, __LINE__);
+    char *d = (char *)hc.in(0, b_rp + b_ci + b_val + b_x + b_y, row_ptr, (size_t)(m + 1) * isz);
+    char *d_val = d + b_rp + b_ci, *d_x = d_val + b_val, *d_y = d_x + b_x;
+    hc.h2d(d + b_rp, col_idx, (size_t)nnz * isz);
+    hc.h2d(d_val, val, (size_t)nnz * 8);
+    hc.h2d(d_x, x, xspan * 8);
+    hc.h2d(d_y, y, yspan * 8);
     // the padding of Y comes back as it went
-    EXB_CHECK(hipMemcpyAsync(y, d_y, yspan * 8, hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
+    return hc.out(launch(hc.c, (const void *)d, (const void *)(d + b_rp), (const double *)d_val, (const double *)d_x,
+                         (double *)d_y),
+                  y, d_y, yspan * 8);
+}
+
+// what a host solve returns after its csr_host_call: the status of the layer-1 context's last solve
+static int host_solve_status(const long long *CtxWsPtrs::*info_dev)
+{
+    Ctx &c = ctx(-1, 1);
+    std::lock_guard<std::mutex> lk(c.mu);
+    long long h[8];
+    return solve_status(c.*info_dev, h);
 }
 
 extern "C" {
@@ -1509,12 +1316,7 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
                                      return exsptrsv_on(c, uplo, diag, m, index_bits, d_rp, d_ci, d_val, d_x, fpe, early_exit,
                                                         c.stream);
                                  });
-    if (rc || m == 0) return rc;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> lk(c.mu);
-    long long h[8];
-    if (int e = sparse_header(c.sptrsv_info_dev, h)) return e;
-    return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
+    return (rc || m == 0) ? rc : host_solve_status(&CtxWsPtrs::sptrsv_info_dev);
 }
 
 // the same with a block: X (m x k, row stride ldx; B on entry, the solution on return) travels as the host path's Y
@@ -1527,12 +1329,7 @@ int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, cons
                                      return exsptrsm_on(c, uplo, diag, m, k, index_bits, d_rp, d_ci, d_val, d_x, ldx, fpe,
                                                         early_exit, c.stream);
                                  });
-    if (rc || m == 0 || k == 0) return rc;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> lk(c.mu);
-    long long h[8];
-    if (int e = sparse_header(c.sptrsm_info_dev, h)) return e;
-    return h[1] ? EXBLAS_SPTRSV_STALLED : 0;
+    return (rc || m == 0 || k == 0) ? rc : host_solve_status(&CtxWsPtrs::sptrsm_info_dev);
 }
 
 // whole rows travel, padding included (the last row only up to its last entry); C comes back the same way, so that its
@@ -1544,26 +1341,15 @@ int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t l
     const int bad = bdot_check_args(mode, n, p, q, x, ldx, y, ldy, cm, ldc, fpe, &empty);
     if (bad || empty) return bad;
     const bool diag = mode == 'D' || mode == 'd';
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    HostCall hc("exblas_exbdot");
     const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)p : 0;
     const size_t yspan = n > 0 ? (size_t)(n - 1) * (size_t)ldy + (size_t)q : 0;
     const size_t cspan = diag ? (size_t)p : (size_t)(p - 1) * (size_t)ldc + (size_t)q;
-    double *d_x, *d_y, *d_c;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d_x = (double *)stage_buf(c, 0, xspan * 8 + 8);
-        d_y = (double *)stage_buf(c, 1, yspan * 8 + 8);
-        d_c = (double *)stage_buf(c, 2, cspan * 8);
-        if (xspan > 0) EXB_CHECK(hipMemcpyAsync(d_x, x, xspan * 8, hipMemcpyHostToDevice, c.stream));
-        if (yspan > 0) EXB_CHECK(hipMemcpyAsync(d_y, y, yspan * 8, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_c, cm, cspan * 8, hipMemcpyHostToDevice, c.stream));
-    }
-    const int rc = exbdot_on(c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, c.stream);
-    if (rc) die("exblas_exbdot", (hipError_t)rc, __FILE__, __LINE__);
-    EXB_CHECK(hipMemcpyAsync(cm, d_c, cspan * 8, hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
+    double *d_x = hc.in(0, xspan * 8 + 8, x, xspan * 8);
+    double *d_y = hc.in(1, yspan * 8 + 8, y, yspan * 8);
+    double *d_c = hc.in(2, cspan * 8, cm, cspan * 8);
+    return hc.out(exbdot_on(hc.c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, hc.c.stream), cm, d_c,
+                  cspan * 8);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
@@ -1571,28 +1357,18 @@ int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, c
 {
     check_fpe(fpe);
     if (m <= 0 || n <= 0) return 0;
-    Ctx &c = ctx(-1, 1);
-    std::lock_guard<std::mutex> api_lock(g_host_mu);
+    HostCall hc("exblas_exgemm");
     const bool ta = (transa == 'T' || transa == 't'), tb = (transb == 'T' || transb == 't');
     // row-major storage (ExGEMM.Superacc.cl:254-255): A is m x k (k x m when transposed), etc.
-    size_t abytes = (size_t)(ta ? k : m) * (size_t)lda * sizeof(double);
-    size_t bbytes = (size_t)(tb ? n : k) * (size_t)ldb * sizeof(double);
-    size_t cbytes = (size_t)m * (size_t)ldc * sizeof(double);
-    double *d_a, *d_b, *d_c;
-    {
-        std::lock_guard<std::mutex> lk(c.mu);
-        d_a = (double *)stage_buf(c, 0, abytes);
-        d_b = (double *)stage_buf(c, 1, bbytes);
-        d_c = (double *)stage_buf(c, 2, cbytes);
-        EXB_CHECK(hipMemcpyAsync(d_a, a, abytes, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_b, b, bbytes, hipMemcpyHostToDevice, c.stream));
-        EXB_CHECK(hipMemcpyAsync(d_c, cm, cbytes, hipMemcpyHostToDevice, c.stream));
-    }
-    int rc = exgemm_on(c, transa, transb, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, fpe, early_exit, c.stream);
-    if (rc) die("exblas_exgemm", (hipError_t)rc, __FILE__, __LINE__);
-    EXB_CHECK(hipMemcpyAsync(cm, d_c, cbytes, hipMemcpyDeviceToHost, c.stream));
-    EXB_CHECK(hipStreamSynchronize(c.stream));
-    return 0;
+    const size_t abytes = (size_t)(ta ? k : m) * (size_t)lda * sizeof(double);
+    const size_t bbytes = (size_t)(tb ? n : k) * (size_t)ldb * sizeof(double);
+    const size_t cbytes = (size_t)m * (size_t)ldc * sizeof(double);
+    double *d_a = hc.in(0, abytes, a, abytes);
+    double *d_b = hc.in(1, bbytes, b, bbytes);
+    double *d_c = hc.in(2, cbytes, cm, cbytes);
+    return hc.out(exgemm_on(hc.c, transa, transb, m, n, k, alpha, d_a, lda, d_b, ldb, beta, d_c, ldc, fpe, early_exit,
+                            hc.c.stream),
+                  cm, d_c, cbytes);
 }
 
 }  // extern "C"

@@ -8,12 +8,10 @@
 
 namespace exb {
 
-// Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
-// launchers (ExSUM.Launcher.cpp:16-36), which make the reference GPU library non re-entrant, and the
-// per-call OpenCL context + JIT (gpu:ExSUM.cpp:86-209).
-struct Ctx {
-    int device = -1;
-    int num_cu = 256;
+// The knobs a new context inherits: the environment sets them for layer 0, the exblas_set_* calls for every context of
+// the device that exists, and a context created later (a host-layer context, a handle) takes layer 0's with one
+// assignment of this struct (capi.hip: init_ctx).  A knob declared here is inherited; nothing else has to be edited.
+struct CtxKnobs {
     int blocks_per_cu = 8;   // EXBLAS_BLOCKS_PER_CU: generic cap of resident blocks per CU
     // Measured on MI355X (tools/tune.py, n = 2^28): the one-stream ExSUM kernel is fastest with FEW fat
     // blocks (2 per CU: 7.15 TB/s vs 6.46 at 8), the two-stream ExDOT kernel with many (16-32 per CU).
@@ -22,35 +20,51 @@ struct Ctx {
     int bpc_heavy = 4;       // ExSUM variants without early exit, N >= 5, in -DEXBLAS_FULL_CASCADE=1 builds only (VALU-latency-bound)
     int ngroups = 32;        // EXBLAS_NGROUPS: global group accumulators the blocks add into
     int grid_adj = 0;        // EXBLAS_GRID_ADJ: workgroups added to the grid of the streaming ExSUM / ExDOT kernels
-    // when set, the NEXT streaming ExSUM / ExDOT launch carries this event as the completion signal of its own dispatch
-    // packet (hipExtLaunchKernelGGL) and clears the field: no separate event packet follows the kernel in the queue
-    // (comm.hip: pipelined_step)
-    hipEvent_t launch_stop_event = nullptr;
-    hipEvent_t launch_start_event = nullptr;
-    // which ExGEMM implementation the last call used.  The int8 path decides on the device: gemm_info_dev then points
-    // at its info block (read lazily, with a synchronisation, by exblas_last_gemm_info); otherwise the host knows.
-    int last_gemm_slices = 0;  // host-decided paths: 0 scalar kernel; 2..4: fp64-slice MFMA path with that many slices
-    const int *gemm_info_dev = nullptr;
     int gemm_path = 0;       // 0: int8 matrix cores when the data qualifies (decided on the device) -- residues modulo
                              // 8-bit moduli for min(m, n) >= 192, base-256 digit slices below; 2: digit slices always;
                              // 4: residues always; 1: scalar kernel only; 3: fp64 slices on MFMA-F64 (host-decided)
     int gemm_max_slices = 0; // 0 = default (16): digits per operand the int8 path reserves workspace for
     int gemm_max_moduli = 0; // 0 = default (39): moduli the residue path reserves workspace for
-    int gemm_ws_moduli = 0;  // moduli the last residue-path call actually reserved for (fewer after an out-of-memory retry)
     int spmv_path = 0;       // exblas_set_spmv_path: 0 automatic, 1 accumulator finish for every row, 2 in-register
                              // rounding wherever certified (no row split), 3 every row split at a small chunk
-    const long long *spmv_info_dev = nullptr;  // header of the last ExSpMV call's workspace (exblas_last_spmv_info)
     int spmm_path = 0;       // exblas_set_spmm_path: 0 automatic, 1 every output rounded from an integer accumulator,
                              // 2 in-register rounding wherever certified (no row split), 3 every row split at a small chunk
-    const long long *spmm_info_dev = nullptr;  // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
     int sptrsv_path = 0;     // exblas_set_sptrsv_path: 0 automatic, 1 every row rounded from its integer accumulator,
                              // 2 every row in the one-row-per-wave form
-    const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
-    const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
+};
+
+// The pointers of a context that point INTO its workspace block (Ctx::ws): exblas_release_workspace resets this struct
+// whole when it frees the block, so a pointer declared here is forgotten with it; nothing else has to be edited.
+// Known wart, left as it is: the block is shared, so a last_*_info query after a DIFFERENT routine has reused the
+// workspace reads that routine's header through the older pointer.
+struct CtxWsPtrs {
+    // which ExGEMM implementation the last call used.  The int8 path decides on the device: gemm_info_dev then points
+    // at its info block (read lazily, with a synchronisation, by exblas_last_gemm_info); otherwise the host knows
+    // (Ctx::last_gemm_slices).
+    const int *gemm_info_dev = nullptr;
+    const long long *spmv_info_dev = nullptr;    // header of the last ExSpMV call's workspace (exblas_last_spmv_info)
+    const long long *spmm_info_dev = nullptr;    // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
+    const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
+    const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
+};
+
+// Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
+// launchers (ExSUM.Launcher.cpp:16-36), which make the reference GPU library non re-entrant, and the
+// per-call OpenCL context + JIT (gpu:ExSUM.cpp:86-209).
+struct Ctx : CtxKnobs, CtxWsPtrs {
+    int device = -1;
+    int num_cu = 256;
+    // when set, the NEXT streaming ExSUM / ExDOT launch carries this event as the completion signal of its own dispatch
+    // packet (hipExtLaunchKernelGGL) and clears the field: no separate event packet follows the kernel in the queue
+    // (comm.hip: pipelined_step)
+    hipEvent_t launch_stop_event = nullptr;
+    hipEvent_t launch_start_event = nullptr;
+    int last_gemm_slices = 0;  // host-decided ExGEMM paths: 0 scalar kernel; 2..4: fp64-slice MFMA path with that many slices
+    int gemm_ws_moduli = 0;  // moduli the last residue-path call actually reserved for (fewer after an out-of-memory retry)
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1

@@ -789,7 +789,7 @@ void orc_init_ill_cond_rand(int n, double *a, double c)
 
 /* Counter-based generators (ours): element i depends only on (kind, seed, i, n_total, p0, p1)
  * and uses integer arithmetic, exact int->double conversions and multiplications by powers
- * of two only, so k_gen in exblas_amd/csrc/capi.hip produces the same bits on the GPU.  They follow the
+ * of two only, so k_gen in exblas_amd/csrc/probes.hip produces the same bits on the GPU.  They follow the
  * *shape* of the reference's distributions (common.cpp), not its rand() stream:
  *   0 naive            1.1                                            (common.cpp:147)
  *   1 fpuniform        m in [1,2) * 2^(emax-range+U[0,range)), >0      (common.cpp:18-33)

@@ -73,6 +73,26 @@ def test_set_tuning_refuses_a_kernel_variant():
     assert r.returncode == 0 and r.stdout.strip().endswith("ret 1"), (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 
 
+def test_dev_functions_are_the_default_contexts_methods():
+    """Every routine with a handle form has one Python body, a Context method; the module's *_dev function is that method
+    bound to the context without a handle (the device's default context).  Importing and looking creates no context."""
+    import inspect
+    import exblas_amd
+    names = ["exsum", "exdot", "exsum_accumulate", "exdot_accumulate", "finish", "exgemv", "extrsv", "exgemm", "exspmv",
+             "exspmm", "exsptrsv", "exsptrsm", "exbdot", "exbdot_export", "exbdot_round"]
+    owners = set()
+    for name in names:
+        f = getattr(exblas_amd, name + "_dev")
+        assert inspect.ismethod(f) and f.__func__ is getattr(exblas_amd.Context, name), name
+        assert isinstance(f.__self__, exblas_amd.Context) and f.__self__.handle is None, name
+        params = list(inspect.signature(getattr(exblas_amd.Context, name)).parameters.values())
+        assert params[0].name == "self" and inspect.signature(f) == inspect.Signature(params[1:]), name
+        owners.add(id(f.__self__))
+    assert len(owners) == 1
+    f.__self__.destroy()            # nothing to destroy
+    assert f.__self__.handle is None
+
+
 def test_product_does_not_import_oracle():
     """The shipped package may mention the oracle in comments, but never import, include, link or dlopen it."""
     bad = re.compile(r"^\s*(from|import)\s+.*oracle|#\s*include\s*[\"<].*oracle|CDLL\(.*oracle|dlopen\(.*oracle", re.M)

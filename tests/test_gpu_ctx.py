@@ -185,3 +185,118 @@ def test_launch_events_bracket_the_streaming_kernel(ex):
         ex.finish_dev()
         torch.cuda.synchronize()
         assert e0.elapsed_time(e1) == t_before
+
+
+def _words(ex, rec):
+    return ex.read_record(rec).words
+
+
+def test_handle_equals_default_on_strides_counts_and_accumulate(ex):
+    """The arguments the handle methods lacked before they became the one implementation: a stride, both strides with an
+    explicit count, and exdot_accumulate.  A handle and the default context give the same record, all 128 words."""
+    import torch
+    n = 100003
+    x = ex.gen_dev("ill_cond", 3 * n, 41, 1e32)
+    y = ex.gen_dev("fpuniform_signed", 3 * n, 42, 40, 20)
+    c = ex.Context()
+    try:
+        assert (_words(ex, c.exsum(x, 4, False, inca=3)) == _words(ex, ex.exsum_dev(x, 4, False, inca=3))).all()
+        got = _words(ex, c.exdot(x, y, 8, True, incx=2, incy=3, n=n))
+        assert (got == _words(ex, ex.exdot_dev(x, y, 8, True, incx=2, incy=3, n=n))).all()
+        x1, x2, y1, y2 = x[:n], x[n:2 * n + 1], y[:n], y[n:2 * n + 1]
+        c.exdot_accumulate(x1, y1)
+        c.exdot_accumulate(x2, y2)
+        got = _words(ex, c.finish())
+        assert (got == _words(ex, ex.exdot_dev(torch.cat([x1, x2]), torch.cat([y1, y2])))).all()
+    finally:
+        c.destroy()
+
+
+def _bidiagonal(m):
+    """lower bidiagonal, dominant diagonal, as (row_ptr, col_idx, val, (m, m)) numpy arrays"""
+    crow = np.concatenate([[0], 2 * np.arange(1, m + 1) - 1]).astype(np.int32)
+    col = np.concatenate([[0]] + [[i - 1, i] for i in range(1, m)]).astype(np.int32)
+    val = np.concatenate([[4.0]] + [[0.5 + i / 256.0, 4.0 + i / 64.0] for i in range(1, m)])
+    return crow, col, val, (m, m)
+
+
+_KNOBS_CHILD = """
+import ctypes as C, json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import torch
+import exblas_amd as ex
+lib = ex.load_library()
+ex.set_spmv_path(1); ex.set_spmm_path(1); ex.set_sptrsv_path(1); ex.set_sptrsm_path(1)
+lib.exblas_set_gemm_path(1)
+m, k = 70, 3
+A = _bidiagonal(m)
+b = 1.0 + np.arange(m) / 128.0
+B = np.stack([b, -b, 3.0 * b], axis=1)
+out = {}
+ex.exspmv(A, b); out["spmv"] = ex.last_spmv_info()
+ex.exspmm(A, B); out["spmm"] = ex.last_spmm_info()
+ex.exsptrsv(A, b); out["sptrsv"] = ex.last_sptrsv_info()
+ex.exsptrsm(A, B); out["sptrsm"] = ex.last_sptrsm_info()
+c = ex.Context()
+n = 96
+P, Q = ex.gen_dev("fpuniform", n * n, 6, 10, 0), ex.gen_dev("fpuniform", n * n, 7, 10, 0)
+R = torch.zeros(n * n, dtype=torch.float64, device="cuda")
+c.exgemm("N", "N", n, n, n, 1.0, P, n, Q, n, 0.0, R, n, 8, True)
+info = (C.c_int * 8)()
+out["gemm_rc"] = lib.exblas_last_gemm_info_ctx(c.handle, info)
+out["gemm"] = list(info)
+c.destroy()
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_knobs_set_before_a_layer_exists_reach_it():
+    """The path knobs are set when only the default context exists; the host-array calls then create the host layer's
+    context and a handle is created after that.  Both must take the knobs: every row / output rounded from its
+    accumulator, the scalar ExGEMM kernel.  A fresh process, so that the layers do not exist yet."""
+    import inspect
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", inspect.getsource(_bidiagonal) + _KNOBS_CHILD, root], capture_output=True,
+                       text=True, timeout=240)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    out = json.loads(r.stdout.split("RESULT ", 1)[1])
+    m, k = 70, 3
+    for name, units in (("spmv", m), ("spmm", m * k), ("sptrsv", m), ("sptrsm", m * k)):
+        assert out[name][0] == 0 and out[name][1] == units, (name, out)
+    assert out["gemm_rc"] == 0 and out["gemm"][0] == 0, out
+
+
+def test_release_workspace_forgets_every_pointer_into_it(ex):
+    """After exblas_release_workspace no last_*_info query may follow a pointer into the freed block: ExSpMV / ExSpMM
+    answer "no call", the solves and ExGEMM answer zeros; the next call works as before."""
+    import ctypes as C
+    import torch
+    lib = ex.load_library()
+    m, k = 70, 3
+    crow, col, val, shape = _bidiagonal(m)
+    A = (torch.from_numpy(crow).cuda(), torch.from_numpy(col).cuda(), torch.from_numpy(val).cuda(), shape)
+    b = torch.from_numpy(1.0 + np.arange(m) / 128.0).cuda()
+    B = torch.stack([b, -b, 3.0 * b], dim=1).contiguous()
+    before = _bits(ex.exspmv_dev(A, b))
+    ex.exspmm_dev(A, B)
+    ex.exsptrsv_dev(A, b.clone())
+    ex.exsptrsm_dev(A, B.clone())
+    gm, gk, gn = 130, 200, 75           # the int8-path shape of smoke(): its info block lives in the workspace
+    P, Q = ex.gen_dev("fpuniform", gm * gk, 3, 10, 0), ex.gen_dev("fpuniform", gk * gn, 4, 10, 0)
+    ex.exgemm_dev("N", "N", gm, gn, gk, 1.0, P, gk, Q, gn, 0.0, torch.zeros(gm * gn, dtype=torch.float64, device="cuda"),
+                  gn, 8, True)
+    assert lib.exblas_release_workspace() == 0
+    out4 = (C.c_int64 * 4)(7, 7, 7, 7)
+    assert lib.exblas_last_spmv_info(out4) == -1
+    assert lib.exblas_last_spmm_info(out4) == -1
+    for query in (lib.exblas_last_sptrsv_info, lib.exblas_last_sptrsm_info):
+        out4 = (C.c_int64 * 4)(7, 7, 7, 7)
+        assert query(out4) == 0 and list(out4) == [0, 0, 0, 0]
+    info = (C.c_int * 8)(7, 7, 7, 7, 7, 7, 7, 7)
+    assert lib.exblas_last_gemm_info(info) == 0 and info[0] == 0
+    assert (_bits(ex.exspmv_dev(A, b)) == before).all()
