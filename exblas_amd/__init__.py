@@ -50,6 +50,7 @@ C_ABI_SYMBOLS = [
     "exblas_last_sptrsv_info",
     "exblas_exsptrsm_csr_dev", "exblas_exsptrsm_csr_ctx", "exblas_exsptrsm_csr", "exblas_set_sptrsm_path",
     "exblas_last_sptrsm_info",
+    "exblas_extrsm_dev", "exblas_extrsm_ctx", "exblas_extrsm", "exblas_set_trsm_path", "exblas_last_trsm_info",
     "exblas_exbdot_dev", "exblas_exbdot_ctx", "exblas_exbdot", "exblas_set_bdot_path",
     "exblas_exbdot_export_dev", "exblas_exbdot_export_ctx", "exblas_exbdot_round_dev", "exblas_exbdot_round_ctx",
     "exblas_exbdot_allreduce_dev",
@@ -196,6 +197,12 @@ def load_library():
     L.exblas_set_sptrsm_path.argtypes = [i32]
     L.exblas_set_sptrsm_path.restype = None
     L.exblas_last_sptrsm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_extrsm_dev.argtypes = [C.c_char, C.c_char, C.c_char, i32, i32, vp, i32, vp, i64, i32, i32, vp]
+    L.exblas_extrsm_ctx.argtypes = [vp] + L.exblas_extrsm_dev.argtypes
+    L.exblas_extrsm.argtypes = [C.c_char, C.c_char, C.c_char, i32, i32, vp, i32, vp, i64, i32, i32]
+    L.exblas_set_trsm_path.argtypes = [i32]
+    L.exblas_set_trsm_path.restype = None
+    L.exblas_last_trsm_info.argtypes = [C.POINTER(i64)]
     L.exblas_exbdot_dev.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32, vp]
     L.exblas_exbdot_ctx.argtypes = [vp] + L.exblas_exbdot_dev.argtypes
     L.exblas_exbdot.argtypes = [C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32]
@@ -469,6 +476,73 @@ def last_sptrsm_info():
     return _last_info("sptrsm")
 
 
+def _trsm_layout(A, uplo, trans):
+    """How ExTRSM reads the 2-D operand A (anything with shape and stride(i), strides in elements) without copying it:
+    returns (uplo, trans, lda) for the C call, which takes column-major storage.  `uplo` names the triangle of A[i, j] as
+    Python indexes it.  stride(0) == 1 is column-major, lda = stride(1); stride(1) == 1 is row-major, the column-major
+    storage of A^T: the other triangle, the other trans, lda = stride(0)."""
+    if not isinstance(uplo, str) or uplo not in ("L", "l", "U", "u"):
+        raise ValueError(f"extrsm: uplo must be 'L' or 'U', got {uplo!r}")
+    if not isinstance(trans, str) or trans not in ("N", "n", "T", "t"):
+        raise ValueError(f"extrsm: trans must be 'N' or 'T', got {trans!r}")
+    uplo, trans = uplo.upper(), trans.upper()
+    n = int(A.shape[0])
+    s0, s1 = int(A.stride(0)), int(A.stride(1))
+    if n <= 1:                                  # nothing, or one entry: any strides do
+        return uplo, trans, 1
+    if s0 == 1 and s1 >= n:
+        return uplo, trans, s1
+    if s1 == 1 and s0 >= n:
+        return ("U" if uplo == "L" else "L"), ("T" if trans == "N" else "N"), s0
+    raise ValueError(f"extrsm: A must have one unit stride and the other >= n = {n} (it is not copied), got strides "
+                     f"({s0}, {s1})")
+
+
+def _trsm_fpe(fpe):
+    fpe = int(fpe)
+    if fpe < 0 or fpe >= 9:
+        raise ValueError(f"extrsm: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
+    return fpe
+
+
+def _trsm_args(A, X, uplo, trans, diag, fpe, early_exit):
+    """Validates a device ExTRSM call before anything is launched; returns the C arguments up to the stream."""
+    _dense_dev("extrsm", "A", A, 2)
+    n = int(A.shape[0])
+    if A.shape[1] != n:
+        raise ValueError(f"extrsm: A must be square, got shape {tuple(A.shape)}")
+    if n > 0x7fffffff:
+        raise ValueError(f"extrsm: unsupported shape {tuple(A.shape)}")
+    u, t, lda = _trsm_layout(A, uplo, trans)
+    _, d = _solve_flags("extrsm", "L", diag)
+    if getattr(X, "ndim", 2) == 1:
+        raise ValueError("extrsm: X must be a 2-D block of right-hand sides; for one vector use extrsv_dev")
+    _dense_dev("extrsm", "X", X, 2)
+    if X.shape[0] != n:
+        raise ValueError(f"extrsm: X must have n = {n} rows")
+    k = int(X.shape[1])
+    # a block that does not conform is refused, not copied: it is solved in place
+    if X.stride(1) != 1:
+        raise ValueError("extrsm: X must be row-major with stride(1) == 1 (it is solved in place)")
+    if X.stride(0) < k:
+        raise ValueError(f"extrsm: the rows of X overlap: stride(0) = {X.stride(0)} < k = {k}")
+    fpe = _trsm_fpe(fpe)
+    _on_gpu("extrsm", A=A, X=X)
+    return (u.encode(), t.encode(), d, n, k, _ptr(A), lda, _ptr(X), max(int(X.stride(0)), 1), fpe, int(bool(early_exit)))
+
+
+def set_trsm_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one row per work item, 3 column
+    panels and tiles of 4 columns.  Same bits on every path."""
+    load_library().exblas_set_trsm_path(int(mode))
+
+
+def last_trsm_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last ExTRSM; raises when that
+    call's watchdog was raised."""
+    return _last_info("trsm")
+
+
 def _ld(t, k):
     """Leading dimension of a row-major 2-D tensor with unit column stride (a single row: k)."""
     return max(int(t.stride(0)), k) if t.shape[0] > 1 else k
@@ -708,6 +782,18 @@ class Context:
             _check(rc, "extrsv")
         return rc
 
+    def extrsm(self, A, X, uplo="L", trans="N", diag="N", fpe=8, early_exit=True):
+        """ExTRSM: solves op(A) X = B in place on the n x k block X (B on entry) for k right-hand sides at once, exact and
+        reproducible, stream-ordered on the current stream: column j is bit for bit what extrsv_dev gives on B[:, j], and
+        the chain of n rounded divisions is walked once, not k times.  A: a 2-D float64 tensor with one unit stride, never
+        copied -- column-major (stride(0) == 1) or row-major (stride(1) == 1); `uplo` names the triangle of A[i, j] as
+        Python indexes it, the other triangle is never read.  X: a 2-D float64 tensor with stride(1) == 1 and
+        stride(0) >= k (a view [:, :k] of a wider block is fine: its padding is not touched).  fpe: 0, 1 or 2..8.
+        Returns X."""
+        args = _trsm_args(A, X, uplo, trans, diag, fpe, early_exit)
+        _check_sparse(load_library().exblas_extrsm_ctx(self.handle, *args, _stream_ptr(_torch())), "extrsm")
+        return X
+
     def exgemm(self, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, c, ldc, fpe=0, early_exit=False):
         torch = _require_gpu()
         _check(load_library().exblas_exgemm_ctx(self.handle, transa.encode(), transb.encode(), m, n, k, alpha,
@@ -792,6 +878,7 @@ _default.handle = None
 exsum_dev, exdot_dev, finish_dev = _default.exsum, _default.exdot, _default.finish
 exsum_accumulate_dev, exdot_accumulate_dev = _default.exsum_accumulate, _default.exdot_accumulate
 exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.exgemm
+extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
 
@@ -968,6 +1055,41 @@ def exsptrsm(A, B, uplo="L", diag="N", fpe=8, early_exit=True):
     _require_gpu()
     _check_sparse(load_library().exblas_exsptrsm_csr(u, d, m, k, bits, _hptr(crow), _hptr(col), _hptr(val), _hptr(X),
                                                      max(k, 1), int(fpe), int(bool(early_exit))), "exsptrsm")
+    return X
+
+
+class _HostStrides:
+    """shape and element strides of a numpy array, as _trsm_layout reads them"""
+
+    def __init__(self, a):
+        self.shape = a.shape
+        self._strides = tuple(s // a.itemsize for s in a.strides)
+
+    def stride(self, i):
+        return self._strides[i]
+
+
+def extrsm(A, B, uplo="L", trans="N", diag="N", fpe=8, early_exit=True):
+    """ExTRSM on host arrays: A float64 of shape (n, n), C- or Fortran-ordered (anything else is copied to C order; `uplo`
+    names the triangle of A[i, j]), B float64 of shape (n, k); returns the solution (a new n x k float64 array; B is not
+    changed)."""
+    A = _dense_host("extrsm", "A", A, 2)
+    n = int(A.shape[0])
+    if A.shape[1] != n:
+        raise ValueError(f"extrsm: A must be square, got shape {tuple(A.shape)}")
+    if not (A.flags.c_contiguous or A.flags.f_contiguous):
+        A = np.ascontiguousarray(A)
+    u, t, lda = _trsm_layout(_HostStrides(A), uplo, trans)
+    _, d = _solve_flags("extrsm", "L", diag)
+    B = _dense_host("extrsm", "B", B, 2, " (a block of right-hand sides; for one vector use extrsv)")
+    if B.shape[0] != n:
+        raise ValueError(f"extrsm: B must have n = {n} rows")
+    fpe = _trsm_fpe(fpe)
+    X = np.array(B, dtype=np.float64, copy=True, order="C")
+    k = int(X.shape[1])
+    _require_gpu()
+    _check_sparse(load_library().exblas_extrsm(u.encode(), t.encode(), d, n, k, _hptr(A), max(lda, 1), _hptr(X), max(k, 1),
+                                               fpe, int(bool(early_exit))), "extrsm")
     return X
 
 

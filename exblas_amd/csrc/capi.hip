@@ -318,6 +318,7 @@ void exblas_set_spmv_path(int mode) { set_path(&CtxKnobs::spmv_path, mode, 3); }
 void exblas_set_spmm_path(int mode) { set_path(&CtxKnobs::spmm_path, mode, 3); }
 void exblas_set_sptrsv_path(int mode) { set_path(&CtxKnobs::sptrsv_path, mode, 2); }
 void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3); }
+void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
@@ -367,6 +368,10 @@ int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs:
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
 int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::sptrsm_info_dev, true, out4); }
+
+// out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0 (a dense triangle
+// has no structure to count); EXBLAS_SPTRSV_STALLED as above
+int exblas_last_trsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::trsm_info_dev, true, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -527,6 +532,30 @@ static int extrsv_on(Ctx &c, char uplo, char transa, char diag, int n, const dou
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)extrsv_dispatch(c, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of ExTRSM, on host or device pointers alike; fpe >= 9 is refused as ExTRSV refuses it.  *empty:
+// nothing to compute (n == 0 or k == 0), which is decided before the pointers are looked at.
+static int trsm_check_args(char uplo, char transa, char diag, int n, int k, const double *a, int lda, const double *x,
+                           int64_t ldx, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(uplo, "LlUu") || !one_of(transa, "NnTt") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    if (n < 0 || k < 0 || lda < (n > 1 ? n : 1) || ldx < k || fpe < 0) return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = n == 0 || k == 0;
+    if (!*empty && (!a || !x)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int extrsm_on(Ctx &c, char uplo, char transa, char diag, int n, int k, const double *d_a, int lda, double *d_x,
+                     int64_t ldx, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // n == 0 or k == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = trsm_check_args(uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)extrsm_dispatch(c, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, round_mode(), st);
 }
 
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
@@ -769,6 +798,13 @@ int exblas_extrsv_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n,
     return extrsv_on(*cp, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_extrsm_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n, int k, const double *d_a, int lda,
+                      double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return extrsm_on(*cp, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -831,6 +867,11 @@ int exblas_extrsv_dev(char uplo, char transa, char diag, int n, const double *d_
                       int fpe, int early_exit, void *stream)
 {
     return exblas_extrsv_ctx(nullptr, uplo, transa, diag, n, d_a, lda, d_x, incx, fpe, early_exit, stream);
+}
+int exblas_extrsm_dev(char uplo, char transa, char diag, int n, int k, const double *d_a, int lda, double *d_x,
+                      int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    return exblas_extrsm_ctx(nullptr, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, stream);
 }
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
                       const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
@@ -1330,6 +1371,25 @@ int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, cons
                                                         early_exit, c.stream);
                                  });
     return (rc || m == 0 || k == 0) ? rc : host_solve_status(&CtxWsPtrs::sptrsm_info_dev);
+}
+
+// the n columns of A travel with their lda padding (the last one only up to its n-th entry), and whole rows of X (the
+// last one only up to its k-th entry), which come back the same way: the padding of X returns as it went
+int exblas_extrsm(char uplo, char transa, char diag, int n, int k, const double *a, int lda, double *x, int64_t ldx,
+                  int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = trsm_check_args(uplo, transa, diag, n, k, a, lda, x, ldx, fpe, &empty);
+    if (bad || empty) return bad;
+    {
+        HostCall hc("exblas_extrsm");
+        const size_t abytes = ((size_t)lda * (size_t)(n - 1) + (size_t)n) * sizeof(double);
+        const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)k) * sizeof(double);
+        double *d_a = hc.in(0, abytes, a, abytes);
+        double *d_x = hc.in(1, xbytes, x, xbytes);
+        hc.out(extrsm_on(hc.c, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, hc.c.stream), x, d_x, xbytes);
+    }
+    return host_solve_status(&CtxWsPtrs::trsm_info_dev);
 }
 
 // whole rows travel, padding included (the last row only up to its last entry); C comes back the same way, so that its

@@ -33,6 +33,8 @@ struct CtxKnobs {
                              // 2 every row in the one-row-per-wave form
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
+    int trsm_path = 0;       // exblas_set_trsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
+                             // per item, 3 column panels and tiles of 4 columns
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -50,6 +52,7 @@ struct CtxWsPtrs {
     const long long *spmm_info_dev = nullptr;    // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
     const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
+    const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -210,6 +213,10 @@ int exbdot_merged_dev(char mode, int64_t n, int p, int q, const double *d_x, int
 // trsv.hip
 hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, const double *a, int lda, double *x,
                            int incx, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// trsm.hip
+hipError_t extrsm_dispatch(Ctx &c, char uplo, char transa, char diag, int n, int k, const double *a, int lda, double *x,
+                           long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
 struct I8Plan {

@@ -137,7 +137,8 @@ int exblas_reserve_workspace(size_t bytes);
  * outputs), L = min(m, floor(32 MiB / (576 k))) accumulator slots for split rows: at most 32 MiB whatever k is; rows
  * past L run whole.  ExSpTRSV: 256 + 8 m bytes (the header and the mailbox of m doubles).  ExSpTRSM: 256 + 8 m min(k, P)
  * bytes (the header and the mailbox of one column panel), P = max(64, 64 floor(EXBLAS_SPTRSM_MAILBOX_BYTES / (8 m) / 64))
- * columns per panel: at most 64 MiB (EXBLAS_SPTRSM_MAILBOX_BYTES) unless 512 m exceeds it.  ExBDOT:
+ * columns per panel: at most 64 MiB (EXBLAS_SPTRSM_MAILBOX_BYTES) unless 512 m exceeds it.  ExTRSM: 256 + 8 n min(k, P)
+ * bytes likewise, P = max(64, 64 floor(EXBLAS_TRSM_MAILBOX_BYTES / (8 n) / 64)) (the same 64 MiB).  ExBDOT:
  * EXBLAS_BDOT_WORKSPACE_BYTES (2.25 MiB: 4096 accumulator sets of 576 bytes) whatever n, p and q are. */
 size_t exblas_workspace_bytes(void);
 /* Frees the workspace blocks that later, larger calls replaced.  Synchronises the device; only call it when no graph
@@ -341,6 +342,43 @@ void exblas_set_sptrsm_path(int mode);
  * the device; valid until the next call that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as
  * exblas_last_sptrsv_info does. */
 int exblas_last_sptrsm_info(int64_t *out4);
+/* ExTRSM: ExTRSV with k right-hand sides.  A is the n x n column-major triangle of exblas_extrsv_dev (lda >= max(1, n),
+ * uplo 'L'/'U', transa 'N'/'T', diag 'N'/'U'); d_x is an n x k ROW-MAJOR block with leading dimension ldx >= k, as in
+ * ExSpTRSM and ExBDOT, that holds B on entry and the solution on return.  For every column j, X[:, j] afterwards holds
+ * exactly the bits that exblas_extrsv_dev(uplo, transa, diag, n, A, lda, X + j, incx = ldx, fpe', early_exit', stream)
+ * writes for B[:, j], for any fpe' that is 0 or in 2..8, in the current rounding mode:
+ *     x_ij = fl( Round( b_ij - sum_{c before i} op(A)(i,c) * x_cj ) / op(A)(i,i) )
+ * in substitution order, the sum exact over the already fixed doubles and rounded once by the superaccumulator rounding
+ * of exblas_set_round_mode, then one IEEE division (none for diag 'U').  Product domain and Inf / NaN rules: ExTRSV's;
+ * every stored entry of the strict triangle counts, so a zero times an infinite x_cj is NaN.  The other triangle, the
+ * lda padding and, under diag 'U', the stored diagonal are never read.
+ * The bits depend on the data and (uplo, transa, diag, rounding mode) only: not on k, ldx, the column panel or tile, the
+ * row grouping, the grid, the path (exblas_set_trsm_path), fpe (0 or 2..8), early_exit, the context or the stream.
+ * Columns are independent: a NaN or Inf in column j of B changes no bit of another column.  The padding of a row of X
+ * beyond column k - 1 is neither read nor written.  All offsets (row * ldx, column * lda) are 64-bit.
+ * fpe == 0 rounds every output from an integer accumulator; fpe == 1 is the plain fp64 solve on the same structure
+ * (deterministic, not exact); fpe >= 9 returns EXBLAS_UNSUPPORTED and touches nothing, as exblas_extrsv_dev does.
+ * The chain of n rounded divisions is walked once for all columns and A is read once per tile of 64 columns, not once
+ * per column: lanes own columns, so the wait for a solved row and the entries of A serve every column of a tile.
+ * Columns are solved in panels of min(k, P) columns, one after the other in stream order (each a preset kernel and a
+ * solve kernel), P the largest multiple of 64 with 8 n P <= EXBLAS_TRSM_MAILBOX_BYTES, at least 64 (see
+ * exblas_workspace_bytes).  No host synchronisation: capturable into a hipGraph after exblas_reserve_workspace or one
+ * call with the same (n, k).  n == 0 or k == 0: success, nothing is launched; k == 1 is valid.  n < 0, k < 0,
+ * lda < max(1, n), ldx < k, a uplo, transa or diag outside L/U, N/T, N/U (either case) or fpe < 0: hipErrorInvalidValue.
+ * Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: a scaling alpha, the right-side solve X op(A) = B, a column-major X, conjugation. */
+#define EXBLAS_TRSM_MAILBOX_BYTES ((size_t)64 << 20)
+int exblas_extrsm_dev(char uplo, char transa, char diag, int n, int k, const double *d_a, int lda, double *d_x,
+                      int64_t ldx, int fpe, int early_exit, void *stream);
+/* Test hook for ExTRSM (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
+ * 2 the smallest row group (one row per work item), 3 column panels of 4 columns and column tiles of 4 (the seams between
+ * panels and tiles then occur at small k). */
+void exblas_set_trsm_path(int mode);
+/* The most recent ExTRSM on this device: out[0] outputs (i, j) rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == n * k for fpe != 1 (both 0 for fpe == 1); all 0 after a
+ * call that launched nothing.  Synchronises the device; valid until the next call that uses the workspace.  Returns 0, a
+ * hipError_t, or EXBLAS_SPTRSV_STALLED as exblas_last_sptrsv_info does. */
+int exblas_last_trsm_info(int64_t *out4);
 /* ExBDOT: exact, reproducible inner products of two dense ROW-MAJOR blocks on device pointers, both read once.  X is
  * n x p with leading dimension ldx >= p, Y is n x q with ldy >= q.
  *   mode 'G' (Gram):      C[i * ldc + j] = Round( sum_r X[r, i] * Y[r, j] ),  C p x q row-major, ldc >= q
@@ -445,6 +483,8 @@ int exblas_exgemv_ctx(exblas_ctx_t *ctx, char transa, int m, int n, double alpha
                       void *stream);
 int exblas_extrsv_ctx(exblas_ctx_t *ctx, char uplo, char transa, char diag, int n, const double *d_a, int lda,
                       double *d_x, int incx, int fpe, int early_exit, void *stream);
+int exblas_extrsm_ctx(exblas_ctx_t *ctx, char uplo, char transa, char diag, int n, int k, const double *d_a, int lda,
+                      double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
 int exblas_exgemm_ctx(exblas_ctx_t *ctx, char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc,
                       int fpe, int early_exit, void *stream);
@@ -615,6 +655,12 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
  * (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see exblas_last_sptrsm_info). */
 int exblas_exsptrsm_csr(char uplo, char diag, int m, int k, int index_bits, const void *row_ptr, const void *col_idx,
                         const double *val, double *x, int64_t ldx, int fpe, int early_exit);
+/* exblas_extrsm_dev on host arrays (a: the n columns of lda; x: the n x k row-major block with leading dimension ldx, B on
+ * entry, the solution on return; its padding comes back as it went): staged through the device, synchronous.  Returns 0,
+ * hipErrorInvalidValue, EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched) or EXBLAS_SPTRSV_STALLED (see
+ * exblas_last_trsm_info). */
+int exblas_extrsm(char uplo, char transa, char diag, int n, int k, const double *a, int lda, double *x, int64_t ldx,
+                  int fpe, int early_exit);
 /* exblas_exbdot_dev on host arrays (X: n rows of ldx, Y: n rows of ldy, C: p rows of ldc in 'G', p doubles in 'D'; the
  * padding of C keeps its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue. */
 int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
