@@ -1,7 +1,13 @@
-// sptrs_common.hip.h -- what the two sparse triangular solves (sptrsv.hip: ExSpTRSV, sptrsm.hip: ExSpTRSM) share: the
-// workspace header, the mailbox conventions (a reserved "not posted" pattern, the canonical NaN, agent-scope relaxed
-// atomic store and load, a wave-uniform poll loop with a light sleep and the 2 s watchdog), the preset kernel, the ticket
-// take, the classification of one stored entry, the counters and their flush, and the decoding of uplo / diag.
+// sptrs_common.hip.h -- what the three mailbox solves (sptrsv.hip: ExSpTRSV, sptrsm.hip: ExSpTRSM, trsm.hip: ExTRSM) share.
+// All three: the workspace header and its carving (st_workspace), the mailbox conventions (a reserved "not posted"
+// pattern, the canonical NaN, agent-scope relaxed atomic store and load, a wave-uniform poll loop with a light sleep and
+// the 2 s watchdog), the preset kernel, the ticket take, the counters and their flush, the rule for fpe, path and rounding
+// mode (st_rule), the grid size (st_grid), the decoding of uplo / diag.  The two sparse ones: the classification of one
+// stored entry.  The two block solves: the tile widths, the sink of a lane's expansion (StLaneSink) and the host loop
+// over the column panels (StPanel, st_block_solve).  Their lane geometry, publication and certify / fall-back blocks stay
+// one copy per file: the exact kernels sit at the SGPR limit, every shared spelling compiled changed the count of spilled
+// SGPRs they read back, and all of them together ran 1 to 4 % slower (profiles/block_solve_refactor_ab.md).  A change to
+// one copy has to be made in the other by hand.
 #pragma once
 #include "spmv_common.hip.h"
 
@@ -106,6 +112,18 @@ __device__ __forceinline__ void st_flush_counters(const StCounters &cn, long lon
     }
 }
 
+// ---- the block solves: lanes own columns ----
+
+constexpr int ST_TILE = 64;        // columns per tile ...
+constexpr int ST_TILE_SMALL = 4;   // ... and on path 3, where the panel is as narrow
+
+// a lane's expansion has no accumulator behind it: whatever would spill sends the column to the fallback loop
+struct StLaneSink {
+    unsigned &flags;
+    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
+    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
+};
+
 // ticket := 0, mailbox of n values := "not posted" (a kernel, not memset nodes: one node kind in a captured graph); with
 // `first` the whole header is cleared: the counters and the watchdog flag, which add up over the launches that follow
 static __global__ void __launch_bounds__(SP_BLOCK) k_sptrs_preset(long long n, int first, long long *__restrict__ hdr,
@@ -116,11 +134,39 @@ static __global__ void __launch_bounds__(SP_BLOCK) k_sptrs_preset(long long n, i
     for (long long i = i0; i < n; i += (long long)gridDim.x * SP_BLOCK) xq[i] = ST_EMPTY;
 }
 
+// blocks of a persistent kernel (or of the preset) over `nitems` items, `per` of them to a block
+static inline int st_grid(const Ctx &c, long long nitems, int per)
+{
+    return (int)min((long long)c.num_cu * 8, (nitems + per - 1) / per);
+}
+
 static inline hipError_t st_preset(const Ctx &c, long long n, int first, long long *hdr, double *xq, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_sptrs_preset, dim3((int)min((long long)c.num_cu * 8, (n + SP_BLOCK - 1) / SP_BLOCK)), dim3(SP_BLOCK),
-                       0, st, n, first, hdr, (long long *)xq);
+    hipLaunchKernelGGL(k_sptrs_preset, dim3(st_grid(c, n, SP_BLOCK)), dim3(SP_BLOCK), 0, st, n, first, hdr, (long long *)xq);
     return hipGetLastError();
+}
+
+// the workspace of a solve: the header, then the mailbox of `slots` doubles
+struct StSpace {
+    long long *hdr;
+    double *xq;
+};
+static inline hipError_t st_workspace(Ctx &c, size_t slots, hipStream_t st, StSpace &w)
+{
+    hipError_t e = hipSuccess;
+    char *base = (char *)workspace(c, ST_HDR_BYTES + slots * sizeof(double), st, &e);
+    if (base) w = {(long long *)base, (double *)(base + ST_HDR_BYTES)};
+    return base ? hipSuccess : e;
+}
+
+// fpe: 0 every output from the integer accumulator, 1 the plain solve, 2..8 the expansions; path 1 and the reference
+// rounding mode send every output through the accumulator as well; the path it was made for travels with it
+struct StRule {
+    int force_fb, round_mode, path;
+};
+static inline StRule st_rule(int fpe, int path, int round_mode)
+{
+    return {(fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0, fpe == 1 ? 0 : round_mode, path};
 }
 
 // 'U' solves in reverse row order; diag 'U' divides by nothing
@@ -141,6 +187,49 @@ static inline long long watchdog_ticks(int device)
         khz = 100000;   // the constant 100 MHz counter of gfx9
     }
     return 2000ll * khz;
+}
+
+// One column panel of a block solve, as its launch sees it: kp columns from j0 on in `tiles` tiles of 1 << lg, items of
+// R rows, first: the first panel of the call
+struct StPanel {
+    int kp, lg, tiles, R, first;
+    long long j0, limit;
+    StOrient o;
+    StRule rule;
+};
+
+// The host side of a block solve of n rows and k columns in items of R rows (1 on path 2).  Column panels, one after the
+// other in stream order: the largest multiple of 64 columns whose n x panel mailbox fits `budget` bytes, at least 64 (4 on
+// path 3).  Per panel the preset (the first one also clears the counters and the watchdog flag) and launch(P, grid, hdr,
+// xq), which fills the routine's argument struct and starts its ONE solve kernel.  info_dev: the header, once a preset has
+// run (nullptr: the call launched nothing).
+template <class Launch>
+static hipError_t st_block_solve(Ctx &c, const long long *&info_dev, int n, int k, int R, StOrient o, StRule rule,
+                                 size_t budget, hipStream_t st, Launch &&launch)
+{
+    info_dev = nullptr;
+    if (n == 0 || k == 0) return hipSuccess;
+    const int path = rule.path, tile = path == 3 ? ST_TILE_SMALL : ST_TILE;
+    const long long panel = path == 3 ? ST_TILE_SMALL : max(64ll, (long long)(budget / ((size_t)n * sizeof(double))) / 64 * 64);
+    StSpace w;
+    if (hipError_t e = st_workspace(c, (size_t)n * (size_t)min((long long)k, panel), st, w); e != hipSuccess) return e;
+    StPanel P;
+    P.R = path == 2 ? 1 : R;
+    P.limit = watchdog_ticks(c.device);
+    P.o = o;
+    P.rule = rule;
+    for (P.j0 = 0; P.j0 < k; P.j0 += panel) {
+        P.kp = (int)min(panel, (long long)k - P.j0);
+        P.lg = 0;
+        while ((1 << P.lg) < min(P.kp, tile)) ++P.lg;
+        P.tiles = (P.kp + (1 << P.lg) - 1) >> P.lg;
+        P.first = P.j0 == 0;
+        const long long nitems = (((long long)n + P.R - 1) / P.R) * P.tiles;
+        if (hipError_t e = st_preset(c, (long long)n * P.kp, P.first, w.hdr, w.xq, st); e != hipSuccess) return e;
+        info_dev = w.hdr;
+        if (hipError_t e = launch(P, st_grid(c, nitems, SP_WAVES), w.hdr, w.xq); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace exb

@@ -40,6 +40,9 @@
 //
 // Watchdog: that of sptrsv.hip (2 s on one poll, the header flag, everything behind it drains as NaN).
 // fpe == 1 runs the same structure with plain fp64 sums in a fixed order (deterministic, not exact).
+// sptrs_common.hip.h holds what is shared with trsm.hip (StLaneSink, the tile widths, the host loop st_block_solve).  The
+// lane geometry, the publication of a solved value and the certify / fall-back block are the same text in both files:
+// a fix to one goes into the other (sptrs_common.hip.h says why they are not one helper).
 #include "../../include/exblas_hip.h"
 #include "sptrs_common.hip.h"
 
@@ -49,15 +52,6 @@ namespace {
 constexpr int TM_R = 8;            // rows per item
 constexpr int TM_U = 4;            // stored entries per slice and step (mailbox loads in flight per lane)
 constexpr int TM_STAGE = 256;      // entries of an item that are staged in LDS (a wave's: 4 KiB)
-constexpr int TM_TILE = 64;        // columns per tile ...
-constexpr int TM_TILE_SMALL = 4;   // ... and on path 3, where the panel is as narrow
-
-// a lane's expansion has no accumulator behind it: whatever would spill sends the column to the fallback loop
-struct TmSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
-};
 
 struct TmArgs {
     int m, kp, lg, tiles, rev, unit, force_fb, round_mode, count;   // count: this panel counts the structure
@@ -102,7 +96,7 @@ __device__ __forceinline__ void tm_row(const TmArgs &A, bool count, long long po
     while (ns < S && (long long)ns * TM_U < p1 - p0) ns <<= 1;
     unsigned flags = 0;
     long long kdiag = ST_NO_DIAG;
-    TmSink sink{flags};
+    StLaneSink sink{flags};
     StCounters seen;   // the structure of the row as this lane met it
     double f[SP_N];
 #pragma unroll
@@ -323,63 +317,27 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sptrsm(TmArgs A, int R, const I *_
 
 }  // namespace
 
-// columns per panel: the largest multiple of 64 whose m x panel mailbox fits the budget, at least 64 (4 on path 3)
-static long long sptrsm_panel(int m, int path)
-{
-    if (path == 3) return TM_TILE_SMALL;
-    const long long fit = (long long)(EXBLAS_SPTRSM_MAILBOX_BYTES / ((size_t)m * sizeof(double)));
-    return max(64ll, fit / 64 * 64);
-}
-
 hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *row_ptr,
                              const void *col_idx, const double *val, double *x, long long ldx, int fpe, int early_exit,
                              int round_mode, hipStream_t st)
 {
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
-    c.sptrsm_info_dev = nullptr;
-    if (m == 0 || k == 0) return hipSuccess;
-    const int path = c.sptrsm_path;
-    const long long panel = sptrsm_panel(m, path);
-    const int tile = path == 3 ? TM_TILE_SMALL : TM_TILE;
-    // workspace: the header, then the mailbox of m x min(k, panel) doubles
-    hipError_t e;
-    char *base = (char *)workspace(c, ST_HDR_BYTES + (size_t)m * (size_t)min((long long)k, panel) * sizeof(double), st, &e);
-    if (!base) return e;
-    long long *hdr = (long long *)base;
-    double *xq = (double *)(base + ST_HDR_BYTES);
-    const int R = path == 2 ? 1 : TM_R;
-    TmArgs A;
-    A.m = m;
-    const StOrient o = st_orient(uplo, diag);
-    A.rev = o.rev;
-    A.unit = o.unit;
-    A.force_fb = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
-    A.round_mode = fpe == 1 ? 0 : round_mode;
-    A.ldx = ldx;
-    A.limit = watchdog_ticks(c.device);
-    return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
-        constexpr bool PLAIN = decltype(plain)::value;
-        using I = std::remove_cv_t<std::remove_pointer_t<decltype(rp)>>;
-        for (long long j0 = 0; j0 < k; j0 += panel) {   // panels one after the other, in stream order
-            A.kp = (int)min(panel, (long long)k - j0);
-            A.lg = 0;
-            while ((1 << A.lg) < min(A.kp, tile)) ++A.lg;
-            A.tiles = (A.kp + (1 << A.lg) - 1) >> A.lg;
-            A.count = j0 == 0;
-            const long long n = (long long)m * A.kp, nitems = (((long long)m + R - 1) / R) * A.tiles;
-            if (hipError_t le = st_preset(c, n, j0 == 0 ? 1 : 0, hdr, xq, st); le != hipSuccess) return le;
-            c.sptrsm_info_dev = hdr;
-            const int grid = (int)min((long long)c.num_cu * 8, (nitems + SP_WAVES - 1) / SP_WAVES);
+    auto launch = [&](const StPanel &P, int grid, long long *hdr, double *xq) {
+        const TmArgs A{m, P.kp, P.lg, P.tiles, P.o.rev, P.o.unit, P.rule.force_fb, P.rule.round_mode, P.first, ldx, P.limit};
+        return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
+            constexpr bool PLAIN = decltype(plain)::value;
+            using I = std::remove_cv_t<std::remove_pointer_t<decltype(rp)>>;
             if (A.lg == 6)
-                hipLaunchKernelGGL((k_sptrsm<true, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, A, R, rp, ci, val, x + j0,
+                hipLaunchKernelGGL((k_sptrsm<true, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, A, P.R, rp, ci, val, x + P.j0,
                                    hdr, xq);
             else
-                hipLaunchKernelGGL((k_sptrsm<false, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, A, R, rp, ci, val, x + j0,
+                hipLaunchKernelGGL((k_sptrsm<false, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, A, P.R, rp, ci, val, x + P.j0,
                                    hdr, xq);
-            if (hipError_t le = hipGetLastError(); le != hipSuccess) return le;
-        }
-        return hipSuccess;
-    });
+            return hipGetLastError();
+        });
+    };
+    return st_block_solve(c, c.sptrsm_info_dev, m, k, TM_R, st_orient(uplo, diag), st_rule(fpe, c.sptrsm_path, round_mode),
+                          EXBLAS_SPTRSM_MAILBOX_BYTES, st, launch);
 }
 
 }  // namespace exb

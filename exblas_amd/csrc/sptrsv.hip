@@ -38,6 +38,7 @@
 // another wave) raises the header flag, takes the canonical NaN for what it waited for and goes on, so everything
 // behind it drains as NaN and the host reports the call as failed.  No valid input reaches it.
 // fpe == 1 runs the same structure with plain fp64 sums in a fixed order (deterministic, not exact).
+// The workspace, the fpe / path / rounding-mode rule and the grid (st_workspace, st_rule, st_grid) are sptrs_common.hip.h's.
 #include "sptrs_common.hip.h"
 
 namespace exb {
@@ -303,23 +304,18 @@ hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits
     c.sptrsv_info_dev = nullptr;
     if (m == 0) return hipSuccess;
     const StOrient o = st_orient(uplo, diag);
-    // workspace: the header, then the mailbox of m doubles
-    hipError_t e;
-    char *base = (char *)workspace(c, ST_HDR_BYTES + (size_t)m * sizeof(double), st, &e);
-    if (!base) return e;
-    long long *hdr = (long long *)base;
-    double *xq = (double *)(base + ST_HDR_BYTES);
-    if ((e = st_preset(c, m, 1, hdr, xq, st)) != hipSuccess) return e;
-    c.sptrsv_info_dev = hdr;
+    StSpace w;   // the mailbox holds m doubles
+    if (hipError_t e = st_workspace(c, (size_t)m, st, w); e != hipSuccess) return e;
+    if (hipError_t e = st_preset(c, m, 1, w.hdr, w.xq, st); e != hipSuccess) return e;
+    c.sptrsv_info_dev = w.hdr;
     const int R = c.sptrsv_path == 2 ? 1 : ST_R;
-    const int force_fb = (fpe == 0 || c.sptrsv_path == 1 || round_mode) ? 1 : 0;
+    const StRule rule = st_rule(fpe, c.sptrsv_path, round_mode);
     const long long nitems = ((long long)m + R - 1) / R, limit = watchdog_ticks(c.device);
-    const int grid = (int)min((long long)c.num_cu * 8, (nitems + SP_WAVES - 1) / SP_WAVES);
+    const int grid = st_grid(c, nitems, SP_WAVES);
     return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
-        constexpr bool PLAIN = decltype(plain)::value;
         using I = std::remove_cv_t<std::remove_pointer_t<decltype(rp)>>;
-        hipLaunchKernelGGL((k_sptrsv<PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, rp, ci, val, x, o.rev, o.unit, R,
-                           PLAIN ? 0 : force_fb, PLAIN ? 0 : round_mode, limit, hdr, xq);
+        hipLaunchKernelGGL((k_sptrsv<decltype(plain)::value, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, rp, ci, val, x, o.rev,
+                           o.unit, R, rule.force_fb, rule.round_mode, limit, w.hdr, w.xq);
         return hipGetLastError();
     });
 }

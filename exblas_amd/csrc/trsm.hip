@@ -45,6 +45,9 @@
 //
 // Watchdog: that of the sparse solves (2 s on one poll, the header flag, everything behind it drains as NaN).
 // fpe == 1 runs the same structure with plain fp64 sums in a fixed order (deterministic, not exact).
+// sptrs_common.hip.h holds what is shared with sptrsm.hip (StLaneSink, the tile widths, the host loop st_block_solve).  The
+// lane geometry, the publication of a solved value and the certify / fall-back block are the same text in both files:
+// a fix to one goes into the other (sptrs_common.hip.h says why they are not one helper).
 #include "../../include/exblas_hip.h"
 #include "sptrs_common.hip.h"
 
@@ -55,17 +58,8 @@ constexpr int TR_R = 4;            // rows per item: four 4-term expansions per 
 constexpr int TR_U = 4;            // columns of op(A) per slice and step (mailbox loads in flight per lane)
 constexpr int TR_CH = 64;          // columns of op(A) in a staged tile
 constexpr int TR_PITCH = 72;       // doubles per staged row: the 'N' fill (4 rows x 16 columns per store) meets no bank twice
-constexpr int TR_TILE = 64;        // columns of X per tile ...
-constexpr int TR_TILE_SMALL = 4;   // ... and on path 3, where the panel is as narrow
 static_assert(TR_R == 4, "tr_stage's 'N' fill is written for 4 rows x 16 columns per load");
 static_assert(TR_U >= TR_R, "one step takes the previous item's rows");
-
-// a lane's expansion has no accumulator behind it: whatever would spill sends the column to the fallback loop
-struct TrSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
-};
 
 struct TrArgs {
     int n, kp, lg, tiles, rev, unit, force_fb, round_mode, R;
@@ -213,7 +207,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                     }
                 }
                 if constexpr (!PLAIN) {
-                    TrSink sink{flags[r]};
+                    StLaneSink sink{flags[r]};
                     fpe_absorb_prod<SP_N, true, TR_U>(f[r], p, er, sink);
                 }
             }
@@ -237,7 +231,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                 if (leader) ps[r] += L.xs[r * 64 + g];
                 for (int st = G; st < 64; st <<= 1) ps[r] += __shfl_down(ps[r], st, 64);
             } else {
-                TrSink sink{flags[r]};
+                StLaneSink sink{flags[r]};
                 double bv[1] = {leader ? L.xs[r * 64 + g] : 0.0};
                 sp_absorb_beta(f[r], leader, 1.0, bv, 0, sink);
                 for (int st = G; st < 64; st <<= 1) sp_cascade_step(f[r], flags[r], st, (lane & (2 * st - 1)) < G, sink);
@@ -303,7 +297,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                     } else {
                         double p[1], er[1];
                         p[0] = two_prod(av, -v, er[0]);
-                        TrSink sink{flags[r2]};
+                        StLaneSink sink{flags[r2]};
                         fpe_absorb_prod<SP_N, true, 1>(f[r2], p, er, sink);
                     }
                 }
@@ -340,58 +334,25 @@ __global__ void __launch_bounds__(SP_BLOCK) k_trsm(TrArgs A, const double *__res
 
 }  // namespace
 
-// columns per panel: the largest multiple of 64 whose n x panel mailbox fits the budget, at least 64 (4 on path 3)
-static long long trsm_panel(int n, int path)
-{
-    if (path == 3) return TR_TILE_SMALL;
-    const long long fit = (long long)(EXBLAS_TRSM_MAILBOX_BYTES / ((size_t)n * sizeof(double)));
-    return max(64ll, fit / 64 * 64);
-}
-
 // fpe: 0 every output from the integer accumulator, 1 the plain solve, 2..8 the expansions (the caller refused the rest)
 hipError_t extrsm_dispatch(Ctx &c, char uplo, char transa, char diag, int n, int k, const double *a, int lda, double *x,
                            long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st)
 {
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
-    c.trsm_info_dev = nullptr;
-    if (n == 0 || k == 0) return hipSuccess;
-    const int path = c.trsm_path;
-    const long long panel = trsm_panel(n, path);
-    const int tile = path == 3 ? TR_TILE_SMALL : TR_TILE;
-    // workspace: the header, then the mailbox of n x min(k, panel) doubles
-    hipError_t e;
-    char *base = (char *)workspace(c, ST_HDR_BYTES + (size_t)n * (size_t)min((long long)k, panel) * sizeof(double), st, &e);
-    if (!base) return e;
-    long long *hdr = (long long *)base;
-    double *xq = (double *)(base + ST_HDR_BYTES);
     const bool lower = (uplo == 'L' || uplo == 'l'), trans = (transa == 'T' || transa == 't');
-    TrArgs A;
-    A.n = n;
-    A.rev = (lower != trans) ? 0 : 1;   // A**T of a lower matrix is upper: backward substitution
-    A.unit = (diag == 'U' || diag == 'u') ? 1 : 0;
-    A.rs = trans ? (long long)lda : 1ll;
-    A.cs = trans ? 1ll : (long long)lda;
-    A.R = path == 2 ? 1 : TR_R;
-    A.force_fb = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
-    A.round_mode = fpe == 1 ? 0 : round_mode;
-    A.ldx = ldx;
-    A.limit = watchdog_ticks(c.device);
-    for (long long j0 = 0; j0 < k; j0 += panel) {   // panels one after the other, in stream order
-        A.kp = (int)min(panel, (long long)k - j0);
-        A.lg = 0;
-        while ((1 << A.lg) < min(A.kp, tile)) ++A.lg;
-        A.tiles = (A.kp + (1 << A.lg) - 1) >> A.lg;
-        const long long nitems = (((long long)n + A.R - 1) / A.R) * A.tiles;
-        if (hipError_t le = st_preset(c, (long long)n * A.kp, j0 == 0 ? 1 : 0, hdr, xq, st); le != hipSuccess) return le;
-        c.trsm_info_dev = hdr;
-        const int grid = (int)min((long long)c.num_cu * 8, (nitems + SP_WAVES - 1) / SP_WAVES);
+    // A**T of a lower matrix is upper: backward substitution
+    const StOrient o{(lower != trans) ? 0 : 1, st_orient(uplo, diag).unit};
+    auto launch = [&](const StPanel &P, int grid, long long *hdr, double *xq) {
+        const TrArgs A{n, P.kp, P.lg, P.tiles, P.o.rev, P.o.unit, P.rule.force_fb, P.rule.round_mode, P.R,
+                       trans ? (long long)lda : 1ll, trans ? 1ll : (long long)lda, ldx, P.limit};
         if (fpe == 1)
-            hipLaunchKernelGGL((k_trsm<true>), dim3(grid), dim3(SP_BLOCK), 0, st, A, a, x + j0, hdr, xq);
+            hipLaunchKernelGGL((k_trsm<true>), dim3(grid), dim3(SP_BLOCK), 0, st, A, a, x + P.j0, hdr, xq);
         else
-            hipLaunchKernelGGL((k_trsm<false>), dim3(grid), dim3(SP_BLOCK), 0, st, A, a, x + j0, hdr, xq);
-        if (hipError_t le = hipGetLastError(); le != hipSuccess) return le;
-    }
-    return hipSuccess;
+            hipLaunchKernelGGL((k_trsm<false>), dim3(grid), dim3(SP_BLOCK), 0, st, A, a, x + P.j0, hdr, xq);
+        return hipGetLastError();
+    };
+    return st_block_solve(c, c.trsm_info_dev, n, k, TR_R, o, st_rule(fpe, c.trsm_path, round_mode),
+                          EXBLAS_TRSM_MAILBOX_BYTES, st, launch);
 }
 
 }  // namespace exb

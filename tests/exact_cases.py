@@ -15,6 +15,7 @@ Output classes (``classify``), in units of the result's least significant intege
   ``max``    the largest magnitude the case can produce (worst-case families only)
   ``other``  anything else (never present in a planted case)
 """
+import functools
 import math
 from fractions import Fraction
 from types import SimpleNamespace
@@ -757,6 +758,15 @@ TRSV_RAND = 5                          # random entries per planted row (against
 # ten blocks in both windows
 TRSV_CASES = ((40, 40, 20, False), (64, 400, 53, False), (65, 40, 53, False), (200, 400, 53, True), (130, 40, 30, True),
               (700, 400, 53, False), (714, 40, 53, False))
+# every (fpe, early_exit) variant of ExTRSV
+TRSV_VARIANTS = [(0, False), (2, False), (3, False), (4, False), (5, False), (6, False), (7, False), (8, False),
+                 (4, True), (6, True), (8, True)]
+
+
+@functools.lru_cache(maxsize=None)
+def planted_trsv_case(n, W, mbits, filler, unit):
+    """planted_trsv on a row of TRSV_CASES, built once per session for every test file that solves it"""
+    return planted_trsv(n, seed=21, W=W, mbits=mbits, filler=filler, unit=unit)
 
 
 def _p2(e):

@@ -72,6 +72,15 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
+def assert_bits(got, want, what):
+    """bit equality of two arrays of doubles; a NaN matches a NaN (the contracts fix no payload)"""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = (bits(got) != bits(want)) & ~(np.isnan(got) & np.isnan(want))
+    where = np.argwhere(bad)[:6]
+    assert not bad.any(), (what, int(bad.sum()), where.tolist(), got[bad][:6], want[bad][:6])
+
+
 def same_bits(got, want):
     """element-wise same_double on int64 views: equal bits, or both zero"""
     g, w = np.asarray(got, dtype=np.int64), np.asarray(want, dtype=np.int64)

@@ -3,9 +3,12 @@
 Every system is a dense logical lower-triangular (L, b) in substitution order, as exact_cases.planted_trsv and
 range_rows_trsv build them; the expected bits always come from exact_cases.trsv_exact on that dense matrix.  Nothing
 here does arithmetic on the values: the functions only place them."""
+import functools
 from types import SimpleNamespace
 
 import numpy as np
+
+import exact_cases as X
 
 
 def csr_of_triangular(L, uplo="L", itype=np.int64, shuffle=False, junk=False, diag_nan=False, keep=None, seed=0):
@@ -137,3 +140,18 @@ def with_second_diagonal(crow, col, val, value=np.nan):
         nval += val[int(crow[r]):int(crow[r + 1])].tolist() + [value]
         ncrow.append(len(ncol))
     return np.array(ncrow, dtype=crow.dtype), np.array(ncol, dtype=col.dtype), np.array(nval)
+
+
+@functools.lru_cache(maxsize=None)
+def planted_csr(n, W, mbits, filler, unit, uplo, itype, messy):
+    """csr_of_triangular of a planted system (exact_cases.planted_trsv_case), built once per session; messy: the entries
+    of each row shuffled, NaN junk in the other triangle and, under diag = 'U', NaN on the stored diagonal"""
+    c = X.planted_trsv_case(n, W, mbits, filler, unit)
+    return csr_of_triangular(c.L, uplo, itype, shuffle=messy, junk=messy, diag_nan=unit and messy, seed=n)
+
+
+def upload(csr, n):
+    """the device operand (crow, col, val, shape) of a CSR tuple"""
+    import torch
+    crow, col, val = csr[:3]
+    return (torch.from_numpy(crow).cuda(), torch.from_numpy(col).cuda(), torch.from_numpy(val).cuda(), (n, n))

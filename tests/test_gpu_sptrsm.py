@@ -17,7 +17,9 @@ import pytest
 import exact_cases as X
 import sptrsm_cases as M
 import sptrsv_cases as S
-from test_gpu_trsv_rounding_edges import _case   # the planted systems, built once per session
+from helpers import assert_bits as _same, bits as _bits
+from sptrsm_cases import planted_block as _block   # the blocks of the planted systems, built once per session
+from sptrsv_cases import planted_csr as _csr, upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -43,25 +45,6 @@ def ex():
     exblas_amd.load_library().exblas_set_round_mode(0)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same(got, want, what):
-    """bit equality; a NaN matches a NaN (the contract fixes no payload)"""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = (_bits(got) != _bits(want)) & ~(np.isnan(got) & np.isnan(want))
-    where = np.argwhere(bad)[:6]
-    assert not bad.any(), (what, int(bad.sum()), where.tolist(), got[bad][:6], want[bad][:6])
-
-
-def _upload(csr, n):
-    import torch
-    crow, col, val = csr[:3]
-    return (torch.from_numpy(crow).cuda(), torch.from_numpy(col).cuda(), torch.from_numpy(val).cuda(), (n, n))
-
-
 def _clear(ex):
     """the watchdog of the last ExSpTRSM is clear (the C entry returns 0, the Python one does not raise); the counters"""
     out = (ctypes.c_int64 * 4)()
@@ -73,20 +56,8 @@ def _clear(ex):
 
 def _solve(ex, A, B, idx, uplo, diag="N", fpe=8, ee=True, entry=None, pad=0, sentinel=-7.25):
     """logical B (n x k) in, logical X out, and the counters; pad: X is the view [:, :k] of a block pad columns wider"""
-    import torch
-    B = np.asarray(B)
-    n, k = B.shape
-    wide = np.full((n, k + pad), sentinel)
-    wide[idx, :k] = B
-    full = torch.from_numpy(wide).cuda()
-    x = full[:, :k] if pad else full
-    out = (entry or ex.exsptrsm_dev)(A, x, uplo, diag, fpe, ee)
-    assert out is x
-    info = _clear(ex)
-    back = full.cpu().numpy()
-    if pad:
-        assert (_bits(back[:, k:]) == _bits(np.full((n, pad), sentinel))).all(), "the padding was written"
-    return back[idx, :k], info
+    call = entry or ex.exsptrsm_dev
+    return M.solve_block(lambda x: call(A, x, uplo, diag, fpe, ee), lambda: _clear(ex), B, idx, pad, sentinel)
 
 
 def _sptrsv_skipped(ex, A, n, uplo, diag):
@@ -95,21 +66,6 @@ def _sptrsv_skipped(ex, A, n, uplo, diag):
     ex.set_sptrsv_path(0)
     ex.exsptrsv_dev(A, torch.ones(n, dtype=torch.float64, device="cuda"), uplo, diag)
     return ex.last_sptrsv_info()[3]
-
-
-@functools.lru_cache(maxsize=None)
-def _csr(n, W, mbits, filler, unit, uplo, itype, messy):
-    c = _case(n, W, mbits, filler, unit)
-    return S.csr_of_triangular(c.L, uplo, itype, shuffle=messy, junk=messy, diag_nan=unit and messy, seed=n)
-
-
-@functools.lru_cache(maxsize=None)
-def _block(case, unit, kmax):
-    """the widest block of a planted system and its expected solution; narrower blocks are prefixes of it"""
-    c = _case(*X.TRSV_CASES[case], unit)
-    blk = M.rhs_block(c, kmax)
-    blk.want = M.expected_block(c, blk)
-    return c, blk
 
 
 # ---------------------------------------------------------------------------------------------

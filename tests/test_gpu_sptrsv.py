@@ -15,7 +15,9 @@ import pytest
 
 import exact_cases as X
 import sptrsv_cases as S
-from test_gpu_trsv_rounding_edges import _case   # the planted systems, built once per session for both files
+from exact_cases import planted_trsv_case as _case   # the planted systems, built once per session for every file
+from helpers import assert_bits as _same, bits as _bits
+from sptrsv_cases import planted_csr as _csr, upload as _upload
 
 pytestmark = pytest.mark.gpu
 
@@ -37,24 +39,6 @@ def ex():
     exblas_amd.load_library().exblas_set_round_mode(0)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same(got, want, what):
-    """bit equality; a NaN matches a NaN (the contract fixes no payload)"""
-    got, want = np.asarray(got), np.asarray(want)
-    bad = (_bits(got) != _bits(want)) & ~(np.isnan(got) & np.isnan(want))
-    rows = np.nonzero(bad)[0][:6]
-    assert not bad.any(), (what, int(bad.sum()), rows.tolist(), got[rows], want[rows])
-
-
-def _upload(csr, n):
-    import torch
-    crow, col, val = csr[:3]
-    return (torch.from_numpy(crow).cuda(), torch.from_numpy(col).cuda(), torch.from_numpy(val).cuda(), (n, n))
-
-
 def _clear(ex):
     """the watchdog of the last call is clear (the C entry returns 0); returns the counters"""
     out = (ctypes.c_int64 * 4)()
@@ -72,12 +56,6 @@ def _solve(ex, A, b, idx, uplo, diag="N", fpe=8, ee=True, entry=None):
     assert out is x
     info = _clear(ex)
     return x.cpu().numpy()[idx], info
-
-
-@functools.lru_cache(maxsize=None)
-def _csr(n, W, mbits, filler, unit, uplo, itype, messy):
-    c = _case(n, W, mbits, filler, unit)
-    return S.csr_of_triangular(c.L, uplo, itype, shuffle=messy, junk=messy, diag_nan=unit and messy, seed=n)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -16,8 +16,10 @@ import numpy as np
 import pytest
 
 import exact_cases as X
+import sptrsm_cases as M
 import sptrsv_cases as S
-from test_gpu_sptrsm import _block   # the blocks of right-hand sides of the planted systems, built once per session
+from helpers import assert_bits as _same, bits as _bits
+from sptrsm_cases import planted_block as _block   # the blocks of the planted systems, built once per session
 
 pytestmark = pytest.mark.gpu
 
@@ -42,19 +44,6 @@ def ex():
     exblas_amd.load_library().exblas_set_round_mode(0)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same(got, want, what):
-    """bit equality; a NaN matches a NaN (the contract fixes no payload)"""
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = (_bits(got) != _bits(want)) & ~(np.isnan(got) & np.isnan(want))
-    where = np.argwhere(bad)[:6]
-    assert not bad.any(), (what, int(bad.sum()), where.tolist(), got[bad][:6], want[bad][:6])
-
-
 def _clear(ex):
     """the watchdog of the last ExTRSM is clear (the C entry returns 0, the Python one does not raise); the counters"""
     out = (ctypes.c_int64 * 4)()
@@ -76,20 +65,8 @@ def _matrix(L, uplo, trans, diag="N", lda_pad=0):
 
 def _solve(ex, A, B, idx, uplo, trans, diag="N", fpe=8, ee=True, entry=None, pad=0, sentinel=-7.25):
     """logical B (n x k) in, logical X out, and the counters; pad: X is the view [:, :k] of a block pad columns wider"""
-    import torch
-    B = np.asarray(B)
-    n, k = B.shape
-    wide = np.full((n, k + pad), sentinel)
-    wide[idx, :k] = B
-    full = torch.from_numpy(wide).cuda()
-    x = full[:, :k] if pad else full
-    out = (entry or ex.extrsm_dev)(A, x, uplo, trans, diag, fpe, ee)
-    assert out is x
-    info = _clear(ex)
-    back = full.cpu().numpy()
-    if pad:
-        assert (_bits(back[:, k:]) == _bits(np.full((n, pad), sentinel))).all(), "the padding was written"
-    return back[idx, :k], info
+    call = entry or ex.extrsm_dev
+    return M.solve_block(lambda x: call(A, x, uplo, trans, diag, fpe, ee), lambda: _clear(ex), B, idx, pad, sentinel)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -2,10 +2,10 @@
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from exact_cases import TRSV_VARIANTS
+from helpers import bits as _bits
 
-TRSV_VARIANTS = [(0, False), (2, False), (3, False), (4, False), (5, False), (6, False), (7, False), (8, False),
-                 (4, True), (6, True), (8, True)]
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -15,10 +15,6 @@ def ex():
     assert torch.cuda.is_available()
     exblas_amd.load_library().exblas_hip_init(-1)
     return exblas_amd
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def tri_system(oracle, uplo, n, seed, lda=None, dominant=False, unit=False, rng=(10, 0)):

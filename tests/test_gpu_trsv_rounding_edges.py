@@ -20,13 +20,12 @@ down (`trsv_must_round_as_integers`: derived from the certificate's 1.0000001 in
 accepted in registers fails even where round-to-even happens to give the right bits -- and on the control system (the
 same matrix, every planted b_i a quarter unit further from its tie) below a quarter of the rows, the bar
 test_extrsv_scaled_rows_and_columns uses.  Each test prints the counts it saw (pytest -s)."""
-import functools
-
 import numpy as np
 import pytest
 
 import exact_cases as X
-from test_gpu_trsv import TRSV_VARIANTS
+from exact_cases import TRSV_VARIANTS, planted_trsv_case as _case
+from helpers import bits as _bits
 
 pytestmark = pytest.mark.gpu
 
@@ -43,15 +42,6 @@ def ex():
     exblas_amd.load_library().exblas_hip_init(-1)
     yield exblas_amd
     exblas_amd.load_library().exblas_set_round_mode(0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(n, W, mbits, filler, unit):
-    return X.planted_trsv(n, seed=21, W=W, mbits=mbits, filler=filler, unit=unit)
 
 
 def _same(got, want, what, classes=None, gap=None):
