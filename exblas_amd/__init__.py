@@ -54,6 +54,7 @@ C_ABI_SYMBOLS = [
     "exblas_exbdot_dev", "exblas_exbdot_ctx", "exblas_exbdot", "exblas_set_bdot_path",
     "exblas_exbdot_export_dev", "exblas_exbdot_export_ctx", "exblas_exbdot_round_dev", "exblas_exbdot_round_ctx",
     "exblas_exbdot_allreduce_dev",
+    "exblas_exbgemm_dev", "exblas_exbgemm_ctx", "exblas_exbgemm", "exblas_set_bgemm_path", "exblas_last_bgemm_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -213,6 +214,12 @@ def load_library():
     L.exblas_exbdot_round_dev.argtypes = [C.c_char, i32, i32, vp, i32, vp, i64, vp]
     L.exblas_exbdot_round_ctx.argtypes = [vp] + L.exblas_exbdot_round_dev.argtypes
     L.exblas_exbdot_allreduce_dev.argtypes = [vp, C.c_char, i64, i32, i32, vp, i64, vp, i64, vp, i64, i32, i32, vp]
+    L.exblas_exbgemm_dev.argtypes = [i64, i32, i32, dbl, vp, i64, vp, i64, dbl, vp, i64, i32, i32, vp]
+    L.exblas_exbgemm_ctx.argtypes = [vp] + L.exblas_exbgemm_dev.argtypes
+    L.exblas_exbgemm.argtypes = [i64, i32, i32, dbl, vp, i64, vp, i64, dbl, vp, i64, i32, i32]
+    L.exblas_set_bgemm_path.argtypes = [i32]
+    L.exblas_set_bgemm_path.restype = None
+    L.exblas_last_bgemm_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -693,6 +700,75 @@ def set_bdot_path(mode):
     load_library().exblas_set_bdot_path(int(mode))
 
 
+def _bgemm_block(name, t, rows=None, cols=None):
+    """The rules of one row-major block of a device ExBGEMM call (a block is never copied); returns (rows, cols)."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+        raise ValueError(f"exbgemm: {name} must be a float64 torch tensor")
+    if t.dim() != 2:
+        raise ValueError(f"exbgemm: {name} must be 2-D")
+    r, c = int(t.shape[0]), int(t.shape[1])
+    if (rows is not None and r != rows) or (cols is not None and c != cols):
+        want = ("n" if rows is None else str(rows), "q" if cols is None else str(cols))
+        raise ValueError(f"exbgemm: {name} must have shape ({want[0]}, {want[1]}), not ({r}, {c})")
+    if r > 0 and ((c > 1 and t.stride(1) != 1) or (r > 1 and t.stride(0) < c)):
+        raise ValueError(f"exbgemm: {name} must be row-major with stride(1) == 1 and stride(0) >= its column count")
+    return r, c
+
+
+def _bgemm_overlap(a, b):
+    """Whether two row-major blocks share an element.  Two views of one wider buffer (equal row strides) that take
+    different columns of it do not; otherwise the byte spans decide."""
+    spans = []
+    for t in (a, b):
+        r, c = int(t.shape[0]), int(t.shape[1])
+        if r == 0 or c == 0:
+            return False
+        spans.append((t.data_ptr(), t.data_ptr() + 8 * ((r - 1) * _ld(t, c) + c)))
+    if spans[0][0] >= spans[1][1] or spans[1][0] >= spans[0][1]:
+        return False
+    lda, ldb = _ld(a, int(a.shape[1])), _ld(b, int(b.shape[1]))
+    if lda == ldb and (spans[1][0] - spans[0][0]) % 8 == 0:
+        first = ((spans[1][0] - spans[0][0]) // 8) % lda     # the column of the shared buffer where b's rows start
+        return not (first >= int(a.shape[1]) and first + int(b.shape[1]) <= lda)
+    return True
+
+
+def _bgemm_args(X, Cm, alpha, beta, Y, fpe, early_exit):
+    """Validates a device ExBGEMM call before anything is launched; returns (Y, the C arguments up to the stream)."""
+    n, p = _bgemm_block("X", X)
+    _, q = _bgemm_block("C", Cm, rows=p)
+    if n > 0x7fffffff:
+        raise ValueError(f"exbgemm: n = {n} rows exceed INT_MAX")
+    if int(fpe) < 0:
+        raise ValueError("exbgemm: fpe must be >= 0")
+    if Y is not None:
+        _bgemm_block("Y", Y, rows=n, cols=q)
+    tensors = {"X": X, "C": Cm, **({} if Y is None else {"Y": Y})}
+    if len({t.device for t in tensors.values()}) != 1:
+        raise ValueError(f"exbgemm: {', '.join(tensors)} must be on one device")
+    if Y is not None:
+        for name, t in (("X", X), ("C", Cm)):
+            if _bgemm_overlap(t, Y):
+                raise ValueError(f"exbgemm: Y overlaps {name} (Y is updated in place while {name} is read)")
+    _on_gpu("exbgemm", **tensors)
+    if Y is None:
+        Y = _torch().zeros((n, q), dtype=X.dtype, device=X.device)
+    return Y, (n, p, q, float(alpha), _ptr(X), _ld(X, p), _ptr(Cm), _ld(Cm, q), float(beta), _ptr(Y), _ld(Y, q), int(fpe),
+               int(bool(early_exit)))
+
+
+def set_bgemm_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one row,
+    3 column tiles of 4 and chunks of 4 rows of C.  Same bits on every path."""
+    load_library().exblas_set_bgemm_path(int(mode))
+
+
+def last_bgemm_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last ExBGEMM."""
+    return _last_info("bgemm")
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
@@ -849,6 +925,17 @@ class Context:
         _check(load_library().exblas_exbdot_ctx(self.handle, *args, _stream_ptr(_torch())), "exbdot")
         return out
 
+    def exbgemm(self, X, C, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):  # noqa: N803
+        """ExBGEMM: Y = Round(alpha X C + beta Y) output by output, exact, reproducible and rounded once, stream-ordered on
+        the current stream: the block update that ends a block-Krylov iteration (X += P a, R -= Q a, P = Z + P b).  Bit for
+        bit exspmm_dev on X stored as a dense CSR matrix against C.  X (n x p), C (p x q) and Y (n x q) are 2-D float64
+        tensors with stride(1) == 1 and stride(0) >= their column count (a view [:, :k] of a wider block is fine; anything
+        else is refused, not copied); Y is updated in place and must not overlap X or C, or is allocated (zeros) when
+        None.  The design range is p, q <= 64.  Returns Y."""
+        Y, args = _bgemm_args(X, C, alpha, beta, Y, fpe, early_exit)
+        _check(load_library().exblas_exbgemm_ctx(self.handle, *args, _stream_ptr(_torch())), "exbgemm")
+        return Y
+
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
         """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
         [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
@@ -881,6 +968,7 @@ exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.
 extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
+exbgemm_dev = _default.exbgemm
 
 
 def gen_dev(kind, n, seed=1, p0=0.0, p1=0.0, first=0, count=None, n_total=None, out=None):
@@ -1126,6 +1214,25 @@ def exbdot(X, Y=None, mode="G", fpe=8, early_exit=True):
     _check(load_library().exblas_exbdot(mode.encode(), n, p, q, _hptr(X), max(p, 1), _hptr(Y), max(q, 1), _hptr(out),
                                         max(q, 1), int(fpe), int(bool(early_exit))), "exbdot")
     return out
+
+
+def exbgemm(X, C, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):  # noqa: N803
+    """ExBGEMM on host arrays: X (n x p), C (p x q) and Y (n x q, None: zeros) float64; returns the updated block (a new
+    n x q float64 array; the Y passed in is not changed)."""
+    X = np.ascontiguousarray(_dense_host("exbgemm", "X", X, 2))
+    Cm = np.ascontiguousarray(_dense_host("exbgemm", "C", C, 2))
+    n, p, q = int(X.shape[0]), int(X.shape[1]), int(Cm.shape[1])
+    if Cm.shape[0] != p:
+        raise ValueError(f"exbgemm: C must have p = {p} rows, not {Cm.shape[0]}")
+    if n > 0x7fffffff or int(fpe) < 0:
+        raise ValueError("exbgemm: n must not exceed INT_MAX and fpe must be >= 0")
+    Y = np.zeros((n, q)) if Y is None else np.array(Y, dtype=np.float64, copy=True, order="C")
+    if Y.shape != (n, q):
+        raise ValueError(f"exbgemm: Y must have shape ({n}, {q})")
+    _require_gpu()
+    _check(load_library().exblas_exbgemm(n, p, q, float(alpha), _hptr(X), max(p, 1), _hptr(Cm), max(q, 1), float(beta),
+                                         _hptr(Y), max(q, 1), int(fpe), int(bool(early_exit))), "exbgemm")
+    return Y
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

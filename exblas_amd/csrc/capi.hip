@@ -320,6 +320,7 @@ void exblas_set_sptrsv_path(int mode) { set_path(&CtxKnobs::sptrsv_path, mode, 2
 void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3); }
 void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
+void exblas_set_bgemm_path(int mode) { set_path(&CtxKnobs::bgemm_path, mode, 3); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -372,6 +373,27 @@ int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs:
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0 (a dense triangle
 // has no structure to count); EXBLAS_SPTRSV_STALLED as above
 int exblas_last_trsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::trsm_info_dev, true, out4); }
+
+// out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0; all 0 after a call
+// that launched nothing.  The kernel leaves one pair per workgroup (nothing has to be zeroed before it runs): they are
+// added up here.  Synchronises.
+int exblas_last_bgemm_info(int64_t *out4)
+{
+    if (!out4) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    Ctx &c = ctx(-1, g_last_layer[current_device()]);
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (!c.bgemm_info_dev || c.bgemm_info_blocks <= 0) return 0;
+    std::vector<long long> h((size_t)c.bgemm_info_blocks * 2);
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h.data(), c.bgemm_info_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return (int)e;
+    for (size_t b = 0; b < h.size(); b += 2) {
+        out4[0] += h[b];
+        out4[1] += h[b + 1];
+    }
+    return 0;
+}
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -556,6 +578,29 @@ static int extrsm_on(Ctx &c, char uplo, char transa, char diag, int n, int k, co
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)extrsm_dispatch(c, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of ExBGEMM, on host or device pointers alike.  *empty: nothing to compute (n == 0 or q == 0), which
+// is decided before the pointers are looked at.
+static int bgemm_check_args(int64_t n, int p, int q, const double *x, int64_t ldx, const double *cm, int64_t ldc,
+                            const double *y, int64_t ldy, int fpe, bool *empty)
+{
+    *empty = false;
+    if (n < 0 || n > 0x7fffffffll || p < 0 || q < 0 || fpe < 0) return (int)hipErrorInvalidValue;
+    if (ldx < p || ldc < q || ldy < q) return (int)hipErrorInvalidValue;
+    *empty = n == 0 || q == 0;
+    if (!*empty && (!y || (p > 0 && (!x || !cm)))) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int exbgemm_on(Ctx &c, int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
+                      int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // n == 0 or q == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = bgemm_check_args(n, p, q, d_x, ldx, d_c, ldc, d_y, ldy, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exbgemm_dispatch(c, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, round_mode(), st);
 }
 
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
@@ -805,6 +850,14 @@ int exblas_extrsm_ctx(exblas_ctx_t *h, char uplo, char transa, char diag, int n,
     return extrsm_on(*cp, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_exbgemm_ctx(exblas_ctx_t *h, int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx,
+                       const double *d_c, int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit,
+                       void *stream)
+{
+    EXB_HANDLE(h);
+    return exbgemm_on(*cp, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -872,6 +925,11 @@ int exblas_extrsm_dev(char uplo, char transa, char diag, int n, int k, const dou
                       int64_t ldx, int fpe, int early_exit, void *stream)
 {
     return exblas_extrsm_ctx(nullptr, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, stream);
+}
+int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
+                       int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream)
+{
+    return exblas_exbgemm_ctx(nullptr, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, stream);
 }
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
                       const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
@@ -1410,6 +1468,25 @@ int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t l
     double *d_c = hc.in(2, cspan * 8, cm, cspan * 8);
     return hc.out(exbdot_on(hc.c, mode, n, p, q, d_x, ldx, d_y, ldy, d_c, ldc, fpe, early_exit, hc.c.stream), cm, d_c,
                   cspan * 8);
+}
+
+// whole rows of X, C and Y travel, padding included (the last row of each only up to its last entry); Y comes back the
+// same way, so that its padding returns as it went
+int exblas_exbgemm(int64_t n, int p, int q, double alpha, const double *x, int64_t ldx, const double *cm, int64_t ldc,
+                   double beta, double *y, int64_t ldy, int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = bgemm_check_args(n, p, q, x, ldx, cm, ldc, y, ldy, fpe, &empty);
+    if (bad || empty) return bad;
+    HostCall hc("exblas_exbgemm");
+    const size_t xspan = p > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)p : 0;
+    const size_t cspan = p > 0 ? (size_t)(p - 1) * (size_t)ldc + (size_t)q : 0;
+    const size_t yspan = (size_t)(n - 1) * (size_t)ldy + (size_t)q;
+    double *d_x = hc.in(0, xspan * 8 + 8, x, xspan * 8);
+    double *d_c = hc.in(1, cspan * 8 + 8, cm, cspan * 8);
+    double *d_y = hc.in(2, yspan * 8, y, yspan * 8);
+    return hc.out(exbgemm_on(hc.c, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, hc.c.stream), y, d_y,
+                  yspan * 8);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

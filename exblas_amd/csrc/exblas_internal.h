@@ -35,6 +35,8 @@ struct CtxKnobs {
                              // per item, 3 column panels and tiles of 4 columns
     int trsm_path = 0;       // exblas_set_trsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
+    int bgemm_path = 0;      // exblas_set_bgemm_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
+                             // block of one row, 3 column tiles of 4 and chunks of 4 rows of C
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -53,6 +55,8 @@ struct CtxWsPtrs {
     const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
+    const long long *bgemm_info_dev = nullptr;   // the last ExBGEMM call's counter slots, a pair per workgroup (nullptr: it
+    int bgemm_info_blocks = 0;                   // launched nothing), and how many workgroups there were
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -217,6 +221,11 @@ hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, con
 // trsm.hip
 hipError_t extrsm_dispatch(Ctx &c, char uplo, char transa, char diag, int n, int k, const double *a, int lda, double *x,
                            long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// bgemm.hip
+hipError_t exbgemm_dispatch(Ctx &c, long long n, int p, int q, double alpha, const double *x, long long ldx,
+                            const double *cm, long long ldc, double beta, double *y, long long ldy, int fpe, int early_exit,
+                            int round_mode, hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
 struct I8Plan {

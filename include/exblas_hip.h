@@ -441,6 +441,42 @@ int exblas_exbdot_round_dev(char mode, int p, int q, const int64_t *d_sets, int 
  * kernel supports (4 waves x 64 / T rows, T the outputs of a tile: a few hundred rows are already merged from many
  * workgroups per output), 2 column panels ('D') and output tiles ('G') of width 4 (p, q = 5 then cross an edge). */
 void exblas_set_bdot_path(int mode);
+/* ExBGEMM: exact, reproducible block update Y = alpha X C + beta Y for dense ROW-MAJOR blocks on device pointers: X tall
+ * (n x p, leading dimension ldx >= p), C small (p x q, ldc >= q), Y tall (n x q, ldy >= q, updated in place) -- the last
+ * step of a block-Krylov iteration (X += P a, R -= Q a, P = Z + P b, W -= V (V^T W)).
+ *     Y[r, j] = Round( sum_{i<p} X[r, i] * fl(alpha * C[i, j])  (+)  beta * Y[r, j] )
+ * Every output is, bit for bit, what exblas_exspmm_csr_dev writes for the CSR matrix that stores X densely
+ * (row_ptr[r] = r p, col_idx = 0 .. p-1, values = the row of X) against C as its dense block, with everything said there:
+ * both rounding modes (exblas_set_round_mode), alpha folded into C by one rounded multiply, beta = 0 ignores Y (NaN
+ * included), beta = 1 adds it exactly, any other beta adds the error-free product, ExGEMV's product domain and non-finite
+ * rules.  Every entry of X counts, so a zero in X times an Inf in C is NaN.  p == 0 gives Round(0 (+) beta Y), +0.0 for
+ * beta = 0.  The sum and the beta term are rounded ONCE (exblas_exgemm_dev rounds the sum, then adds beta * C in fp64).
+ * The bits depend on the data and the rounding mode only: not on n, q, ldx / ldc / ldy, the row block, the column tile,
+ * the chunk of C, the grid, fpe (0 or >= 2), early_exit (also with fpe > 8, as in exblas_exspmm_csr_dev), the path
+ * (exblas_set_bgemm_path), the context or the stream.  fpe == 0 rounds every output from an integer accumulator; fpe == 1
+ * is the plain fp64 product on the same structure (deterministic, not exact).
+ * Rows are independent: a NaN or Inf in row r of X changes only row r of Y, one in column j of C only column j.  The
+ * padding of X and C is never read, the padding of Y never written.  X and C must not overlap Y.  All offsets (row * ld)
+ * are 64-bit.  With C replicated, a row-sharded caller needs no communication: each rank updates its own rows.
+ * Any p and q are served (q beyond 64 in column tiles of 64, p beyond 64 in chunks of 64 rows of C, staged again per row
+ * block); the design range is up to 64 each.  n == 0 or q == 0: success, nothing is launched.  n, p or q < 0,
+ * n > INT_MAX, ldx < p, ldc < q, ldy < q or fpe < 0: hipErrorInvalidValue.
+ * ONE stream-ordered kernel launch and nothing else: no memset, no host synchronisation.  The only workspace is that of
+ * the info counters: 16 bytes per workgroup, at most 128 bytes per compute unit, which the kernel stores without needing
+ * them cleared and exblas_last_bgemm_info adds up.  Capturable into a hipGraph after exblas_reserve_workspace or one call.
+ * Returns 0 or a hipError_t.
+ * Not provided: transposes of X or C, column-major blocks, fp32, p or q far beyond 64 (served, not designed for). */
+int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
+                       int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
+/* Test hook for ExBGEMM (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
+ * 2 a register block of one row (one row per lane), 3 column tiles of 4 and chunks of 4 rows of C (the seams between
+ * tiles and chunks then occur at small p and q). */
+void exblas_set_bgemm_path(int mode);
+/* The most recent ExBGEMM on this device: out[0] outputs (r, j) rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == n * q for fpe != 1 (both 0 for fpe == 1); all 0 after a
+ * call that launched nothing.  Synchronises the device; valid until the next call that uses the workspace.  Returns 0 or
+ * a hipError_t. */
+int exblas_last_bgemm_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -501,6 +537,9 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
 int exblas_exbdot_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                       const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
+int exblas_exbgemm_ctx(exblas_ctx_t *ctx, int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx,
+                       const double *d_c, int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit,
+                       void *stream);
 int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
 int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
@@ -665,6 +704,10 @@ int exblas_extrsm(char uplo, char transa, char diag, int n, int k, const double 
  * padding of C keeps its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue. */
 int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t ldx, const double *y, int64_t ldy,
                   double *c, int64_t ldc, int fpe, int early_exit);
+/* exblas_exbgemm_dev on host arrays (X: n rows of ldx, C: p rows of ldc, Y: n rows of ldy, updated in place; the padding
+ * of Y keeps its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue. */
+int exblas_exbgemm(int64_t n, int p, int q, double alpha, const double *x, int64_t ldx, const double *c, int64_t ldc,
+                   double beta, double *y, int64_t ldy, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
