@@ -55,6 +55,7 @@ C_ABI_SYMBOLS = [
     "exblas_exbdot_export_dev", "exblas_exbdot_export_ctx", "exblas_exbdot_round_dev", "exblas_exbdot_round_ctx",
     "exblas_exbdot_allreduce_dev",
     "exblas_exbgemm_dev", "exblas_exbgemm_ctx", "exblas_exbgemm", "exblas_set_bgemm_path", "exblas_last_bgemm_info",
+    "exblas_exbtrsm_dev", "exblas_exbtrsm_ctx", "exblas_exbtrsm", "exblas_set_btrsm_path", "exblas_last_btrsm_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -220,6 +221,12 @@ def load_library():
     L.exblas_set_bgemm_path.argtypes = [i32]
     L.exblas_set_bgemm_path.restype = None
     L.exblas_last_bgemm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exbtrsm_dev.argtypes = [C.c_char, C.c_char, C.c_char, i64, i32, dbl, vp, i32, vp, i64, i32, i32, vp]
+    L.exblas_exbtrsm_ctx.argtypes = [vp] + L.exblas_exbtrsm_dev.argtypes
+    L.exblas_exbtrsm.argtypes = [C.c_char, C.c_char, C.c_char, i64, i32, dbl, vp, i32, vp, i64, i32, i32]
+    L.exblas_set_btrsm_path.argtypes = [i32]
+    L.exblas_set_btrsm_path.restype = None
+    L.exblas_last_btrsm_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -483,15 +490,16 @@ def last_sptrsm_info():
     return _last_info("sptrsm")
 
 
-def _trsm_layout(A, uplo, trans):
+def _trsm_layout(A, uplo, trans, who="extrsm"):
     """How ExTRSM reads the 2-D operand A (anything with shape and stride(i), strides in elements) without copying it:
     returns (uplo, trans, lda) for the C call, which takes column-major storage.  `uplo` names the triangle of A[i, j] as
     Python indexes it.  stride(0) == 1 is column-major, lda = stride(1); stride(1) == 1 is row-major, the column-major
-    storage of A^T: the other triangle, the other trans, lda = stride(0)."""
+    storage of A^T: the other triangle, the other trans, lda = stride(0).  `who` names the routine in the messages
+    (ExBTRSM reads its triangle the same way)."""
     if not isinstance(uplo, str) or uplo not in ("L", "l", "U", "u"):
-        raise ValueError(f"extrsm: uplo must be 'L' or 'U', got {uplo!r}")
+        raise ValueError(f"{who}: uplo must be 'L' or 'U', got {uplo!r}")
     if not isinstance(trans, str) or trans not in ("N", "n", "T", "t"):
-        raise ValueError(f"extrsm: trans must be 'N' or 'T', got {trans!r}")
+        raise ValueError(f"{who}: trans must be 'N' or 'T', got {trans!r}")
     uplo, trans = uplo.upper(), trans.upper()
     n = int(A.shape[0])
     s0, s1 = int(A.stride(0)), int(A.stride(1))
@@ -501,7 +509,7 @@ def _trsm_layout(A, uplo, trans):
         return uplo, trans, s1
     if s1 == 1 and s0 >= n:
         return ("U" if uplo == "L" else "L"), ("T" if trans == "N" else "N"), s0
-    raise ValueError(f"extrsm: A must have one unit stride and the other >= n = {n} (it is not copied), got strides "
+    raise ValueError(f"{who}: A must have one unit stride and the other >= n = {n} (it is not copied), got strides "
                      f"({s0}, {s1})")
 
 
@@ -769,6 +777,68 @@ def last_bgemm_info():
     return _last_info("bgemm")
 
 
+BTRSM_MAX_P = 512  # EXBLAS_BTRSM_MAX_P: a wider triangle is refused
+
+
+def _btrsm_fpe(fpe):
+    fpe = int(fpe)
+    if fpe < 0 or fpe >= 9:
+        raise ValueError(f"exbtrsm: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
+    return fpe
+
+
+def _btrsm_triangle(T, shape, stride_of, uplo, trans, diag):
+    """The rules of the triangle of an ExBTRSM call, device or host: square, at most BTRSM_MAX_P wide, one unit stride;
+    returns (uplo, trans, diag, p, ldt) for the C call."""
+    if len(shape) != 2:
+        raise ValueError("exbtrsm: T must be 2-D")
+    p = int(shape[0])
+    if shape[1] != p:
+        raise ValueError(f"exbtrsm: T must be square, got shape {tuple(shape)}")
+    if p > BTRSM_MAX_P:
+        raise ValueError(f"exbtrsm: p = {p} exceeds EXBLAS_BTRSM_MAX_P = {BTRSM_MAX_P}")
+    u, t, ldt = _trsm_layout(stride_of, uplo, trans, "exbtrsm")
+    _, d = _solve_flags("exbtrsm", "L", diag)
+    return u.encode(), t.encode(), d, p, max(ldt, 1)
+
+
+def _btrsm_args(T, X, uplo, trans, diag, alpha, fpe, early_exit):
+    """Validates a device ExBTRSM call before anything is launched (no GPU needed for that); returns the C arguments up
+    to the stream.  Neither operand is copied."""
+    torch = _torch()
+    for name, t in (("T", T), ("X", X)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"exbtrsm: {name} must be a float64 torch tensor")
+    if X.dim() != 2:
+        raise ValueError("exbtrsm: X must be 2-D (n x p, one row per system)")
+    u, t, d, p, ldt = _btrsm_triangle(T, tuple(T.shape), T, uplo, trans, diag)
+    n = int(X.shape[0])
+    if X.shape[1] != p:
+        raise ValueError(f"exbtrsm: X must have p = {p} columns, not {int(X.shape[1])}")
+    # a block that does not conform is refused, not copied: it is solved in place
+    if n > 0 and ((p > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < p)):
+        raise ValueError("exbtrsm: X must be row-major with stride(1) == 1 and stride(0) >= p (its rows must not overlap; "
+                         "it is solved in place)")
+    fpe = _btrsm_fpe(fpe)
+    if T.device != X.device:
+        raise ValueError("exbtrsm: T, X must be on one device")
+    if _bgemm_overlap(T, X) if T.stride(1) == 1 else _bgemm_overlap(T.t(), X):
+        raise ValueError("exbtrsm: X overlaps T (X is solved in place while T is read)")
+    _on_gpu("exbtrsm", T=T, X=X)
+    return (u, t, d, n, p, float(alpha), _ptr(T), ldt, _ptr(X), _ld(X, max(p, 1)), fpe, int(bool(early_exit)))
+
+
+def set_btrsm_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one column,
+    3 four rows per wave item and chunks of 4 x 4 of T.  Same bits on every path."""
+    load_library().exblas_set_btrsm_path(int(mode))
+
+
+def last_btrsm_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last ExBTRSM."""
+    return _last_info("btrsm")
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
@@ -936,6 +1006,19 @@ class Context:
         _check(load_library().exblas_exbgemm_ctx(self.handle, *args, _stream_ptr(_torch())), "exbgemm")
         return Y
 
+    def exbtrsm(self, T, X, uplo="U", trans="N", diag="N", alpha=1.0, fpe=8, early_exit=True):  # noqa: N803
+        """ExBTRSM: solves X op(T) = alpha B in place on the tall n x p block X (B on entry) from the right, exact,
+        reproducible and rounded once per output, stream-ordered on the current stream: Q = X R^-1 of CholQR, the
+        normalisation of a block Krylov method.  With alpha = 1, row r is bit for bit what extrsv_dev gives for the other
+        trans on B[r, :].  T: a p x p float64 tensor with one unit stride, never copied -- column-major (stride(0) == 1) or
+        row-major (stride(1) == 1); `uplo` names the triangle of T[i, j] as Python indexes it, the other triangle is never
+        read; p <= 512.  X: a 2-D float64 tensor with stride(1) == 1 and stride(0) >= p (a view [:, :p] of a wider block
+        is fine: its padding is not touched; anything else is refused, not copied).  fpe: 0, 1 or 2..8.  One kernel launch,
+        no mailbox.  The design range is p <= 64.  Returns X."""
+        args = _btrsm_args(T, X, uplo, trans, diag, alpha, fpe, early_exit)
+        _check(load_library().exblas_exbtrsm_ctx(self.handle, *args, _stream_ptr(_torch())), "exbtrsm")
+        return X
+
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
         """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
         [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
@@ -969,6 +1052,7 @@ extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
 exbgemm_dev = _default.exbgemm
+exbtrsm_dev = _default.exbtrsm
 
 
 def gen_dev(kind, n, seed=1, p0=0.0, p1=0.0, first=0, count=None, n_total=None, out=None):
@@ -1233,6 +1317,26 @@ def exbgemm(X, C, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):  # noqa:
     _check(load_library().exblas_exbgemm(n, p, q, float(alpha), _hptr(X), max(p, 1), _hptr(Cm), max(q, 1), float(beta),
                                          _hptr(Y), max(q, 1), int(fpe), int(bool(early_exit))), "exbgemm")
     return Y
+
+
+def exbtrsm(T, B, uplo="U", trans="N", diag="N", alpha=1.0, fpe=8, early_exit=True):  # noqa: N803
+    """ExBTRSM on host arrays: T float64 of shape (p, p), C- or Fortran-ordered (anything else is copied to C order; `uplo`
+    names the triangle of T[i, j]), B float64 of shape (n, p); returns the solution of X op(T) = alpha B (a new n x p
+    float64 array; B is not changed)."""
+    T = _dense_host("exbtrsm", "T", T, 2)
+    if not (T.flags.c_contiguous or T.flags.f_contiguous):
+        T = np.ascontiguousarray(T)
+    u, t, d, p, ldt = _btrsm_triangle(T, T.shape, _HostStrides(T), uplo, trans, diag)
+    B = _dense_host("exbtrsm", "B", B, 2, " (n x p, one row per system; for one vector use extrsv)")
+    if B.shape[1] != p:
+        raise ValueError(f"exbtrsm: B must have p = {p} columns, not {B.shape[1]}")
+    fpe = _btrsm_fpe(fpe)
+    X = np.array(B, dtype=np.float64, copy=True, order="C")
+    n = int(X.shape[0])
+    _require_gpu()
+    _check(load_library().exblas_exbtrsm(u, t, d, n, p, float(alpha), _hptr(T), ldt, _hptr(X), max(p, 1), fpe,
+                                         int(bool(early_exit))), "exbtrsm")
+    return X
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

@@ -321,6 +321,7 @@ void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3
 void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
 void exblas_set_bgemm_path(int mode) { set_path(&CtxKnobs::bgemm_path, mode, 3); }
+void exblas_set_btrsm_path(int mode) { set_path(&CtxKnobs::btrsm_path, mode, 3); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -374,25 +375,36 @@ int exblas_last_sptrsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs:
 // has no structure to count); EXBLAS_SPTRSV_STALLED as above
 int exblas_last_trsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::trsm_info_dev, true, out4); }
 
-// out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0; all 0 after a call
-// that launched nothing.  The kernel leaves one pair per workgroup (nothing has to be zeroed before it runs): they are
-// added up here.  Synchronises.
-int exblas_last_bgemm_info(int64_t *out4)
+// The counters of the last ExBGEMM / ExBTRSM on the last-used layer: the kernel leaves one pair per workgroup (nothing
+// has to be zeroed before it runs), they are added up here.  All 0 after a call that launched nothing.  Synchronises.
+static int last_slot_info(const long long *CtxWsPtrs::*info_dev, int CtxWsPtrs::*blocks, int64_t *out4)
 {
     if (!out4) return (int)hipErrorInvalidValue;
     for (int i = 0; i < 4; ++i) out4[i] = 0;
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
     std::lock_guard<std::mutex> lk(c.mu);
-    if (!c.bgemm_info_dev || c.bgemm_info_blocks <= 0) return 0;
-    std::vector<long long> h((size_t)c.bgemm_info_blocks * 2);
+    if (!(c.*info_dev) || c.*blocks <= 0) return 0;
+    std::vector<long long> h((size_t)(c.*blocks) * 2);
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(h.data(), c.bgemm_info_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), c.*info_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return (int)e;
     for (size_t b = 0; b < h.size(); b += 2) {
         out4[0] += h[b];
         out4[1] += h[b + 1];
     }
     return 0;
+}
+
+// out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0
+int exblas_last_bgemm_info(int64_t *out4)
+{
+    return last_slot_info(&CtxWsPtrs::bgemm_info_dev, &CtxWsPtrs::bgemm_info_blocks, out4);
+}
+
+// the same for ExBTRSM
+int exblas_last_btrsm_info(int64_t *out4)
+{
+    return last_slot_info(&CtxWsPtrs::btrsm_info_dev, &CtxWsPtrs::btrsm_info_blocks, out4);
 }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
@@ -601,6 +613,31 @@ static int exbgemm_on(Ctx &c, int64_t n, int p, int q, double alpha, const doubl
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exbgemm_dispatch(c, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of ExBTRSM, on host or device pointers alike, before a device is touched; fpe >= 9 is refused as
+// ExTRSM refuses it.  *empty: nothing to compute (n == 0 or p == 0), which is decided before the pointers are looked at.
+static int btrsm_check_args(char uplo, char transt, char diag, int64_t n, int p, const double *t, int ldt, const double *x,
+                            int64_t ldx, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(uplo, "LlUu") || !one_of(transt, "NnTt") || !one_of(diag, "NnUu")) return (int)hipErrorInvalidValue;
+    if (n < 0 || p < 0 || p > EXBLAS_BTRSM_MAX_P || ldt < (p > 1 ? p : 1) || ldx < p || fpe < 0)
+        return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = n == 0 || p == 0;
+    if (!*empty && (!t || !x)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int exbtrsm_on(Ctx &c, char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *d_t, int ldt,
+                      double *d_x, int64_t ldx, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // n == 0 or p == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = btrsm_check_args(uplo, transt, diag, n, p, d_t, ldt, d_x, ldx, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exbtrsm_dispatch(c, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, round_mode(), st);
 }
 
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
@@ -858,6 +895,15 @@ int exblas_exbgemm_ctx(exblas_ctx_t *h, int64_t n, int p, int q, double alpha, c
     return exbgemm_on(*cp, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_exbtrsm_ctx(exblas_ctx_t *h, char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *d_t,
+                       int ldt, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = btrsm_check_args(uplo, transt, diag, n, p, d_t, ldt, d_x, ldx, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return exbtrsm_on(*cp, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -926,6 +972,12 @@ int exblas_extrsm_dev(char uplo, char transa, char diag, int n, int k, const dou
 {
     return exblas_extrsm_ctx(nullptr, uplo, transa, diag, n, k, d_a, lda, d_x, ldx, fpe, early_exit, stream);
 }
+int exblas_exbtrsm_dev(char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *d_t, int ldt,
+                       double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    return exblas_exbtrsm_ctx(nullptr, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, stream);
+}
+
 int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
                        int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream)
 {
@@ -1487,6 +1539,23 @@ int exblas_exbgemm(int64_t n, int p, int q, double alpha, const double *x, int64
     double *d_y = hc.in(2, yspan * 8, y, yspan * 8);
     return hc.out(exbgemm_on(hc.c, n, p, q, alpha, d_x, ldx, d_c, ldc, beta, d_y, ldy, fpe, early_exit, hc.c.stream), y, d_y,
                   yspan * 8);
+}
+
+// the p columns of T travel with their ldt padding (the last one only up to its p-th entry), and whole rows of X (the
+// last one only up to its p-th entry), which come back the same way: the padding of X returns as it went
+int exblas_exbtrsm(char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *t, int ldt, double *x,
+                   int64_t ldx, int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = btrsm_check_args(uplo, transt, diag, n, p, t, ldt, x, ldx, fpe, &empty);
+    if (bad || empty) return bad;
+    HostCall hc("exblas_exbtrsm");
+    const size_t tbytes = ((size_t)ldt * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)p) * sizeof(double);
+    double *d_t = hc.in(0, tbytes, t, tbytes);
+    double *d_x = hc.in(1, xbytes, x, xbytes);
+    return hc.out(exbtrsm_on(hc.c, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, hc.c.stream), x, d_x,
+                  xbytes);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

@@ -37,6 +37,8 @@ struct CtxKnobs {
                              // per item, 3 column panels and tiles of 4 columns
     int bgemm_path = 0;      // exblas_set_bgemm_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
                              // block of one row, 3 column tiles of 4 and chunks of 4 rows of C
+    int btrsm_path = 0;      // exblas_set_btrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
+                             // block of one column, 3 4 rows per wave item and chunks of 4 rows and columns of T
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -57,6 +59,8 @@ struct CtxWsPtrs {
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
     const long long *bgemm_info_dev = nullptr;   // the last ExBGEMM call's counter slots, a pair per workgroup (nullptr: it
     int bgemm_info_blocks = 0;                   // launched nothing), and how many workgroups there were
+    const long long *btrsm_info_dev = nullptr;   // the same for the last ExBTRSM call
+    int btrsm_info_blocks = 0;
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -226,6 +230,10 @@ hipError_t extrsm_dispatch(Ctx &c, char uplo, char transa, char diag, int n, int
 hipError_t exbgemm_dispatch(Ctx &c, long long n, int p, int q, double alpha, const double *x, long long ldx,
                             const double *cm, long long ldc, double beta, double *y, long long ldy, int fpe, int early_exit,
                             int round_mode, hipStream_t st);
+
+// btrsm.hip
+hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long n, int p, double alpha, const double *t,
+                            int ldt, double *x, long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
 struct I8Plan {

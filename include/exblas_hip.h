@@ -477,6 +477,46 @@ void exblas_set_bgemm_path(int mode);
  * call that launched nothing.  Synchronises the device; valid until the next call that uses the workspace.  Returns 0 or
  * a hipError_t. */
 int exblas_last_bgemm_info(int64_t *out4);
+/* ExBTRSM: exact, reproducible triangular solve FROM THE RIGHT on a tall block, X op(T) = alpha B, on device pointers: T is
+ * ExTRSV's p x p COLUMN-MAJOR triangle (ldt >= max(1, p); uplo, transt, diag as there), X is n x p ROW-MAJOR (ldx >= p, all
+ * offsets 64-bit), holds B on entry and the solution on return -- Q = X R^-1 of CholQR, the P (P^T A P)^-1 of a block CG
+ * through its Cholesky factor, the normalisation of block Gram-Schmidt.  Per row r, in substitution order over the columns
+ * (forward when op(T) is upper: 'U','N' or 'L','T'; backward otherwise):
+ *     x_rj = fl( Round( alpha * b_rj - sum_{i before j} x_ri * op(T)(i, j) ) / op(T)(j, j) )
+ * the sum exact over the already fixed doubles and rounded ONCE in the current rounding mode (exblas_set_round_mode), then
+ * one IEEE division (none under diag 'U', never a multiplication by a reciprocal).  With alpha = 1, row r is bit for bit
+ * what exblas_extrsv_dev(uplo, the other trans, diag, p, T, ldt, X + r ldx, 1) writes for B[r, :], i.e. column r of
+ * exblas_extrsm_dev on the transposed block.  The alpha term follows ExBGEMM's beta term: alpha = 1 adds b_rj exactly, any
+ * other non-zero alpha adds the error-free product alpha * b_rj (both parts: alpha * b is NOT rounded before the sum),
+ * alpha = 0 does not read B (NaN there is ignored) and solves the zero right-hand side.  Every entry of the strict triangle
+ * counts (a zero times an infinite x_ri is NaN); the other triangle, the ldt padding and the diagonal under 'U' are never
+ * read; the padding of X beyond column p - 1 is neither read nor written.  Rows are independent: a NaN in row r of B
+ * changes row r only; a row-sharded caller with T replicated needs no communication.
+ * The bits depend on the data, (uplo, transt, diag, alpha) and the rounding mode only: not on n, ldx, the rows of a wave, the
+ * column block, the chunk of T, the grid, the path (exblas_set_btrsm_path), fpe (0 or 2..8), early_exit, the context or the
+ * stream.  fpe == 0 rounds every output from an integer accumulator; fpe == 1 is the plain fp64 solve on the same structure
+ * (deterministic, not exact; counters 0); fpe >= 9: EXBLAS_UNSUPPORTED, nothing is touched (as exblas_extrsm_dev).
+ * The design range is p <= 64 (the triangle is staged once per workgroup); p up to EXBLAS_BTRSM_MAX_P is served with the
+ * same bits (chunks of T staged again per item).  p > EXBLAS_BTRSM_MAX_P is REFUSED with hipErrorInvalidValue before the
+ * device is touched: the rows of a wave must fit its share of the LDS.  n == 0 or p == 0: success, nothing is launched.
+ * Bad flags, n or p < 0, ldt < max(1, p), ldx < p or fpe < 0: hipErrorInvalidValue, also before the device is touched.
+ * ONE stream-ordered kernel launch and nothing else: no preset kernel, no memset, no mailbox, no host synchronisation.  The
+ * only workspace is that of the info counters, 16 bytes per workgroup (ExBGEMM's scheme).  Capturable into a hipGraph
+ * after one call on the device (the first one raises the kernel's dynamic LDS limit) and, for a context without
+ * workspace, exblas_reserve_workspace or one call on it.  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: the left-side solve (exblas_extrsm_dev), column-major X, conjugation, fp32. */
+#define EXBLAS_BTRSM_MAX_P 512
+int exblas_exbtrsm_dev(char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *d_t, int ldt,
+                       double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
+/* Test hook for ExBTRSM (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
+ * 2 a register block of one column, 3 four rows per wave item and chunks of 4 rows x 4 columns of T (the seams between
+ * items, slices and chunks then occur at small n and p). */
+void exblas_set_btrsm_path(int mode);
+/* The most recent ExBTRSM on this device: out[0] outputs (r, j) rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == n * p for fpe != 1 (both 0 for fpe == 1); all 0 after a
+ * call that launched nothing.  Synchronises the device; valid until the next call that uses the workspace.  Returns 0 or
+ * a hipError_t. */
+int exblas_last_btrsm_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -540,6 +580,8 @@ int exblas_exbdot_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, con
 int exblas_exbgemm_ctx(exblas_ctx_t *ctx, int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx,
                        const double *d_c, int64_t ldc, double beta, double *d_y, int64_t ldy, int fpe, int early_exit,
                        void *stream);
+int exblas_exbtrsm_ctx(exblas_ctx_t *ctx, char uplo, char transt, char diag, int64_t n, int p, double alpha,
+                       const double *d_t, int ldt, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
 int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
 int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
@@ -708,6 +750,11 @@ int exblas_exbdot(char mode, int64_t n, int p, int q, const double *x, int64_t l
  * of Y keeps its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue. */
 int exblas_exbgemm(int64_t n, int p, int q, double alpha, const double *x, int64_t ldx, const double *c, int64_t ldc,
                    double beta, double *y, int64_t ldy, int fpe, int early_exit);
+/* exblas_exbtrsm_dev on host arrays (t: the p columns of ldt; x: the n x p row-major block with leading dimension ldx, B on
+ * entry, the solution on return; its padding comes back as it went): staged through the device, synchronous.  Returns 0,
+ * hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
+int exblas_exbtrsm(char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *t, int ldt, double *x,
+                   int64_t ldx, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
