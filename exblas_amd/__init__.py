@@ -56,6 +56,7 @@ C_ABI_SYMBOLS = [
     "exblas_exbdot_allreduce_dev",
     "exblas_exbgemm_dev", "exblas_exbgemm_ctx", "exblas_exbgemm", "exblas_set_bgemm_path", "exblas_last_bgemm_info",
     "exblas_exbtrsm_dev", "exblas_exbtrsm_ctx", "exblas_exbtrsm", "exblas_set_btrsm_path", "exblas_last_btrsm_info",
+    "exblas_expotrf_dev", "exblas_expotrf_ctx", "exblas_expotrf", "exblas_set_potrf_path", "exblas_last_potrf_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -227,6 +228,12 @@ def load_library():
     L.exblas_set_btrsm_path.argtypes = [i32]
     L.exblas_set_btrsm_path.restype = None
     L.exblas_last_btrsm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_expotrf_dev.argtypes = [C.c_char, i32, vp, i32, vp, i32, i32, vp]
+    L.exblas_expotrf_ctx.argtypes = [vp] + L.exblas_expotrf_dev.argtypes
+    L.exblas_expotrf.argtypes = [C.c_char, i32, vp, i32, C.POINTER(i32), i32, i32]
+    L.exblas_set_potrf_path.argtypes = [i32]
+    L.exblas_set_potrf_path.restype = None
+    L.exblas_last_potrf_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -839,6 +846,58 @@ def last_btrsm_info():
     return _last_info("btrsm")
 
 
+def _potrf_fpe(fpe):
+    fpe = int(fpe)
+    if fpe < 0 or fpe >= 9:
+        raise ValueError(f"expotrf: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
+    return fpe
+
+
+def _potrf_triangle(shape, stride_of, uplo):
+    """The rules of the matrix of an ExPOTRF call, device or host: square, at most BTRSM_MAX_P wide, one unit stride;
+    returns (uplo, p, ldg) for the C call.  A row-major matrix is passed as the other triangle of its transpose."""
+    if len(shape) != 2:
+        raise ValueError("expotrf: G must be 2-D")
+    p = int(shape[0])
+    if shape[1] != p:
+        raise ValueError(f"expotrf: G must be square, got shape {tuple(shape)}")
+    if p > BTRSM_MAX_P:
+        raise ValueError(f"expotrf: p = {p} exceeds EXBLAS_BTRSM_MAX_P = {BTRSM_MAX_P}")
+    u, _, ldg = _trsm_layout(stride_of, uplo, "N", "expotrf")
+    return u.encode(), p, max(ldg, 1)
+
+
+def _potrf_args(G, uplo, info, fpe, early_exit):
+    """Validates a device ExPOTRF call before anything is launched (no GPU needed for that); returns (info, the C
+    arguments up to the stream).  G is never copied; info is allocated when None."""
+    torch = _torch()
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float64:
+        raise ValueError("expotrf: G must be a float64 torch tensor")
+    u, p, ldg = _potrf_triangle(tuple(G.shape), G, uplo)
+    fpe = _potrf_fpe(fpe)
+    if info is not None:
+        if not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.numel() != 1:
+            raise ValueError("expotrf: info must be a one-element int32 torch tensor")
+        if info.device != G.device:
+            raise ValueError("expotrf: G, info must be on one device")
+    _on_gpu("expotrf", G=G)
+    if info is None:
+        info = torch.zeros(1, dtype=torch.int32, device=G.device)
+    return info, (u, p, _ptr(G), ldg, _ptr(info), fpe, int(bool(early_exit)))
+
+
+def set_potrf_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one row,
+    3 column tiles of 4 and no staging in LDS.  Same bits on every path."""
+    load_library().exblas_set_potrf_path(int(mode))
+
+
+def last_potrf_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last ExPOTRF; their sum is the
+    number of entries that call fixed."""
+    return _last_info("potrf")
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
@@ -1019,6 +1078,20 @@ class Context:
         _check(load_library().exblas_exbtrsm_ctx(self.handle, *args, _stream_ptr(_torch())), "exbtrsm")
         return X
 
+    def expotrf(self, G, uplo="U", info=None, fpe=8, early_exit=True):  # noqa: N803
+        """ExPOTRF: the exact-sum Cholesky factor of the p x p Gram matrix G, in place, stream-ordered on the current stream
+        and never synchronising: uplo 'U' leaves R upper with G = R^T R, 'L' leaves L = R^T.  Every sum is exact and
+        rounded once, followed by one correctly rounded square root or division, so the factor is reproducible bit for
+        bit and is what exbtrsm_dev / extrsm_dev take.  G: a float64 tensor with one unit stride, never copied --
+        column-major (stride(0) == 1) or row-major (stride(1) == 1); `uplo` names the triangle of G[i, j] as Python
+        indexes it, the other triangle is neither read nor written; p <= 512.  info: a one-element int32 device tensor
+        (allocated when None) that receives 0, or j + 1 when the radicand of pivot j (0-based) is not > 0: that value is
+        stored at (j, j), and row j beyond it and the later rows stay as they were (LAPACK's rule).  fpe: 0, 1 or 2..8.
+        One kernel launch of one workgroup.  The design range is p <= 64.  Returns (G, info)."""
+        info, args = _potrf_args(G, uplo, info, fpe, early_exit)
+        _check(load_library().exblas_expotrf_ctx(self.handle, *args, _stream_ptr(_torch())), "expotrf")
+        return G, info
+
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
         """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
         [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
@@ -1053,6 +1126,19 @@ exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.e
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
 exbgemm_dev = _default.exbgemm
 exbtrsm_dev = _default.exbtrsm
+expotrf_dev = _default.expotrf
+
+
+def excholqr_dev(X, fpe=8, early_exit=True):  # noqa: N803
+    """CholQR of the tall n x p row-major block X on the default context, all on the device: G = exbdot_dev(X),
+    R = expotrf_dev(G, 'U'), X := X R^-1 by exbtrsm_dev, in place.  Three stream-ordered launches, no synchronisation,
+    capturable as a whole (after one call).  Returns (X, R, info): X holds Q; R is p x p with the factor in its upper
+    triangle (the strict lower triangle keeps G's entries); info is expotrf_dev's word, to be read when the caller wants
+    to -- when it is not 0, X^T X was not numerically positive definite and Q, R are not to be used."""
+    G = exbdot_dev(X, fpe=fpe, early_exit=early_exit)
+    R, info = expotrf_dev(G, "U", fpe=fpe, early_exit=early_exit)
+    exbtrsm_dev(R, X, "U", "N", fpe=fpe, early_exit=early_exit)
+    return X, R, info
 
 
 def gen_dev(kind, n, seed=1, p0=0.0, p1=0.0, first=0, count=None, n_total=None, out=None):
@@ -1337,6 +1423,20 @@ def exbtrsm(T, B, uplo="U", trans="N", diag="N", alpha=1.0, fpe=8, early_exit=Tr
     _check(load_library().exblas_exbtrsm(u, t, d, n, p, float(alpha), _hptr(T), ldt, _hptr(X), max(p, 1), fpe,
                                          int(bool(early_exit))), "exbtrsm")
     return X
+
+
+def expotrf(G, uplo="U", fpe=8, early_exit=True):  # noqa: N803
+    """ExPOTRF on a host array: G float64 of shape (p, p), C- or Fortran-ordered (anything else is copied to C order;
+    `uplo` names the triangle of G[i, j]); returns (R, info): a new array with the factor in that triangle (the other
+    triangle as it was in G; G is not changed) and the info word as an int."""
+    G = _dense_host("expotrf", "G", G, 2)
+    R = np.array(G, dtype=np.float64, copy=True, order="F" if (G.flags.f_contiguous and not G.flags.c_contiguous) else "C")
+    u, p, ldg = _potrf_triangle(R.shape, _HostStrides(R), uplo)
+    fpe = _potrf_fpe(fpe)
+    info = C.c_int32(0)
+    _require_gpu()
+    _check(load_library().exblas_expotrf(u, p, _hptr(R), ldg, C.byref(info), fpe, int(bool(early_exit))), "expotrf")
+    return R, int(info.value)
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

@@ -141,6 +141,14 @@ __global__ void __launch_bounds__(BD_BLOCK) k_bdot_acc(BdotGeom g, long long n, 
     }
 }
 
+// the group sets before a batch accumulates into them (a kernel, not a memset: a captured memset node of this size did
+// not survive a second replay of the graph)
+__global__ void __launch_bounds__(BD_BLOCK) k_bdot_zero(long long *__restrict__ sets, long long count)
+{
+    for (long long i = (long long)blockIdx.x * BD_BLOCK + threadIdx.x; i < count; i += (long long)gridDim.x * BD_BLOCK)
+        sets[i] = 0;
+}
+
 // One wave sums the `ncopies` copies of an output's set, `stride` words apart (the accumulator groups, or the exported
 // sets of the shards): the low 32 bits and the signed high parts of the limbs are summed apart and the high parts enter
 // one limb up (as in k_finalize), so the sum cannot overflow however many adds the copies hold -- nor can 2^31 copies of
@@ -286,8 +294,9 @@ static int bdot_launch(Ctx &c, bool diag, long long n, int p, int q, const doubl
             if (c.bdot_path != 1) g.steps = (g.steps + BD_U - 1) / BD_U * BD_U;
             const long long nslabs = max(1ll, (total + g.steps - 1) / g.steps);
             // the workspace is shared with routines that leave scratch in it: the sets are zeroed here as well
-            err = hipMemsetAsync(sets, 0, (size_t)g.ngroups * nout * SET_WORDS * 8, st);
-            if (err != hipSuccess) return (int)err;
+            const long long nzero = (long long)g.ngroups * nout * SET_WORDS;
+            hipLaunchKernelGGL(k_bdot_zero, dim3((unsigned)min(4096ll, (nzero + BD_BLOCK - 1) / BD_BLOCK)), dim3(BD_BLOCK), 0,
+                               st, sets, nzero);
             hipLaunchKernelGGL((k_bdot_acc<N, EE, PLAIN>), dim3((unsigned)(nslabs * g.ntiles)), dim3(BD_BLOCK), 0, st, g, n,
                                x, ldx, y, ldy, sets);
             const dim3 waves((unsigned)((nout + BD_WAVES - 1) / BD_WAVES));

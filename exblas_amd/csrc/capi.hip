@@ -322,6 +322,7 @@ void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
 void exblas_set_bgemm_path(int mode) { set_path(&CtxKnobs::bgemm_path, mode, 3); }
 void exblas_set_btrsm_path(int mode) { set_path(&CtxKnobs::btrsm_path, mode, 3); }
+void exblas_set_potrf_path(int mode) { set_path(&CtxKnobs::potrf_path, mode, 3); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -405,6 +406,12 @@ int exblas_last_bgemm_info(int64_t *out4)
 int exblas_last_btrsm_info(int64_t *out4)
 {
     return last_slot_info(&CtxWsPtrs::btrsm_info_dev, &CtxWsPtrs::btrsm_info_blocks, out4);
+}
+
+// the same for ExPOTRF: out[0] + out[1] is the number of entries the call fixed (the radicand of a breakdown included)
+int exblas_last_potrf_info(int64_t *out4)
+{
+    return last_slot_info(&CtxWsPtrs::potrf_info_dev, &CtxWsPtrs::potrf_info_blocks, out4);
 }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
@@ -638,6 +645,28 @@ static int exbtrsm_on(Ctx &c, char uplo, char transt, char diag, int64_t n, int 
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exbtrsm_dispatch(c, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of ExPOTRF, on host or device pointers alike, before a device is touched.  *empty: p == 0, which
+// is decided before the pointers are looked at.
+static int potrf_check_args(char uplo, int p, const double *g, int ldg, const int *info, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(uplo, "LlUu") || p < 0 || p > EXBLAS_BTRSM_MAX_P || ldg < (p > 1 ? p : 1) || fpe < 0)
+        return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = p == 0;
+    if (!*empty && (!g || !info)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int expotrf_on(Ctx &c, char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // p == 0 goes on: the call counts as the device's last one, and the dispatch launches nothing
+    if (int rc = potrf_check_args(uplo, p, d_g, ldg, d_info, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)expotrf_dispatch(c, uplo, p, d_g, ldg, d_info, fpe, early_exit, round_mode(), st);
 }
 
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
@@ -904,6 +933,15 @@ int exblas_exbtrsm_ctx(exblas_ctx_t *h, char uplo, char transt, char diag, int64
     return exbtrsm_on(*cp, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_expotrf_ctx(exblas_ctx_t *h, char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit,
+                       void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = potrf_check_args(uplo, p, d_g, ldg, d_info, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return expotrf_on(*cp, uplo, p, d_g, ldg, d_info, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -976,6 +1014,11 @@ int exblas_exbtrsm_dev(char uplo, char transt, char diag, int64_t n, int p, doub
                        double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
 {
     return exblas_exbtrsm_ctx(nullptr, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, stream);
+}
+
+int exblas_expotrf_dev(char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit, void *stream)
+{
+    return exblas_expotrf_ctx(nullptr, uplo, p, d_g, ldg, d_info, fpe, early_exit, stream);
 }
 
 int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
@@ -1556,6 +1599,23 @@ int exblas_exbtrsm(char uplo, char transt, char diag, int64_t n, int p, double a
     double *d_x = hc.in(1, xbytes, x, xbytes);
     return hc.out(exbtrsm_on(hc.c, uplo, transt, diag, n, p, alpha, d_t, ldt, d_x, ldx, fpe, early_exit, hc.c.stream), x, d_x,
                   xbytes);
+}
+
+// the p columns of G travel with their ldg padding (the last one only up to its p-th entry) and come back the same way;
+// *info (when given) receives the info word
+int exblas_expotrf(char uplo, int p, double *g, int ldg, int *info, int fpe, int early_exit)
+{
+    bool empty;
+    int dummy = 0;
+    const int bad = potrf_check_args(uplo, p, g, ldg, &dummy, fpe, &empty);
+    if (bad || empty) return bad;   // (p == 0: *info is not written either)
+    HostCall hc("exblas_expotrf");
+    const size_t gbytes = ((size_t)ldg * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    double *d_g = hc.in(0, gbytes, g, gbytes);
+    int *d_info = (int *)hc.in(1, sizeof(int), nullptr, 0);
+    const int rc = expotrf_on(hc.c, uplo, p, d_g, ldg, d_info, fpe, early_exit, hc.c.stream);
+    if (rc == 0 && info) EXB_CHECK(hipMemcpyAsync(info, d_info, sizeof(int), hipMemcpyDeviceToHost, hc.c.stream));
+    return hc.out(rc, g, d_g, gbytes);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

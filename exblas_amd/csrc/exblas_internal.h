@@ -39,6 +39,8 @@ struct CtxKnobs {
                              // block of one row, 3 column tiles of 4 and chunks of 4 rows of C
     int btrsm_path = 0;      // exblas_set_btrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
                              // block of one column, 3 4 rows per wave item and chunks of 4 rows and columns of T
+    int potrf_path = 0;      // exblas_set_potrf_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
+                             // block of one row, 3 column tiles of 4 and no staging in LDS
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -61,6 +63,8 @@ struct CtxWsPtrs {
     int bgemm_info_blocks = 0;                   // launched nothing), and how many workgroups there were
     const long long *btrsm_info_dev = nullptr;   // the same for the last ExBTRSM call
     int btrsm_info_blocks = 0;
+    const long long *potrf_info_dev = nullptr;   // the same for the last ExPOTRF call (one workgroup)
+    int potrf_info_blocks = 0;
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -234,6 +238,10 @@ hipError_t exbgemm_dispatch(Ctx &c, long long n, int p, int q, double alpha, con
 // btrsm.hip
 hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long n, int p, double alpha, const double *t,
                             int ldt, double *x, long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// potrf.hip
+hipError_t expotrf_dispatch(Ctx &c, char uplo, int p, double *g, int ldg, int *info, int fpe, int early_exit, int round_mode,
+                            hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
 struct I8Plan {

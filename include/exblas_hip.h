@@ -400,7 +400,7 @@ int exblas_last_trsm_info(int64_t *out4);
  * 64 each.
  * n == 0 writes +0.0 to every output; p == 0 or q == 0: success, nothing is launched.  n < 0 or n > INT_MAX, p < 0,
  * q < 0, ldx < p, ldy < q, ldc < q in 'G', p != q in 'D', a mode other than G/g/D/d or fpe < 0: hipErrorInvalidValue.
- * Stream-ordered launches only (per batch a memset, the accumulate kernel and the finalize kernel; no host
+ * Stream-ordered launches only (per batch a zeroing kernel, the accumulate kernel and the finalize kernel; no host
  * synchronisation): the accumulators -- one 68-limb set of 576 bytes per output and accumulator group -- live in the
  * context workspace, EXBLAS_BDOT_WORKSPACE_BYTES whatever the sizes, are zeroed before use (other routines leave scratch
  * in the workspace) and are left zeroed.  Capturable into a hipGraph after exblas_reserve_workspace or one call.
@@ -517,6 +517,47 @@ void exblas_set_btrsm_path(int mode);
  * call that launched nothing.  Synchronises the device; valid until the next call that uses the workspace.  Returns 0 or
  * a hipError_t. */
 int exblas_last_btrsm_info(int64_t *out4);
+/* ExPOTRF: exact-sum Cholesky factorisation of a small symmetric positive definite matrix (the Gram matrix X^T X of CholQR,
+ * the P^T A P of a block CG), on device pointers, IN PLACE on ExTRSV's p x p COLUMN-MAJOR triangle (ldg >= max(1, p)): what
+ * it leaves is what exblas_extrsm_dev and exblas_exbtrsm_dev take, with no conversion.  For uplo = 'U', G = R^T R with R
+ * upper.  Row by row, j = 0 .. p-1:
+ *     r_jj = sqrt( Round( g_jj - sum_{k<j} r_kj^2 ) )
+ *     r_ji = fl( Round( g_ji - sum_{k<j} r_kj * r_ki ) / r_jj )      for i > j
+ * every sum exact over the already fixed doubles (both parts of every TwoProd and every entry count, zeros included: a zero
+ * times an infinite entry is NaN) and rounded ONCE in the current rounding mode (exblas_set_round_mode), then ONE IEEE
+ * correctly rounded square root or ONE IEEE division (never a multiplication by a reciprocal).  The diagonal of R is
+ * positive.  uplo = 'L' is G = L L^T with L = R^T: the same numbers in the other triangle.
+ * The bits depend on the data, uplo and the rounding mode only: not on the path (exblas_set_potrf_path), the row block, the
+ * column tile, the slices, the number of waves, fpe (0 or 2..8), early_exit, ldg, the context or the stream.  Two identities
+ * follow: the strict part of column i of R is bit for bit what exblas_extrsv_dev('U', 'T', 'N', i, R, ldg, .) writes for
+ * g[0:i, i]; the radicand of r_ii is bit for bit ExBGEMM's Round(-1 * r[0:i, i]^T r[0:i, i] + 1 * g_ii) on a 1 x i block.
+ * BREAKDOWN (LAPACK's rule): at the first j whose rounded radicand v is not > 0 (zero, negative, NaN) the routine stores v
+ * itself at (j, j), leaves every entry of row j beyond the diagonal and all later rows as they were on entry, and writes
+ * j + 1 to the int32 word d_info; otherwise it writes 0.  +Inf passes, as in LAPACK.  The word is written by every call
+ * that launches, with a plain store: nothing has to be cleared, and it is valid after every graph replay.  The routine
+ * never synchronises; the caller reads the word when it wants to.
+ * The other triangle is neither read nor written; the padding of a column beyond row p - 1 is not touched.
+ * fpe == 0 rounds every output from an integer accumulator; fpe == 1 is the plain fp64 factorisation on the same structure
+ * (deterministic, not exact; counters 0); fpe >= 9: EXBLAS_UNSUPPORTED, nothing is touched.
+ * The design range is p <= 64 (the triangle is factored in LDS); p up to EXBLAS_BTRSM_MAX_P, every triangle ExBTRSM accepts,
+ * is served with the same bits (in place in global memory).  A larger p is REFUSED with hipErrorInvalidValue before the
+ * device is touched; so are a bad uplo, p < 0, ldg < max(1, p), fpe < 0 and a null d_info with p > 0.  p == 0: success,
+ * nothing is launched, d_info is not written.
+ * ONE stream-ordered launch of ONE workgroup and nothing else: no memset, no mailbox, no ticket, no host synchronisation.
+ * The only workspace is that of the two counters (16 bytes).  Capturable into a hipGraph after one call on the context (or
+ * exblas_reserve_workspace).  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: batched factorisations, pivoting, a shifted CholQR, LDL^T, fp32, more than one workgroup, p > 512. */
+int exblas_expotrf_dev(char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit, void *stream);
+/* Test hook for ExPOTRF (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
+ * 2 a register block of one row, 3 column tiles of 4 and no staging in LDS (the seams between tiles, slices and row
+ * blocks, and the in-place form of p > 64, then occur at small p). */
+void exblas_set_potrf_path(int mode);
+/* The most recent ExPOTRF on this device: out[0] outputs rounded in registers, out[1] outputs rounded from the integer
+ * accumulator, out[2] = out[3] = 0.  out[0] + out[1] is the number of entries the call fixed for fpe != 1 (both 0 for
+ * fpe == 1): p (p + 1) / 2 on success, j (2p - j + 1) / 2 + 1 after a breakdown at pivot j (0-based); all 0 after a call
+ * that launched nothing.  The workgroup stores them with plain stores: valid after each graph replay.  Synchronises the
+ * device; valid until the next call that uses the workspace.  Returns 0 or a hipError_t. */
+int exblas_last_potrf_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -582,6 +623,8 @@ int exblas_exbgemm_ctx(exblas_ctx_t *ctx, int64_t n, int p, int q, double alpha,
                        void *stream);
 int exblas_exbtrsm_ctx(exblas_ctx_t *ctx, char uplo, char transt, char diag, int64_t n, int p, double alpha,
                        const double *d_t, int ldt, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
+int exblas_expotrf_ctx(exblas_ctx_t *ctx, char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit,
+                       void *stream);
 int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
 int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
@@ -755,6 +798,10 @@ int exblas_exbgemm(int64_t n, int p, int q, double alpha, const double *x, int64
  * hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
 int exblas_exbtrsm(char uplo, char transt, char diag, int64_t n, int p, double alpha, const double *t, int ldt, double *x,
                    int64_t ldx, int fpe, int early_exit);
+/* exblas_expotrf_dev on a host array (g: the p columns of ldg, factored in place; its padding and the other triangle come
+ * back as they went); *info (may be NULL) receives the info word: staged through the device, synchronous.  Returns 0,
+ * hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
+int exblas_expotrf(char uplo, int p, double *g, int ldg, int *info, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
