@@ -494,6 +494,13 @@ __global__ void __launch_bounds__(BLOCK) k_exsum_segmented(const double *__restr
     if (valid && lane == 0) out[seg] = round_mode ? r.rf : __longlong_as_double((long long)r.ex);
 }
 
+// every segment reads 0.0: an unsupported variant (a kernel, not a memset: a captured memset node of a few MiB does not
+// replay reliably on this stack, see k_bdot_zero and k_gemv_zero)
+__global__ void __launch_bounds__(BLOCK) k_exsum_segmented_zero(long long nseg, double *__restrict__ out)
+{
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < nseg; i += (long long)gridDim.x * BLOCK) out[i] = 0.0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
@@ -631,7 +638,9 @@ hipError_t exsum_segmented_dispatch(const double *values, const long long *offse
         hipLaunchKernelGGL((k_exsum_segmented<N(), EE()>), grid, block, 0, st, values, offsets, nseg, round_mode, out);
     };
     if (fpe < 2) go(std::integral_constant<int, 0>(), std::false_type());
-    else if (!select_variant<2>(fpe, early_exit, go)) return hipMemsetAsync(out, 0, sizeof(double) * nseg, st);
+    else if (!select_variant<2>(fpe, early_exit, go))
+        hipLaunchKernelGGL(k_exsum_segmented_zero, dim3((unsigned)min(4096ll, (nseg + BLOCK - 1) / BLOCK)), block, 0, st, nseg,
+                           out);
     return hipGetLastError();
 }
 

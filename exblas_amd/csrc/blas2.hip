@@ -105,6 +105,22 @@ __global__ void __launch_bounds__(GV_BLOCK) k_gemvN_fpe(int m, int n, double alp
     }
 }
 
+// the rows' accumulators (and the tickets behind them) before an 'N' call adds to them (a kernel, not a memset: captured
+// into a graph, the 2.25 MiB memset node of m = 4096 ended a replay with a memory access fault; bdot.hip's k_bdot_zero
+// replaced a node of that size for the same stack's sake)
+__global__ void __launch_bounds__(GV_BLOCK) k_gemv_zero(long long *__restrict__ ws, long long count)
+{
+    for (long long i = (long long)blockIdx.x * GV_BLOCK + threadIdx.x; i < count; i += (long long)gridDim.x * GV_BLOCK)
+        ws[i] = 0;
+}
+
+static inline void gemv_zero(long long *ws, size_t bytes, hipStream_t st)
+{
+    const long long count = (long long)(bytes / sizeof(long long));
+    hipLaunchKernelGGL(k_gemv_zero, dim3((unsigned)std::min(4096ll, (count + GV_BLOCK - 1) / GV_BLOCK)), dim3(GV_BLOCK), 0,
+                       st, ws, count);
+}
+
 // x' = fl(alpha * x), contiguous: what k_gemvN_fpe_sx reads with SCALAR loads
 __global__ void __launch_bounds__(256) k_scale_x(int n, double alpha, const double *__restrict__ x, long long incx,
                                                  double *__restrict__ xa)
@@ -496,8 +512,7 @@ static hipError_t gemvN_fpe(Ctx &c, int m, int n, double alpha, const double *a,
     int *tickets = (int *)(base + ws_bytes);
     double *part = (double *)(base + ws_bytes + tk_bytes);
     double *xa = (double *)(base + ws_bytes + tk_bytes + part_bytes);
-    e = hipMemsetAsync(ws, 0, ws_bytes + tk_bytes, st);  // the rows' spill accumulators and the tickets
-    if (e != hipSuccess) return e;
+    gemv_zero(ws, ws_bytes + tk_bytes, st);  // the rows' spill accumulators and the tickets
     const bool vec = (m % 2 == 0) && (lda % 2 == 0) && (((uintptr_t)a) & 15u) == 0;
     dim3 grid(gx, KS);
     if (vec) {
@@ -529,8 +544,7 @@ static hipError_t gemvN_sa(Ctx &c, int m, int n, double alpha, const double *a, 
     hipError_t e;
     long long *ws = (long long *)workspace(c, ws_bytes, st, &e);
     if (!ws) return e;
-    e = hipMemsetAsync(ws, 0, ws_bytes, st);
-    if (e != hipSuccess) return e;
+    gemv_zero(ws, ws_bytes, st);
     hipLaunchKernelGGL(k_gemvN_sa, dim3(gx, KS), dim3(GV_BLOCK), 0, st, m, n, alpha, a, (long long)lda, x,
                        (long long)incx, kper, ws);
     hipLaunchKernelGGL(k_gemv_finish, dim3((m + GV_WAVES - 1) / GV_WAVES), dim3(GV_BLOCK), 0, st, m, 0,

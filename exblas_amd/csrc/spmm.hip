@@ -447,8 +447,7 @@ static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I 
     unsigned long long *bm = (unsigned long long *)(base + b_hdr + b_lslot + b_lrows + b_lbase);
     long long *lacc = (long long *)(base + b_hdr + b_lslot + b_lrows + b_lbase + b_bm);
     c.spmm_info_dev = hdr;
-    e = hipMemsetAsync(hdr, 0, SM_HDR_WORDS * sizeof(long long), st);
-    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sp_zero_header, dim3(1), dim3(64), 0, st, hdr, SM_HDR_WORDS);
     const int cap = c.num_cu * 8;
     hipLaunchKernelGGL((k_spmm_hist<I>), dim3((m + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, st, m, rp, long_min, hdr);
     hipLaunchKernelGGL((k_spmm_classify<I>), dim3((m + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, st, m, k, rp, long_min,

@@ -276,8 +276,7 @@ static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, co
     long long *lbase = (long long *)(base + b_hdr + b_med + b_lrows);
     long long *lacc = (long long *)(base + b_hdr + b_med + b_lrows + b_lbase);
     c.spmv_info_dev = hdr;
-    e = hipMemsetAsync(hdr, 0, SP_HDR * sizeof(long long), st);
-    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sp_zero_header, dim3(1), dim3(64), 0, st, hdr, SP_HDR);
     const int cap = c.num_cu * 8;
     hipLaunchKernelGGL((k_spmv_classify<I>), dim3((m + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, st, m, rp, short_max,
                        long_min, lcap, hdr, med, lrows, lacc);

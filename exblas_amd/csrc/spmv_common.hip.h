@@ -209,6 +209,13 @@ __device__ __forceinline__ long long sp_chunk_owner(const long long *__restrict_
     return lo;
 }
 
+// the header of an ExSpMV / ExSpMM call before its first kernel counts into it (one small kernel, not a memset node: a
+// captured graph with memset nodes does not replay reliably on this stack, see sptrs_common.hip.h's preset)
+static __global__ void __launch_bounds__(64) k_sp_zero_header(long long *__restrict__ hdr, int words)
+{
+    for (int i = threadIdx.x; i < words; i += 64) hdr[i] = 0;
+}
+
 // split rows: chunk counts of the rows in lrows[0 .. min(hdr[1], lcap)) -> exclusive scan (lbase), total in hdr[2]
 template <class I>
 __global__ void __launch_bounds__(1024) k_spmv_long_prep(const I *__restrict__ rp, const int *__restrict__ lrows,

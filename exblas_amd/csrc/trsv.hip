@@ -32,6 +32,8 @@
 #include "exblas_internal.h"
 #include "fpe.hip.h"
 
+#include <algorithm>
+
 namespace exb {
 namespace {
 
@@ -389,6 +391,16 @@ __global__ void __launch_bounds__(TB *TW) k_dtrsv(int n, const double *__restric
     }
 }
 
+// The ticket and statistics words to zero and the mailbox to XQ_EMPTY before a solve.  A kernel, not two memset nodes: a
+// captured graph with the memset nodes ended a replay with a memory access fault on this stack, and a ticket word that
+// is not cleared sends every workgroup to a block-row beyond the matrix.
+__global__ void __launch_bounds__(256) k_trsv_preset(int n, int *__restrict__ sync, long long *__restrict__ xq)
+{
+    const int i0 = blockIdx.x * 256 + threadIdx.x;
+    if (i0 < 16) sync[i0] = 0;
+    for (long long i = i0; i < n; i += (long long)gridDim.x * 256) xq[i] = XQ_EMPTY;
+}
+
 template <int N, bool EE>
 hipError_t trsv_variant(int n, const double *a, long long rs, long long cs, double *x, long long incx, int rev, int unit,
                         int mode, int *sync, double *xq, hipStream_t st)
@@ -417,9 +429,7 @@ hipError_t extrsv_dispatch(Ctx &c, char uplo, char transa, char diag, int n, con
     int *sync = (int *)workspace(c, 64 + (size_t)n * sizeof(double), st, &e);
     if (!sync) return e;
     double *xq = (double *)((char *)sync + 64);
-    e = hipMemsetAsync(sync, 0, 64, st);
-    if (e != hipSuccess) return e;
-    if ((e = hipMemsetAsync(xq, 0xff, (size_t)n * sizeof(double), st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_trsv_preset, dim3(std::min(1024, (n + 255) / 256)), dim3(256), 0, st, n, sync, (long long *)xq);
     const long long ix = incx;
     if (fpe == 0) return trsv_variant<0, false>(n, a, rs, cs, x, ix, rev, unit, round_mode, sync, xq, st);
     if (fpe == 1) {

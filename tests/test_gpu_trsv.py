@@ -246,8 +246,9 @@ def test_extrsv_randomized_soak(ex):
 
 
 def test_extrsv_and_gemv_in_a_hip_graph(ex, oracle):
-    """exgemv_dev and extrsv_dev are stream-ordered launches (plus two memset nodes for the solve): captured once,
-    replayed three times -- solve L x = A v + y repeatedly, bits equal to the oracle's every time"""
+    """exgemv_dev and extrsv_dev are stream-ordered launches: captured once, replayed three times -- solve
+    L x = A v + y repeatedly, bits equal to the oracle's every time.  (The same inputs on every replay; new data,
+    larger sizes and a dirty workspace between replays: tests/test_gpu_graph_replay.py.)"""
     import torch
     n = 700
     a, b = tri_system(oracle, "L", n, 333, dominant=True)
