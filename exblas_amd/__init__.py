@@ -406,6 +406,11 @@ def _last_info(routine):
     return tuple(int(v) for v in out)
 
 
+def _set_path(routine, mode):
+    """The body of every set_*_path test hook: the routine's exblas_set_<routine>_path(mode)."""
+    getattr(load_library(), f"exblas_set_{routine}_path")(int(mode))
+
+
 def _spmv_args(A, x, y, alpha, beta, fpe, early_exit):
     """Validates a device ExSpMV call before anything is launched; returns (y, the C arguments up to the stream)."""
     crow, col, val, m, n, bits = _csr_dev("exspmv", A)
@@ -427,7 +432,7 @@ def _spmv_args(A, x, y, alpha, beta, fpe, early_exit):
 def set_spmv_path(mode):
     """Test hook: 0 automatic, 1 accumulator finish for every row, 2 in-register rounding wherever certified (no row
     split), 3 every row split at a small chunk.  Same bits on every path."""
-    load_library().exblas_set_spmv_path(int(mode))
+    _set_path("spmv", mode)
 
 
 def last_spmv_info():
@@ -457,7 +462,7 @@ def _sptrsv_args(A, x, uplo, diag, fpe, early_exit):
 def set_sptrsv_path(mode):
     """Test hook: 0 automatic, 1 every row rounded from its integer accumulator, 2 every row in the one-row-per-wave
     form.  Same bits on every path."""
-    load_library().exblas_set_sptrsv_path(int(mode))
+    _set_path("sptrsv", mode)
 
 
 def last_sptrsv_info():
@@ -488,7 +493,7 @@ def _sptrsm_args(A, X, uplo, diag, fpe, early_exit):
 def set_sptrsm_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one row per work item, 3 column
     panels and tiles of 4 columns.  Same bits on every path."""
-    load_library().exblas_set_sptrsm_path(int(mode))
+    _set_path("sptrsm", mode)
 
 
 def last_sptrsm_info():
@@ -520,10 +525,11 @@ def _trsm_layout(A, uplo, trans, who="extrsm"):
                      f"({s0}, {s1})")
 
 
-def _trsm_fpe(fpe):
+def _fpe_0_to_8(who, fpe):
+    """fpe of the routines that refuse what they have no variant for (ExTRSM, ExBTRSM, ExPOTRF)."""
     fpe = int(fpe)
     if fpe < 0 or fpe >= 9:
-        raise ValueError(f"extrsm: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
+        raise ValueError(f"{who}: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
     return fpe
 
 
@@ -548,7 +554,7 @@ def _trsm_args(A, X, uplo, trans, diag, fpe, early_exit):
         raise ValueError("extrsm: X must be row-major with stride(1) == 1 (it is solved in place)")
     if X.stride(0) < k:
         raise ValueError(f"extrsm: the rows of X overlap: stride(0) = {X.stride(0)} < k = {k}")
-    fpe = _trsm_fpe(fpe)
+    fpe = _fpe_0_to_8("extrsm", fpe)
     _on_gpu("extrsm", A=A, X=X)
     return (u.encode(), t.encode(), d, n, k, _ptr(A), lda, _ptr(X), max(int(X.stride(0)), 1), fpe, int(bool(early_exit)))
 
@@ -556,7 +562,7 @@ def _trsm_args(A, X, uplo, trans, diag, fpe, early_exit):
 def set_trsm_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one row per work item, 3 column
     panels and tiles of 4 columns.  Same bits on every path."""
-    load_library().exblas_set_trsm_path(int(mode))
+    _set_path("trsm", mode)
 
 
 def last_trsm_info():
@@ -597,7 +603,7 @@ def _spmm_args(A, X, Y, alpha, beta, fpe, early_exit):
 def set_spmm_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from an integer accumulator, 2 in-register rounding wherever
     certified (no row split), 3 every row split at a small chunk.  Same bits on every path."""
-    load_library().exblas_set_spmm_path(int(mode))
+    _set_path("spmm", mode)
 
 
 def last_spmm_info():
@@ -712,7 +718,7 @@ def _bdot_round_args(sets, mode, p, q, out):
 def set_bdot_path(mode):
     """Test hook: 0 automatic, 1 the smallest row slab per workgroup, 2 column panels and output tiles of width 4.
     Same bits on every path."""
-    load_library().exblas_set_bdot_path(int(mode))
+    _set_path("bdot", mode)
 
 
 def _bgemm_block(name, t, rows=None, cols=None):
@@ -776,7 +782,7 @@ def _bgemm_args(X, Cm, alpha, beta, Y, fpe, early_exit):
 def set_bgemm_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one row,
     3 column tiles of 4 and chunks of 4 rows of C.  Same bits on every path."""
-    load_library().exblas_set_bgemm_path(int(mode))
+    _set_path("bgemm", mode)
 
 
 def last_bgemm_info():
@@ -787,26 +793,25 @@ def last_bgemm_info():
 BTRSM_MAX_P = 512  # EXBLAS_BTRSM_MAX_P: a wider triangle is refused
 
 
-def _btrsm_fpe(fpe):
-    fpe = int(fpe)
-    if fpe < 0 or fpe >= 9:
-        raise ValueError(f"exbtrsm: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
-    return fpe
+def _small_square(who, name, shape, stride_of, uplo, trans):
+    """The rules of the small operand `name` of ExBTRSM and ExPOTRF, device or host: 2-D, square, at most BTRSM_MAX_P wide,
+    one unit stride (_trsm_layout); returns (uplo, trans, p, ld) for the C call."""
+    if len(shape) != 2:
+        raise ValueError(f"{who}: {name} must be 2-D")
+    p = int(shape[0])
+    if shape[1] != p:
+        raise ValueError(f"{who}: {name} must be square, got shape {tuple(shape)}")
+    if p > BTRSM_MAX_P:
+        raise ValueError(f"{who}: p = {p} exceeds EXBLAS_BTRSM_MAX_P = {BTRSM_MAX_P}")
+    u, t, ld = _trsm_layout(stride_of, uplo, trans, who)
+    return u.encode(), t.encode(), p, max(ld, 1)
 
 
 def _btrsm_triangle(T, shape, stride_of, uplo, trans, diag):
-    """The rules of the triangle of an ExBTRSM call, device or host: square, at most BTRSM_MAX_P wide, one unit stride;
-    returns (uplo, trans, diag, p, ldt) for the C call."""
-    if len(shape) != 2:
-        raise ValueError("exbtrsm: T must be 2-D")
-    p = int(shape[0])
-    if shape[1] != p:
-        raise ValueError(f"exbtrsm: T must be square, got shape {tuple(shape)}")
-    if p > BTRSM_MAX_P:
-        raise ValueError(f"exbtrsm: p = {p} exceeds EXBLAS_BTRSM_MAX_P = {BTRSM_MAX_P}")
-    u, t, ldt = _trsm_layout(stride_of, uplo, trans, "exbtrsm")
+    """The rules of the triangle of an ExBTRSM call, device or host; returns (uplo, trans, diag, p, ldt) for the C call."""
+    u, t, p, ldt = _small_square("exbtrsm", "T", shape, stride_of, uplo, trans)
     _, d = _solve_flags("exbtrsm", "L", diag)
-    return u.encode(), t.encode(), d, p, max(ldt, 1)
+    return u, t, d, p, ldt
 
 
 def _btrsm_args(T, X, uplo, trans, diag, alpha, fpe, early_exit):
@@ -826,7 +831,7 @@ def _btrsm_args(T, X, uplo, trans, diag, alpha, fpe, early_exit):
     if n > 0 and ((p > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < p)):
         raise ValueError("exbtrsm: X must be row-major with stride(1) == 1 and stride(0) >= p (its rows must not overlap; "
                          "it is solved in place)")
-    fpe = _btrsm_fpe(fpe)
+    fpe = _fpe_0_to_8("exbtrsm", fpe)
     if T.device != X.device:
         raise ValueError("exbtrsm: T, X must be on one device")
     if _bgemm_overlap(T, X) if T.stride(1) == 1 else _bgemm_overlap(T.t(), X):
@@ -838,7 +843,7 @@ def _btrsm_args(T, X, uplo, trans, diag, alpha, fpe, early_exit):
 def set_btrsm_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one column,
     3 four rows per wave item and chunks of 4 x 4 of T.  Same bits on every path."""
-    load_library().exblas_set_btrsm_path(int(mode))
+    _set_path("btrsm", mode)
 
 
 def last_btrsm_info():
@@ -846,25 +851,11 @@ def last_btrsm_info():
     return _last_info("btrsm")
 
 
-def _potrf_fpe(fpe):
-    fpe = int(fpe)
-    if fpe < 0 or fpe >= 9:
-        raise ValueError(f"expotrf: fpe must be 0 (accumulators only), 1 (plain fp64) or 2..8, got {fpe}")
-    return fpe
-
-
 def _potrf_triangle(shape, stride_of, uplo):
-    """The rules of the matrix of an ExPOTRF call, device or host: square, at most BTRSM_MAX_P wide, one unit stride;
-    returns (uplo, p, ldg) for the C call.  A row-major matrix is passed as the other triangle of its transpose."""
-    if len(shape) != 2:
-        raise ValueError("expotrf: G must be 2-D")
-    p = int(shape[0])
-    if shape[1] != p:
-        raise ValueError(f"expotrf: G must be square, got shape {tuple(shape)}")
-    if p > BTRSM_MAX_P:
-        raise ValueError(f"expotrf: p = {p} exceeds EXBLAS_BTRSM_MAX_P = {BTRSM_MAX_P}")
-    u, _, ldg = _trsm_layout(stride_of, uplo, "N", "expotrf")
-    return u.encode(), p, max(ldg, 1)
+    """The rules of the matrix of an ExPOTRF call, device or host; returns (uplo, p, ldg) for the C call.  A row-major
+    matrix is passed as the other triangle of its transpose."""
+    u, _, p, ldg = _small_square("expotrf", "G", shape, stride_of, uplo, "N")
+    return u, p, ldg
 
 
 def _potrf_args(G, uplo, info, fpe, early_exit):
@@ -874,7 +865,7 @@ def _potrf_args(G, uplo, info, fpe, early_exit):
     if not isinstance(G, torch.Tensor) or G.dtype != torch.float64:
         raise ValueError("expotrf: G must be a float64 torch tensor")
     u, p, ldg = _potrf_triangle(tuple(G.shape), G, uplo)
-    fpe = _potrf_fpe(fpe)
+    fpe = _fpe_0_to_8("expotrf", fpe)
     if info is not None:
         if not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.numel() != 1:
             raise ValueError("expotrf: info must be a one-element int32 torch tensor")
@@ -889,7 +880,7 @@ def _potrf_args(G, uplo, info, fpe, early_exit):
 def set_potrf_path(mode):
     """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 a register block of one row,
     3 column tiles of 4 and no staging in LDS.  Same bits on every path."""
-    load_library().exblas_set_potrf_path(int(mode))
+    _set_path("potrf", mode)
 
 
 def last_potrf_info():
@@ -1342,7 +1333,7 @@ def extrsm(A, B, uplo="L", trans="N", diag="N", fpe=8, early_exit=True):
     B = _dense_host("extrsm", "B", B, 2, " (a block of right-hand sides; for one vector use extrsv)")
     if B.shape[0] != n:
         raise ValueError(f"extrsm: B must have n = {n} rows")
-    fpe = _trsm_fpe(fpe)
+    fpe = _fpe_0_to_8("extrsm", fpe)
     X = np.array(B, dtype=np.float64, copy=True, order="C")
     k = int(X.shape[1])
     _require_gpu()
@@ -1416,7 +1407,7 @@ def exbtrsm(T, B, uplo="U", trans="N", diag="N", alpha=1.0, fpe=8, early_exit=Tr
     B = _dense_host("exbtrsm", "B", B, 2, " (n x p, one row per system; for one vector use extrsv)")
     if B.shape[1] != p:
         raise ValueError(f"exbtrsm: B must have p = {p} columns, not {B.shape[1]}")
-    fpe = _btrsm_fpe(fpe)
+    fpe = _fpe_0_to_8("exbtrsm", fpe)
     X = np.array(B, dtype=np.float64, copy=True, order="C")
     n = int(X.shape[0])
     _require_gpu()
@@ -1432,7 +1423,7 @@ def expotrf(G, uplo="U", fpe=8, early_exit=True):  # noqa: N803
     G = _dense_host("expotrf", "G", G, 2)
     R = np.array(G, dtype=np.float64, copy=True, order="F" if (G.flags.f_contiguous and not G.flags.c_contiguous) else "C")
     u, p, ldg = _potrf_triangle(R.shape, _HostStrides(R), uplo)
-    fpe = _potrf_fpe(fpe)
+    fpe = _fpe_0_to_8("expotrf", fpe)
     info = C.c_int32(0)
     _require_gpu()
     _check(load_library().exblas_expotrf(u, p, _hptr(R), ldg, C.byref(info), fpe, int(bool(early_exit))), "expotrf")

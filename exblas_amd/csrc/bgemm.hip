@@ -8,10 +8,8 @@
 // the beta terms under ExGEMV's rules) exactly and rounds it once, so the bits depend on the data and the rounding mode
 // only.
 //
-// Structure: ONE kernel and nothing else -- no memset either (a memset node replayed in a captured graph was seen to
-// leave the counters of this routine undefined from the second replay on).  The info counters are therefore not shared
-// words that would have to be zeroed first: every workgroup stores its own pair (registers, accumulator) into its slot of
-// the workspace, and exblas_last_bgemm_info adds the slots up on the host.
+// Structure: the frame of block_common.hip.h (one kernel, certify in registers or settle through the wave's accumulator,
+// a counter slot per workgroup, the plain kernel of fpe == 1); what is this routine's own:
 //   * LANES OWN COLUMNS.  G is the tile width (q rounded up to a power of two, at most 64; 4 on path 3), a wave holds
 //     S = 64 / G row slices, and each lane keeps BG_R (4; 1 on path 2) 4-term expansions: the register block.  A wave's
 //     item is S * R consecutive rows times one tile; slice s owns the rows r * S + s of it, so that for every r the wave
@@ -24,16 +22,13 @@
 //     with coalesced loads along the unit stride.  The pitch of a staged row is xc + 1 doubles, odd: the S slices'
 //     broadcast reads of one column meet 32 different banks per half wave (ds_read_b64 takes the bank from the address in
 //     units of 4 bytes modulo 64).
-//   * Rounding.  The beta term goes into the lane's expansion (sp_absorb_beta), spmv_round_fast certifies the rounding in
-//     registers and the lane stores.  What it cannot certify (ties, near-ties inside the margin, spills, non-finite
-//     flags, values outside its range), and every output under fpe == 0, path 1 or the reference rounding mode, is
-//     settled on the spot by the whole wave: the lanes stride the p products of that output straight from memory into the
-//     wave's ONE integer accumulator in LDS, lane 0 adds the beta term, sp_acc_round rounds.  No bitmap, no second kernel.
-//     Y[r, j] is the caller's value until its one store.
-// fpe == 1 runs the same structure with plain fp64 sums in the order of i (deterministic, not exact; no counters).
+//   * Rounding.  The beta term goes into the lane's expansion (sp_absorb_beta) before the certificate.  The fall-back
+//     (bg_resolve) strides the p products of the output straight from memory, lane 0 adds the beta term.  Y[r, j] is the
+//     caller's value until its one store.
+// The plain sums of fpe == 1 run in the order of i.
 // Rows are independent and nothing crosses lanes: a row-sharded caller with C replicated needs no communication.
 #include "../../include/exblas_hip.h"
-#include "spmv_common.hip.h"
+#include "block_common.hip.h"
 
 namespace exb {
 namespace {
@@ -51,41 +46,19 @@ struct BgArgs {
     double alpha, beta;
 };
 
-// a lane's expansion has no accumulator behind it: whatever would spill sends the output to the wave's accumulator
-struct BgLaneSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
-};
-
 // What no lane could certify: output (row, col) through the wave's integer accumulator, every operand from memory.
 // Wave-uniform.
 __device__ void bg_resolve(const BgArgs &A, const double *__restrict__ x, const double *__restrict__ c, double *y,
                            long long row, long long col, long long *acc)
 {
-    const int lane = threadIdx.x & 63;
-    unsigned fl = 0;
-    RowSink sink{acc, fl};
     const double *xr = x + row * A.ldx, *cj = c + col;
-    for (int i = lane; i < A.p; i += 64) {
-        double e;
-        const double pr = two_prod(xr[i], A.alpha * cj[(long long)i * A.ldc], e);
-        sink_product(sink, pr, e);
-    }
     double *yp = y + row * A.ldy + col;
-    if (lane == 0 && A.beta != 0.0) {
-        const double yv = *yp;
-        if (A.beta == 1.0) {
-            sink.add(yv);
-        } else {
-            double e;
-            const double pr = two_prod(A.beta, yv, e);
-            sink_product(sink, pr, e);
-        }
-    }
-    sp_wave_sync();
-    const double v = sp_acc_round(acc, NonFiniteLanes(fl).of(~0ull), A.round_mode);
-    if (lane == 0) *yp = v;
+    const double v = blk_resolve(
+        acc, A.p, A.round_mode, [&](int i, double &a, double &b) { a = xr[i], b = A.alpha * cj[(long long)i * A.ldc]; },
+        [&](RowSink &sink) {
+            if (A.beta != 0.0) blk_sink_term(sink, A.beta, *yp);
+        });
+    if ((threadIdx.x & 63) == 0) *yp = v;
     sp_wave_sync();
 }
 
@@ -165,7 +138,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_bgemm(BgArgs A, const double *__re
                                     double pr[BG_U], er[BG_U];
 #pragma unroll
                                     for (int u = 0; u < BG_U; ++u) pr[u] = two_prod(xr[u], cv[u], er[u]);
-                                    BgLaneSink sink{flags[r]};
+                                    SpLaneSink sink{flags[r]};
                                     fpe_absorb_prod<SP_N, true, BG_U>(f[r], pr, er, sink);
                                 }
                             }
@@ -185,7 +158,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_bgemm(BgArgs A, const double *__re
                 if constexpr (PLAIN) {
                     if (ok) *yp = (A.beta == 0.0) ? ps[r] : ps[r] + A.beta * *yp;
                 } else {
-                    BgLaneSink sink{flags[r]};
+                    SpLaneSink sink{flags[r]};
                     if (!A.force) sp_absorb_beta(f[r], ok, A.beta, yp, 0, sink);
                     bool fb = false;
                     if (ok) {
@@ -205,17 +178,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_bgemm(BgArgs A, const double *__re
             }
         }
     }
-    // the workgroup's counters into its own slot: plain stores, nothing to zero beforehand (both 0 for the plain kernel)
-    if (lane == 0) {
-        cnt[w][0] = n_reg;
-        cnt[w][1] = n_fb;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        unsigned long long t = 0;
-        for (int v = 0; v < SP_WAVES; ++v) t += cnt[v][threadIdx.x];
-        slots[2 * (long long)blockIdx.x + threadIdx.x] = (long long)t;
-    }
+    blk_store_counters(cnt, n_reg, n_fb, slots, blockIdx.x);
 }
 
 }  // namespace
@@ -227,8 +190,7 @@ hipError_t exbgemm_dispatch(Ctx &c, long long n, int p, int q, double alpha, con
                             int round_mode, hipStream_t st)
 {
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
-    c.bgemm_info_dev = nullptr;
-    c.bgemm_info_blocks = 0;
+    c.bgemm_slots = SlotInfo();
     if (n == 0 || q == 0) return hipSuccess;
     const int path = c.bgemm_path;
     BgArgs A;
@@ -245,18 +207,15 @@ hipError_t exbgemm_dispatch(Ctx &c, long long n, int p, int q, double alpha, con
     A.lgxc = 0;
     while ((1 << A.lgxc) < xc) ++A.lgxc;
     A.ch = min(chmax, max(1, (p + xc - 1) / xc) * xc);   // a multiple of xc
-    A.force = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
-    A.round_mode = fpe == 1 ? 0 : round_mode;
+    const StRule rule = st_rule(fpe, path, round_mode);
+    A.force = rule.force_fb, A.round_mode = rule.round_mode;
     A.nrb = (n + (long long)SP_WAVES * RW - 1) / ((long long)SP_WAVES * RW);
     A.nitems = A.nrb * tiles;
-    int grid = (int)min((long long)c.num_cu * 8, A.nitems);
-    A.per = (A.nitems + grid - 1) / grid;
-    grid = (int)((A.nitems + A.per - 1) / A.per);
+    const auto [grid, per] = blk_partition(c, A.nitems);
+    A.per = per;
     hipError_t e = hipSuccess;
-    long long *slots = (long long *)workspace(c, (size_t)grid * 2 * sizeof(long long), st, &e);
+    long long *slots = blk_reserve_slots(c, c.bgemm_slots, grid, st, &e);
     if (!slots) return e;
-    c.bgemm_info_dev = slots;
-    c.bgemm_info_blocks = grid;
     const size_t lds = ((size_t)A.ch * G + (size_t)SP_WAVES * RW * (xc + 1)) * sizeof(double);
     if (fpe == 1)
         hipLaunchKernelGGL((k_bgemm<true>), dim3(grid), dim3(SP_BLOCK), lds, st, A, x, cm, y, slots);

@@ -10,8 +10,9 @@
 // exactly, 0 does not read B, anything else adds the error-free product, both parts.  Every path sums that multiset of
 // TwoProd pairs exactly, so the bits depend on the data, (uplo, transt, diag, alpha) and the rounding mode only.
 //
-// Structure: ONE kernel and nothing else (no preset kernel, no memset, no mailbox, no ticket: rows are independent, the
-// chain runs along a row).  The counters are ExBGEMM's: every workgroup stores its own pair into its slot.
+// Structure: the frame of block_common.hip.h (one kernel, certify in registers or settle through the wave's accumulator,
+// a counter slot per workgroup, the plain kernel of fpe == 1).  No mailbox and no ticket: rows are independent, the chain
+// runs along a row.  What is this routine's own:
 //   * LANES OWN ROWS.  A wave's item is RW consecutive rows (a power of two, 64 when the LDS allows, 4 on path 3); lane
 //     lr + s * RW is slice s of row lr.  The S = 64 / RW slices of a row share the earlier columns i round-robin in groups
 //     of four and are merged exactly by the shuffle cascade of the sparse routines before the certificate.
@@ -25,14 +26,11 @@
 //     four earlier columns it reads its own four x_ri from LDS and the 16 entries of op(T) (broadcast).  Then the alpha
 //     term (sp_absorb_beta), the merge, and the 4 x 4 diagonal block one column after the other: certify, divide, write
 //     x to the LDS row, multiply into the later columns of the block.
-//   * Rounding.  spmv_round_fast certifies in registers.  What it cannot certify (ties, near-ties inside the margin,
-//     spills, non-finite flags, values outside its range), and every output under fpe == 0, path 1 or the reference
-//     rounding mode, is settled on the spot by the whole wave, before the lane's chain goes on: the lanes stride the
-//     earlier columns of that one output (x_ri from the wave's LDS row, op(T)(i, j) from memory) into the wave's ONE
-//     integer accumulator in LDS, lane 0 adds the alpha term, sp_acc_round rounds, then the division.
-// fpe == 1 runs the same structure with plain fp64 sums (deterministic, not exact; no counters).
+//   * Rounding.  The fall-back (bt_resolve) settles an output before the lane's chain goes on: the lanes stride the
+//     earlier columns of that one output (x_ri from the wave's LDS row, op(T)(i, j) from memory), lane 0 adds the alpha
+//     term, then the division.
 #include "../../include/exblas_hip.h"
-#include "spmv_common.hip.h"
+#include "block_common.hip.h"
 #include <atomic>
 
 namespace exb {
@@ -49,13 +47,6 @@ struct BtArgs {
     long long n, ldx, rs, cs, nitems, per;   // op(T)(i, j) = t[phys(i) * rs + phys(j) * cs]: one of rs, cs is 1, the other ldt
     int p, lgr, nb, lgch, lgcw, tsz, rev, unit, force, round_mode, dq, dr;   // dq, dr: 64 / p, 64 % p
     double alpha;
-};
-
-// a lane's expansion has no accumulator behind it: whatever would spill sends the output to the wave's accumulator
-struct BtLaneSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
 };
 
 // substitution position -> physical column of X, row / column of T
@@ -84,31 +75,19 @@ __device__ __forceinline__ void bt_stage(const BtArgs &A, const double *__restri
 // op(T) from memory.  The row holds x at the earlier columns and b at j.  Wave-uniform.
 __device__ void bt_resolve(const BtArgs &A, const double *__restrict__ t, double *xrow, int j, long long *acc)
 {
-    const int lane = threadIdx.x & 63;
-    unsigned fl = 0;
-    RowSink sink{acc, fl};
     const int pj = bt_phys(A, j);
     const double *tj = t + pj * A.cs;
-    for (int i = lane; i < j; i += 64) {
-        const int pi = bt_phys(A, i);
-        double e;
-        const double pr = two_prod(tj[pi * A.rs], -xrow[pi], e);
-        sink_product(sink, pr, e);
-    }
-    if (lane == 0 && A.alpha != 0.0) {
-        const double b = xrow[pj];
-        if (A.alpha == 1.0) {
-            sink.add(b);
-        } else {
-            double e;
-            const double pr = two_prod(A.alpha, b, e);
-            sink_product(sink, pr, e);
-        }
-    }
-    sp_wave_sync();
-    double v = sp_acc_round(acc, NonFiniteLanes(fl).of(~0ull), A.round_mode);
+    double v = blk_resolve(
+        acc, j, A.round_mode,
+        [&](int i, double &a, double &b) {
+            const int pi = bt_phys(A, i);
+            a = tj[pi * A.rs], b = -xrow[pi];
+        },
+        [&](RowSink &sink) {
+            if (A.alpha != 0.0) blk_sink_term(sink, A.alpha, xrow[pj]);
+        });
     if (!A.unit) v = v / tj[pj * A.rs];
-    if (lane == 0) xrow[pj] = v;
+    if ((threadIdx.x & 63) == 0) xrow[pj] = v;
     sp_wave_sync();
 }
 
@@ -194,7 +173,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_btrsm(BtArgs A, const double *__re
                                     }
                                 }
                                 if constexpr (!PLAIN) {
-                                    BtLaneSink sink{flags[c]};
+                                    SpLaneSink sink{flags[c]};
                                     fpe_absorb_prod<SP_N, true, BT_U>(f[c], pr, er, sink);
                                 }
                             }
@@ -211,7 +190,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_btrsm(BtArgs A, const double *__re
                             if (leader && A.alpha != 0.0) ps[c] += A.alpha == 1.0 ? xrow[pj] : A.alpha * xrow[pj];
                             for (int st = RW; st < 64; st <<= 1) ps[c] += __shfl_down(ps[c], st, 64);
                         } else {
-                            BtLaneSink sink{flags[c]};
+                            SpLaneSink sink{flags[c]};
                             sp_absorb_beta(f[c], leader, A.alpha, xrow, pj, sink);
                             for (int st = RW; st < 64; st <<= 1)
                                 sp_cascade_step(f[c], flags[c], st, (lane & (2 * st - 1)) < RW, sink);
@@ -260,7 +239,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_btrsm(BtArgs A, const double *__re
                                 } else {
                                     double pr[1], er[1];
                                     pr[0] = two_prod(tv, -v, er[0]);
-                                    BtLaneSink sink{flags[c2]};
+                                    SpLaneSink sink{flags[c2]};
                                     fpe_absorb_prod<SP_N, true, 1>(f[c2], pr, er, sink);
                                 }
                             }
@@ -278,17 +257,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_btrsm(BtArgs A, const double *__re
         }
         sp_wave_sync();   // the rows are stored before the next item replaces them
     }
-    // the workgroup's counters into its own slot: plain stores, nothing to zero beforehand (both 0 for the plain kernel)
-    if (lane == 0) {
-        cnt[w][0] = n_reg;
-        cnt[w][1] = n_fb;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        unsigned long long tot = 0;
-        for (int v = 0; v < SP_WAVES; ++v) tot += cnt[v][threadIdx.x];
-        slots[2 * (long long)blockIdx.x + threadIdx.x] = (long long)tot;
-    }
+    blk_store_counters(cnt, n_reg, n_fb, slots, blockIdx.x);
 }
 
 // more than 64 KiB of dynamic LDS has to be asked for, once per device and instantiation (no stream operation)
@@ -312,8 +281,7 @@ hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long
                             int ldt, double *x, long long ldx, int fpe, int early_exit, int round_mode, hipStream_t st)
 {
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
-    c.btrsm_info_dev = nullptr;
-    c.btrsm_info_blocks = 0;
+    c.btrsm_slots = SlotInfo();
     if (n == 0 || p == 0) return hipSuccess;
     const int path = c.btrsm_path;
     const bool lower = (uplo == 'L' || uplo == 'l'), trans = (transt == 'T' || transt == 't');
@@ -340,18 +308,15 @@ hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long
     A.lgr = 0;
     while ((1 << A.lgr) < rw) ++A.lgr;
     A.dq = 64 / p, A.dr = 64 % p;
-    A.force = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
-    A.round_mode = fpe == 1 ? 0 : round_mode;
+    const StRule rule = st_rule(fpe, path, round_mode);
+    A.force = rule.force_fb, A.round_mode = rule.round_mode;
     A.nitems = (n + (long long)SP_WAVES * rw - 1) / ((long long)SP_WAVES * rw);
-    int grid = (int)min((long long)c.num_cu * 8, A.nitems);
-    A.per = (A.nitems + grid - 1) / grid;
-    grid = (int)((A.nitems + A.per - 1) / A.per);
+    const auto [grid, per] = blk_partition(c, A.nitems);
+    A.per = per;
     hipError_t e = bt_lds_optin(c.device);
     if (e != hipSuccess) return e;
-    long long *slots = (long long *)workspace(c, (size_t)grid * 2 * sizeof(long long), st, &e);
+    long long *slots = blk_reserve_slots(c, c.btrsm_slots, grid, st, &e);
     if (!slots) return e;
-    c.btrsm_info_dev = slots;
-    c.btrsm_info_blocks = grid;
     const size_t lds = ((size_t)A.tsz + (size_t)SP_WAVES * rw * pitch) * sizeof(double);
     if (fpe == 1)
         hipLaunchKernelGGL((k_btrsm<true>), dim3(grid), dim3(SP_BLOCK), lds, st, A, t, x, slots);

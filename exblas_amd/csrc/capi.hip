@@ -378,16 +378,17 @@ int exblas_last_trsm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::t
 
 // The counters of the last ExBGEMM / ExBTRSM on the last-used layer: the kernel leaves one pair per workgroup (nothing
 // has to be zeroed before it runs), they are added up here.  All 0 after a call that launched nothing.  Synchronises.
-static int last_slot_info(const long long *CtxWsPtrs::*info_dev, int CtxWsPtrs::*blocks, int64_t *out4)
+static int last_slot_info(SlotInfo CtxWsPtrs::*slots, int64_t *out4)
 {
     if (!out4) return (int)hipErrorInvalidValue;
     for (int i = 0; i < 4; ++i) out4[i] = 0;
     Ctx &c = ctx(-1, g_last_layer[current_device()]);
     std::lock_guard<std::mutex> lk(c.mu);
-    if (!(c.*info_dev) || c.*blocks <= 0) return 0;
-    std::vector<long long> h((size_t)(c.*blocks) * 2);
+    const SlotInfo &s = c.*slots;
+    if (!s.dev || s.blocks <= 0) return 0;
+    std::vector<long long> h((size_t)s.blocks * 2);
     hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(h.data(), c.*info_dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), s.dev, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return (int)e;
     for (size_t b = 0; b < h.size(); b += 2) {
         out4[0] += h[b];
@@ -397,22 +398,13 @@ static int last_slot_info(const long long *CtxWsPtrs::*info_dev, int CtxWsPtrs::
 }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] = out[3] = 0
-int exblas_last_bgemm_info(int64_t *out4)
-{
-    return last_slot_info(&CtxWsPtrs::bgemm_info_dev, &CtxWsPtrs::bgemm_info_blocks, out4);
-}
+int exblas_last_bgemm_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::bgemm_slots, out4); }
 
 // the same for ExBTRSM
-int exblas_last_btrsm_info(int64_t *out4)
-{
-    return last_slot_info(&CtxWsPtrs::btrsm_info_dev, &CtxWsPtrs::btrsm_info_blocks, out4);
-}
+int exblas_last_btrsm_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::btrsm_slots, out4); }
 
 // the same for ExPOTRF: out[0] + out[1] is the number of entries the call fixed (the radicand of a breakdown included)
-int exblas_last_potrf_info(int64_t *out4)
-{
-    return last_slot_info(&CtxWsPtrs::potrf_info_dev, &CtxWsPtrs::potrf_info_blocks, out4);
-}
+int exblas_last_potrf_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::potrf_slots, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,

@@ -45,6 +45,12 @@ struct CtxKnobs {
                              // of width 4
 };
 
+// The counter slots a block routine's kernel left in the workspace (block_common.hip.h): a pair per workgroup
+struct SlotInfo {
+    const long long *dev = nullptr;   // nullptr: the call launched nothing
+    int blocks = 0;                   // how many workgroups there were
+};
+
 // The pointers of a context that point INTO its workspace block (Ctx::ws): exblas_release_workspace resets this struct
 // whole when it frees the block, so a pointer declared here is forgotten with it; nothing else has to be edited.
 // Known wart, left as it is: the block is shared, so a last_*_info query after a DIFFERENT routine has reused the
@@ -59,12 +65,7 @@ struct CtxWsPtrs {
     const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
-    const long long *bgemm_info_dev = nullptr;   // the last ExBGEMM call's counter slots, a pair per workgroup (nullptr: it
-    int bgemm_info_blocks = 0;                   // launched nothing), and how many workgroups there were
-    const long long *btrsm_info_dev = nullptr;   // the same for the last ExBTRSM call
-    int btrsm_info_blocks = 0;
-    const long long *potrf_info_dev = nullptr;   // the same for the last ExPOTRF call (one workgroup)
-    int potrf_info_blocks = 0;
+    SlotInfo bgemm_slots, btrsm_slots, potrf_slots;   // of the last ExBGEMM, ExBTRSM and ExPOTRF (one workgroup) call
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference

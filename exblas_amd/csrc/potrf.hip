@@ -13,7 +13,9 @@
 // rest of row j and all later rows as they were, and reports j + 1 in the info word; otherwise 0.  The word is written
 // by every launch with a plain store.  The other triangle and the padding of a column are neither read nor written.
 //
-// Structure: ONE kernel of ONE workgroup (no mailbox, no ticket, no memset; the chain of p pivots is the problem).
+// Structure: the frame of block_common.hip.h (one kernel, certify in registers or settle through the wave's accumulator,
+// the counter slot, the plain kernel of fpe == 1) with ONE workgroup (no mailbox, no ticket; the chain of p pivots is the
+// problem).  What is this routine's own:
 //   * R(k, i) = g[k * rs + i * cs]: 'U' has rs = 1, 'L' has cs = 1; nothing else knows about uplo.
 //   * p <= 64 (not on path 3): the triangle is loaded once into LDS along its unit stride (row pitch 65: odd), factored
 //     there and stored back once, the fixed entries only.  Beyond: factored in place in global memory; the rows a wave
@@ -26,15 +28,13 @@
 //     multiply the fixed row into the later rows of the block.
 //   * The tiles beyond (p > 64, path 3) follow after a barrier, a tile per wave, unsliced: they need only the diagonal
 //     block and their own columns.
-//   * Rounding.  spmv_round_fast certifies in registers.  What it cannot certify (ties, near-ties inside the margin,
-//     spills, non-finite flags, values outside its range), and every output under fpe == 0, path 1 or the reference
-//     rounding mode, is settled on the spot by the whole wave through its ONE integer accumulator in LDS (po_resolve).
-//     The radicand is an ordinary output (r_kj against itself); it is settled before the rest of its row is counted.
+//   * Rounding.  The fall-back (po_resolve) hands the rounded value to every lane; the square root or the division
+//     follows.  The radicand is an ordinary output (r_kj against itself); it is settled before the rest of its row is
+//     counted.
 //   * Waves: four, one per SIMD; while wave 0 walks the diagonal block the others wait at the barrier.  Measured (DESIGN
 //     5m): 3.1 to 3.5 us per pivot at p = 16 .. 64.
-// fpe == 1 runs the same structure with plain fp64 sums (deterministic, not exact; no counters).
 #include "../../include/exblas_hip.h"
-#include "spmv_common.hip.h"
+#include "block_common.hip.h"
 
 namespace exb {
 namespace {
@@ -48,12 +48,6 @@ constexpr int PO_PITCH = 65;    // row pitch of the staged triangle (odd)
 struct PoArgs {
     long long rs, cs;   // R(k, i) = g[k * rs + i * cs]: one of them is 1, the other ldg
     int p, ldg, nb, tw, force, round_mode;
-};
-
-struct PoLaneSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
 };
 
 // the factor while it is made: the LDS triangle (STAGED) or G itself
@@ -73,17 +67,9 @@ struct PoStore {
 template <bool STAGED>
 __device__ double po_resolve(const PoArgs &A, const PoStore<STAGED> &R, int j, int i, long long *acc)
 {
-    const int lane = threadIdx.x & 63;
-    unsigned fl = 0;
-    RowSink sink{acc, fl};
-    for (int k = lane; k < j; k += 64) {
-        double e;
-        const double pr = two_prod(R.at(k, j), -R.at(k, i), e);
-        sink_product(sink, pr, e);
-    }
-    if (lane == 0) sink.add(R.at(j, i));
-    sp_wave_sync();
-    const double v = sp_acc_round(acc, NonFiniteLanes(fl).of(~0ull), A.round_mode);
+    const double v = blk_resolve(
+        acc, j, A.round_mode, [&](int k, double &a, double &b) { a = R.at(k, j), b = -R.at(k, i); },
+        [&](RowSink &sink) { sink.add(R.at(j, i)); });
     sp_wave_sync();
     return v;
 }
@@ -119,7 +105,7 @@ __device__ __forceinline__ void po_earlier(const PoArgs &A, const PoStore<STAGED
                     }
                 }
                 if constexpr (!PLAIN) {
-                    PoLaneSink sink{flags[c]};
+                    SpLaneSink sink{flags[c]};
                     fpe_absorb_prod<SP_N, true, PO_U>(f[c], pr, er, sink);
                 }
             }
@@ -140,7 +126,7 @@ __device__ __forceinline__ void po_add_g(const PoArgs &A, const PoStore<STAGED> 
                 ps[c] += gv;
             } else {
                 double pr[1] = {gv}, er[1] = {0.0};
-                PoLaneSink sink{flags[c]};
+                SpLaneSink sink{flags[c]};
                 fpe_absorb_prod<SP_N, true, 1>(f[c], pr, er, sink);
             }
         }
@@ -228,7 +214,7 @@ __device__ __forceinline__ int po_rows(const PoArgs &A, const PoStore<STAGED> &R
                     } else {
                         double pr[1], er[1];
                         pr[0] = two_prod(a, -b, er[0]);
-                        PoLaneSink sink{flags[c2]};
+                        SpLaneSink sink{flags[c2]};
                         fpe_absorb_prod<SP_N, true, 1>(f[c2], pr, er, sink);
                     }
                 }
@@ -305,7 +291,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_potrf(PoArgs A, double *g, int *in
 #pragma unroll
                                 for (int t = 0; t < SP_N; ++t) q[t] = scr[s - 1][c][t][lane];
                                 flags[c] |= scf[s - 1][c][lane];
-                                PoLaneSink sink{flags[c]};
+                                SpLaneSink sink{flags[c]};
                                 fpe_cascade<SP_N, true, SP_N>(f[c], q, 0, sink);
                             }
                         }
@@ -348,17 +334,8 @@ __global__ void __launch_bounds__(SP_BLOCK) k_potrf(PoArgs A, double *g, int *in
             if (k <= i && (k < nfix || (k == i && k == nfix))) g[(long long)a * A.ldg + b] = tri[k * PO_PITCH + i];
         }
     }
-    // the info word and the counters: plain stores, nothing to clear beforehand (both counters 0 for the plain kernel)
-    if (lane == 0) {
-        cnt[w][0] = n_reg;
-        cnt[w][1] = n_fb;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        unsigned long long tot = 0;
-        for (int v = 0; v < SP_WAVES; ++v) tot += cnt[v][threadIdx.x];
-        slots[threadIdx.x] = (long long)tot;
-    }
+    // the counters and the info word: plain stores, nothing to clear beforehand
+    blk_store_counters(cnt, n_reg, n_fb, slots, 0);
     if (threadIdx.x == 64) info[0] = st;
 }
 
@@ -370,8 +347,7 @@ hipError_t expotrf_dispatch(Ctx &c, char uplo, int p, double *g, int ldg, int *i
                             hipStream_t st)
 {
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
-    c.potrf_info_dev = nullptr;
-    c.potrf_info_blocks = 0;
+    c.potrf_slots = SlotInfo();
     if (p == 0) return hipSuccess;
     const int path = c.potrf_path;
     const bool lower = (uplo == 'L' || uplo == 'l');
@@ -380,14 +356,12 @@ hipError_t expotrf_dispatch(Ctx &c, char uplo, int p, double *g, int ldg, int *i
     A.rs = lower ? (long long)ldg : 1ll, A.cs = lower ? 1ll : (long long)ldg;
     A.nb = path == 2 ? 1 : PO_NB;
     A.tw = path == 3 ? PO_SMALL : PO_TILE;
-    A.force = (fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0;
-    A.round_mode = fpe == 1 ? 0 : round_mode;
+    const StRule rule = st_rule(fpe, path, round_mode);
+    A.force = rule.force_fb, A.round_mode = rule.round_mode;
     const bool staged = path != 3 && p <= PO_TILE;
     hipError_t e = hipSuccess;
-    long long *slots = (long long *)workspace(c, 2 * sizeof(long long), st, &e);
+    long long *slots = blk_reserve_slots(c, c.potrf_slots, 1, st, &e);
     if (!slots) return e;
-    c.potrf_info_dev = slots;
-    c.potrf_info_blocks = 1;
     if (fpe == 1) {
         if (staged) hipLaunchKernelGGL((k_potrf<true, true>), dim3(1), dim3(SP_BLOCK), 0, st, A, g, info, slots);
         else hipLaunchKernelGGL((k_potrf<true, false>), dim3(1), dim3(SP_BLOCK), 0, st, A, g, info, slots);

@@ -4,7 +4,9 @@
 // with the spill into the row's accumulator behind it (sp_certify_or_spill), the rounding of an LDS integer accumulator
 // (sp_acc_round, with sp_pick and sp_acc_clear), the union of a lane group's non-finite flags (NonFiniteLanes) and the
 // wave's LDS hand-over (sp_wave_sync).  Split rows: the chunk-base scan and the chunk-owner search.  Host side: geometry
-// constants, the choice of index type and plain / exact kernels, the split thresholds.
+// constants, the choice of index type and plain / exact kernels, the split thresholds.  For the routines built on these
+// pieces (sptrs_common.hip.h, block_common.hip.h) also the sink of a lane's expansion without an accumulator (SpLaneSink)
+// and the rule for fpe, path and rounding mode (st_rule).
 #pragma once
 #include "superacc.hip.h"
 #include "fpe.hip.h"
@@ -47,6 +49,14 @@ struct RowSink {
         flags |= SP_SPILL;
     }
     __device__ __forceinline__ void note(unsigned bits) { flags |= bits | SP_SPILL; }
+};
+
+// the sink of a lane's expansion that has no accumulator behind it (the block solves, block_common.hip.h): whatever
+// would spill only raises SP_SPILL, which sends the output to the routine's fall-back
+struct SpLaneSink {
+    unsigned &flags;
+    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
+    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
 };
 
 // Certified round-to-nearest-even of the exact value of an expansion f (any N terms, finite, |f| < 2^1012).
@@ -256,6 +266,17 @@ __global__ void __launch_bounds__(1024) k_spmv_long_prep(const I *__restrict__ r
 }
 
 static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The rule of the solves and the block routines (sptrs_common.hip.h, block_common.hip.h) for fpe, path and rounding mode.
+// fpe: 0 every output from the integer accumulator, 1 the plain sums, 2..8 the expansions; path 1 and the reference
+// rounding mode send every output through the accumulator as well; the path it was made for travels with it
+struct StRule {
+    int force_fb, round_mode, path;
+};
+static inline StRule st_rule(int fpe, int path, int round_mode)
+{
+    return {(fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0, fpe == 1 ? 0 : round_mode, path};
+}
 
 // exblas_set_spmv_path / exblas_set_spmm_path -> which rows are split and at what chunk: 3 splits every row at the small
 // chunk, 2 splits none, the others keep the routine's own threshold and chunk

@@ -1,13 +1,13 @@
 // sptrs_common.hip.h -- what the three mailbox solves (sptrsv.hip: ExSpTRSV, sptrsm.hip: ExSpTRSM, trsm.hip: ExTRSM) share.
 // All three: the workspace header and its carving (st_workspace), the mailbox conventions (a reserved "not posted"
 // pattern, the canonical NaN, agent-scope relaxed atomic store and load, a wave-uniform poll loop with a light sleep and
-// the 2 s watchdog), the preset kernel, the ticket take, the counters and their flush, the rule for fpe, path and rounding
-// mode (st_rule), the grid size (st_grid), the decoding of uplo / diag.  The two sparse ones: the classification of one
-// stored entry.  The two block solves: the tile widths, the sink of a lane's expansion (StLaneSink) and the host loop
-// over the column panels (StPanel, st_block_solve).  Their lane geometry, publication and certify / fall-back blocks stay
-// one copy per file: the exact kernels sit at the SGPR limit, every shared spelling compiled changed the count of spilled
-// SGPRs they read back, and all of them together ran 1 to 4 % slower (profiles/block_solve_refactor_ab.md).  A change to
-// one copy has to be made in the other by hand.
+// the 2 s watchdog), the preset kernel, the ticket take, the counters and their flush, the grid size (st_grid), the
+// decoding of uplo / diag; the rule for fpe, path and rounding mode (st_rule) is spmv_common.hip.h's.  The two sparse ones:
+// the classification of one stored entry.  The two block solves: the tile widths, the sink of a lane's expansion
+// (spmv_common.hip.h's SpLaneSink) and the host loop over the column panels (StPanel, st_block_solve).  Their lane
+// geometry, publication and certify / fall-back blocks stay one copy per file: the exact kernels sit at the SGPR limit,
+// every shared spelling compiled changed the count of spilled SGPRs they read back, and all of them together ran 1 to 4 %
+// slower (profiles/block_solve_refactor_ab.md).  A change to one copy has to be made in the other by hand.
 #pragma once
 #include "spmv_common.hip.h"
 
@@ -117,13 +117,6 @@ __device__ __forceinline__ void st_flush_counters(const StCounters &cn, long lon
 constexpr int ST_TILE = 64;        // columns per tile ...
 constexpr int ST_TILE_SMALL = 4;   // ... and on path 3, where the panel is as narrow
 
-// a lane's expansion has no accumulator behind it: whatever would spill sends the column to the fallback loop
-struct StLaneSink {
-    unsigned &flags;
-    __device__ __forceinline__ void add(double) { flags |= SP_SPILL; }
-    __device__ __forceinline__ void note(unsigned) { flags |= SP_SPILL; }
-};
-
 // ticket := 0, mailbox of n values := "not posted" (a kernel, not memset nodes: one node kind in a captured graph); with
 // `first` the whole header is cleared: the counters and the watchdog flag, which add up over the launches that follow
 static __global__ void __launch_bounds__(SP_BLOCK) k_sptrs_preset(long long n, int first, long long *__restrict__ hdr,
@@ -157,16 +150,6 @@ static inline hipError_t st_workspace(Ctx &c, size_t slots, hipStream_t st, StSp
     char *base = (char *)workspace(c, ST_HDR_BYTES + slots * sizeof(double), st, &e);
     if (base) w = {(long long *)base, (double *)(base + ST_HDR_BYTES)};
     return base ? hipSuccess : e;
-}
-
-// fpe: 0 every output from the integer accumulator, 1 the plain solve, 2..8 the expansions; path 1 and the reference
-// rounding mode send every output through the accumulator as well; the path it was made for travels with it
-struct StRule {
-    int force_fb, round_mode, path;
-};
-static inline StRule st_rule(int fpe, int path, int round_mode)
-{
-    return {(fpe != 1 && (fpe == 0 || path == 1 || round_mode)) ? 1 : 0, fpe == 1 ? 0 : round_mode, path};
 }
 
 // 'U' solves in reverse row order; diag 'U' divides by nothing

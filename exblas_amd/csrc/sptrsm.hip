@@ -40,7 +40,7 @@
 //
 // Watchdog: that of sptrsv.hip (2 s on one poll, the header flag, everything behind it drains as NaN).
 // fpe == 1 runs the same structure with plain fp64 sums in a fixed order (deterministic, not exact).
-// sptrs_common.hip.h holds what is shared with trsm.hip (StLaneSink, the tile widths, the host loop st_block_solve).  The
+// sptrs_common.hip.h holds what is shared with trsm.hip (the tile widths, the host loop st_block_solve).  The
 // lane geometry, the publication of a solved value and the certify / fall-back block are the same text in both files:
 // a fix to one goes into the other (sptrs_common.hip.h says why they are not one helper).
 #include "../../include/exblas_hip.h"
@@ -96,7 +96,7 @@ __device__ __forceinline__ void tm_row(const TmArgs &A, bool count, long long po
     while (ns < S && (long long)ns * TM_U < p1 - p0) ns <<= 1;
     unsigned flags = 0;
     long long kdiag = ST_NO_DIAG;
-    StLaneSink sink{flags};
+    SpLaneSink sink{flags};
     StCounters seen;   // the structure of the row as this lane met it
     double f[SP_N];
 #pragma unroll

@@ -45,7 +45,7 @@
 //
 // Watchdog: that of the sparse solves (2 s on one poll, the header flag, everything behind it drains as NaN).
 // fpe == 1 runs the same structure with plain fp64 sums in a fixed order (deterministic, not exact).
-// sptrs_common.hip.h holds what is shared with sptrsm.hip (StLaneSink, the tile widths, the host loop st_block_solve).  The
+// sptrs_common.hip.h holds what is shared with sptrsm.hip (the tile widths, the host loop st_block_solve).  The
 // lane geometry, the publication of a solved value and the certify / fall-back block are the same text in both files:
 // a fix to one goes into the other (sptrs_common.hip.h says why they are not one helper).
 #include "../../include/exblas_hip.h"
@@ -207,7 +207,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                     }
                 }
                 if constexpr (!PLAIN) {
-                    StLaneSink sink{flags[r]};
+                    SpLaneSink sink{flags[r]};
                     fpe_absorb_prod<SP_N, true, TR_U>(f[r], p, er, sink);
                 }
             }
@@ -231,7 +231,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                 if (leader) ps[r] += L.xs[r * 64 + g];
                 for (int st = G; st < 64; st <<= 1) ps[r] += __shfl_down(ps[r], st, 64);
             } else {
-                StLaneSink sink{flags[r]};
+                SpLaneSink sink{flags[r]};
                 double bv[1] = {leader ? L.xs[r * 64 + g] : 0.0};
                 sp_absorb_beta(f[r], leader, 1.0, bv, 0, sink);
                 for (int st = G; st < 64; st <<= 1) sp_cascade_step(f[r], flags[r], st, (lane & (2 * st - 1)) < G, sink);
@@ -297,7 +297,7 @@ __device__ __forceinline__ void tr_item(const TrArgs &A, long long pos0, int til
                     } else {
                         double p[1], er[1];
                         p[0] = two_prod(av, -v, er[0]);
-                        StLaneSink sink{flags[r2]};
+                        SpLaneSink sink{flags[r2]};
                         fpe_absorb_prod<SP_N, true, 1>(f[r2], p, er, sink);
                     }
                 }

@@ -300,3 +300,35 @@ def test_release_workspace_forgets_every_pointer_into_it(ex):
     info = (C.c_int * 8)(7, 7, 7, 7, 7, 7, 7, 7)
     assert lib.exblas_last_gemm_info(info) == 0 and info[0] == 0
     assert (_bits(ex.exspmv_dev(A, b)) == before).all()
+
+
+def test_release_workspace_forgets_the_block_routines_counter_slots(ex):
+    """The same for the routines whose last_*_info follows a pointer AND a count into the workspace (ExBGEMM, ExBTRSM,
+    ExPOTRF: a pair of counters per workgroup) and for ExTRSM's header: after exblas_release_workspace each query writes
+    zeros and returns 0, and the next call of each routine gives the bits it gave before."""
+    import ctypes as C
+    import torch
+    lib = ex.load_library()
+    n, p = 70, 3
+    r = np.arange(n, dtype=np.float64)
+    X0 = torch.from_numpy(1.0 + np.outer(r, [1.0, -2.0, 3.0]) / 128.0 + np.outer(r % 7, [0.5, 0.25, -0.125])).cuda()
+    A = torch.from_numpy(np.tril(1.0 / (1.0 + np.abs(r[:, None] - r[None, :]))) + 2.0 * np.eye(n)).cuda()
+    Cm = torch.tensor([[1.0, 0.5, -0.25], [0.0, 2.0, 0.75], [3.0, -1.0, 1.5]], dtype=torch.float64, device="cuda")
+    M = np.array([[2.0, 0.5, -0.25], [0.0, 1.5, 0.75], [0.0, 0.0, 1.25]])
+    G0 = torch.from_numpy(M.T @ M).cuda()               # well conditioned: the Gram matrix of a 3 x 3 triangle
+    T = torch.from_numpy(M).cuda()
+
+    def calls():
+        G, info = ex.expotrf_dev(G0.clone(), "U")
+        return [_bits(ex.extrsm_dev(A, X0.clone(), "L", "N", "N")), _bits(ex.exbgemm_dev(X0, Cm, 0.5, 2.0, X0.clone())),
+                _bits(ex.exbtrsm_dev(T, X0.clone(), "U", "N", "N")), _bits(G), info.cpu().numpy()]
+
+    before = calls()
+    assert before[4][0] == 0
+    assert lib.exblas_release_workspace() == 0
+    for query in (lib.exblas_last_trsm_info, lib.exblas_last_bgemm_info, lib.exblas_last_btrsm_info,
+                  lib.exblas_last_potrf_info):
+        out4 = (C.c_int64 * 4)(7, 7, 7, 7)
+        assert query(out4) == 0 and list(out4) == [0, 0, 0, 0]
+    for was, now in zip(before, calls()):
+        assert (was == now).all()
