@@ -57,6 +57,10 @@ C_ABI_SYMBOLS = [
     "exblas_exbgemm_dev", "exblas_exbgemm_ctx", "exblas_exbgemm", "exblas_set_bgemm_path", "exblas_last_bgemm_info",
     "exblas_exbtrsm_dev", "exblas_exbtrsm_ctx", "exblas_exbtrsm", "exblas_set_btrsm_path", "exblas_last_btrsm_info",
     "exblas_expotrf_dev", "exblas_expotrf_ctx", "exblas_expotrf", "exblas_set_potrf_path", "exblas_last_potrf_info",
+    "exblas_expotrf_batched_dev", "exblas_expotrf_batched_ctx", "exblas_expotrf_batched", "exblas_set_potrf_batched_path",
+    "exblas_last_potrf_batched_info",
+    "exblas_expotrs_batched_dev", "exblas_expotrs_batched_ctx", "exblas_expotrs_batched", "exblas_set_potrs_batched_path",
+    "exblas_last_potrs_batched_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -234,6 +238,18 @@ def load_library():
     L.exblas_set_potrf_path.argtypes = [i32]
     L.exblas_set_potrf_path.restype = None
     L.exblas_last_potrf_info.argtypes = [C.POINTER(i64)]
+    L.exblas_expotrf_batched_dev.argtypes = [C.c_char, i32, i64, vp, i32, i64, vp, i32, i32, vp]
+    L.exblas_expotrf_batched_ctx.argtypes = [vp] + L.exblas_expotrf_batched_dev.argtypes
+    L.exblas_expotrf_batched.argtypes = [C.c_char, i32, i64, vp, i32, i64, vp, i32, i32]
+    L.exblas_set_potrf_batched_path.argtypes = [i32]
+    L.exblas_set_potrf_batched_path.restype = None
+    L.exblas_last_potrf_batched_info.argtypes = [C.POINTER(i64)]
+    L.exblas_expotrs_batched_dev.argtypes = [C.c_char, C.c_char, i32, i64, i32, vp, i32, i64, vp, i64, i32, i32, vp]
+    L.exblas_expotrs_batched_ctx.argtypes = [vp] + L.exblas_expotrs_batched_dev.argtypes
+    L.exblas_expotrs_batched.argtypes = [C.c_char, C.c_char, i32, i64, i32, vp, i32, i64, vp, i64, i32, i32]
+    L.exblas_set_potrs_batched_path.argtypes = [i32]
+    L.exblas_set_potrs_batched_path.restype = None
+    L.exblas_last_potrs_batched_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -889,6 +905,160 @@ def last_potrf_info():
     return _last_info("potrf")
 
 
+POTRF_BATCHED_MAX_P = 64  # EXBLAS_POTRF_BATCHED_MAX_P: a wider block is refused
+
+
+class _Last2:
+    """the last two dimensions of a 3-D operand (shape and element strides), as _trsm_layout reads them"""
+
+    def __init__(self, shape, stride_of):
+        self.shape = tuple(shape[1:])
+        self._strides = (int(stride_of.stride(1)), int(stride_of.stride(2)))
+
+    def stride(self, i):
+        return self._strides[i]
+
+
+def _batched_triangles(who, name, shape, stride_of, uplo):
+    """The rules of the 3-D operand `name` ([batch, p, p]) of the batched routines, device or host: every matrix has one
+    unit stride among its last two dimensions (_trsm_layout: a row-major matrix is the other triangle of its transpose),
+    stride(0) is the batch stride and the matrices do not overlap.  Returns (uplo, batch, p, ld, stride) for the C call."""
+    if len(shape) != 3:
+        raise ValueError(f"{who}: {name} must be 3-D [batch, p, p]")
+    batch, p = int(shape[0]), int(shape[1])
+    if shape[2] != p:
+        raise ValueError(f"{who}: the matrices of {name} must be square, got shape {tuple(shape)}")
+    if p > POTRF_BATCHED_MAX_P:
+        raise ValueError(f"{who}: p = {p} exceeds EXBLAS_POTRF_BATCHED_MAX_P = {POTRF_BATCHED_MAX_P}")
+    last2 = _Last2(shape, stride_of)
+    if batch == 0:
+        last2._strides = (p, 1)                     # no matrix: any strides do
+    u, _, ld = _trsm_layout(last2, uplo, "N", who)
+    ld = max(ld, 1)
+    stride = int(stride_of.stride(0))
+    if batch > 1 and stride < ld * p:
+        raise ValueError(f"{who}: the matrices of {name} overlap: stride(0) = {stride} < {ld * p}")
+    return u.encode(), batch, p, ld, (stride if batch > 1 else ld * max(p, 1))
+
+
+def _potrf_batched_args(G, uplo, info, fpe, early_exit):
+    """Validates a device batched ExPOTRF call before anything is launched (no GPU needed for that); returns (info, the
+    C arguments up to the stream).  G is never copied; info is allocated when None."""
+    torch = _torch()
+    if not isinstance(G, torch.Tensor) or G.dtype != torch.float64:
+        raise ValueError("expotrf_batched: G must be a float64 torch tensor")
+    u, batch, p, ldg, stride = _batched_triangles("expotrf_batched", "G", tuple(G.shape), G, uplo)
+    fpe = _fpe_0_to_8("expotrf_batched", fpe)
+    if info is not None:
+        if (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.dim() != 1 or info.numel() != batch
+                or (batch > 1 and info.stride(0) != 1)):
+            raise ValueError(f"expotrf_batched: info must be a contiguous int32 torch tensor of batch = {batch} words")
+        if info.device != G.device:
+            raise ValueError("expotrf_batched: G, info must be on one device")
+    _on_gpu("expotrf_batched", G=G)
+    if info is None:
+        info = torch.zeros(batch, dtype=torch.int32, device=G.device)
+    return info, (u, p, batch, _ptr(G), ldg, stride, _ptr(info), fpe, int(bool(early_exit)))
+
+
+def _potrs_sweep(sweep):
+    """'1' (F^T Y = B), '2' (F Z = Y) or 'B' (both) of the batched ExPOTRS, as a C char"""
+    s = str(sweep).upper() if isinstance(sweep, (str, int)) and not isinstance(sweep, bool) else None
+    if s not in ("1", "2", "B"):
+        raise ValueError(f"expotrs_batched: sweep must be '1', '2' or 'B', got {sweep!r}")
+    return s.encode()
+
+
+def _potrs_blocks(n, p, batch):
+    """n rows in blocks of p need ceil(n / p) factors"""
+    if n > 0 and p < 1:
+        raise ValueError("expotrs_batched: the blocks of R are empty (p = 0) but X has rows")
+    want = -(-n // p) if p > 0 else 0
+    if batch != want:
+        raise ValueError(f"expotrs_batched: R holds {batch} blocks of p = {p}, X with n = {n} rows needs {want}")
+
+
+def _potrs_batched_args(R, X, uplo, sweep, fpe, early_exit):
+    """Validates a device batched ExPOTRS call before anything is launched (no GPU needed for that); returns the C
+    arguments up to the stream.  Neither operand is copied."""
+    torch = _torch()
+    for name, t in (("R", R), ("X", X)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"expotrs_batched: {name} must be a float64 torch tensor")
+    if X.dim() != 2:
+        raise ValueError("expotrs_batched: X must be 2-D (n x k, one column per right-hand side)")
+    u, batch, p, ldr, stride = _batched_triangles("expotrs_batched", "R", tuple(R.shape), R, uplo)
+    s = _potrs_sweep(sweep)
+    n, k = int(X.shape[0]), int(X.shape[1])
+    _potrs_blocks(n, p, batch)
+    # a block that does not conform is refused, not copied: it is solved in place
+    if n > 0 and k > 0 and ((k > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < k)):
+        raise ValueError("expotrs_batched: X must be row-major with stride(1) == 1 and stride(0) >= k (its rows must not "
+                         "overlap; it is solved in place)")
+    fpe = _fpe_0_to_8("expotrs_batched", fpe)
+    if R.device != X.device:
+        raise ValueError("expotrs_batched: R, X must be on one device")
+    if batch > 0 and n > 0 and k > 0:
+        r0, x0 = R.data_ptr(), X.data_ptr()
+        r1 = r0 + 8 * ((batch - 1) * stride + (p - 1) * ldr + p)
+        x1 = x0 + 8 * ((n - 1) * _ld(X, k) + k)
+        if r0 < x1 and x0 < r1:
+            raise ValueError("expotrs_batched: X overlaps R (X is solved in place while R is read)")
+    _on_gpu("expotrs_batched", R=R, X=X)
+    return (u, s, p, n, k, _ptr(R), ldr, stride, _ptr(X), _ld(X, max(k, 1)), fpe, int(bool(early_exit)))
+
+
+def set_potrf_batched_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one matrix per wave (no packing),
+    3 one matrix per workgroup item on a handful of workgroups.  Same bits on every path."""
+    _set_path("potrf_batched", mode)
+
+
+def last_potrf_batched_info():
+    """(entries rounded in registers, entries rounded from the accumulator, 0, 0) of the last batched ExPOTRF; their sum is
+    the number of entries that call fixed over the whole batch."""
+    return _last_info("potrf_batched")
+
+
+def set_potrs_batched_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one block per wave, 3 column tiles
+    of 4.  Same bits on every path."""
+    _set_path("potrs_batched", mode)
+
+
+def last_potrs_batched_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last batched ExPOTRS; their sum is
+    n * k per sweep."""
+    return _last_info("potrs_batched")
+
+
+def csr_diag_blocks_dev(A, p):
+    """The dense diagonal blocks of a square CSR operand (as for exspmv_dev: a torch.sparse_csr_tensor or a (crow, col, val,
+    shape) tuple of torch tensors) as a float64 tensor [ceil(n / p), p, p] on A's device: block b holds A[b p : (b + 1) p,
+    b p : (b + 1) p].  Entries outside the blocks are dropped, missing entries are zero, and the rows of the last block
+    beyond n carry an identity diagonal.  A must store each (row, column) at most once (a second copy would overwrite the
+    first instead of adding to it).  Plain torch indexing, no kernel of this library; works on CPU tensors too.  With it
+    a block-Jacobi preconditioner is
+        D = csr_diag_blocks_dev(A, p);  R, info = expotrf_batched_dev(D);  expotrs_batched_dev(R, X)."""
+    torch = _torch()
+    crow, col, val, n, _, _ = _csr_dev("csr_diag_blocks", A, square=True)
+    p = int(p)
+    if p < 1 or p > POTRF_BATCHED_MAX_P:
+        raise ValueError(f"csr_diag_blocks: p must lie in 1 .. {POTRF_BATCHED_MAX_P}, got {p}")
+    if len({crow.device, col.device, val.device}) != 1:
+        raise ValueError("csr_diag_blocks: crow, col, val must be on one device")
+    nb = -(-n // p)
+    D = torch.zeros((nb, p, p), dtype=torch.float64, device=val.device)
+    rows = torch.repeat_interleave(torch.arange(n, device=val.device, dtype=torch.int64), (crow[1:] - crow[:-1]).to(torch.int64))
+    cols = col.to(torch.int64)
+    keep = (rows // p == cols // p) & (cols >= 0) & (cols < n)
+    rows, cols = rows[keep], cols[keep]
+    D[rows // p, rows % p, cols % p] = val[keep]
+    pad = torch.arange(n, nb * p, device=val.device, dtype=torch.int64)
+    D[pad // p, pad % p, pad % p] = 1.0
+    return D
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
@@ -1083,6 +1253,34 @@ class Context:
         _check(load_library().exblas_expotrf_ctx(self.handle, *args, _stream_ptr(_torch())), "expotrf")
         return G, info
 
+    def expotrf_batched(self, G, uplo="U", info=None, fpe=8, early_exit=True):  # noqa: N803
+        """Batched ExPOTRF: the exact-sum Cholesky factors of the batch matrices of G ([batch, p, p] float64, p <= 64), in
+        place, in one stream-ordered launch that never synchronises: the factor step of a block-Jacobi preconditioner.
+        Every matrix is bit for bit what expotrf_dev gives on it alone, whatever the batch, its place in it and its
+        neighbours.  Each matrix has one unit stride among its last two dimensions -- column-major (stride(1) == 1) or
+        row-major (stride(2) == 1); `uplo` names the triangle of G[b, i, j] as Python indexes it, the other triangle is
+        neither read nor written -- and G.stride(0) is the batch stride (the matrices must not overlap); G is never
+        copied.  info: a contiguous int32 device tensor of batch words (allocated when None); info[b] receives 0, or
+        j + 1 when the radicand of pivot j of matrix b is not > 0 (that value is stored at its pivot, the rest of that
+        matrix stays as it was; the other matrices are not affected).  fpe: 0, 1 or 2..8.  Returns (G, info)."""
+        info, args = _potrf_batched_args(G, uplo, info, fpe, early_exit)
+        _check(load_library().exblas_expotrf_batched_ctx(self.handle, *args, _stream_ptr(_torch())), "expotrf_batched")
+        return G, info
+
+    def expotrs_batched(self, R, X, uplo="U", sweep="B", fpe=8, early_exit=True):  # noqa: N803
+        """Batched ExPOTRS: applies blockdiag(G_b)^-1 to the n x k row-major block X in place, G_b = F^T F with the factors
+        R ([ceil(n / p), p, p], as expotrf_batched_dev leaves them, same layout rules and `uplo`), exact, reproducible and
+        rounded once per output, in one stream-ordered launch: the apply step of a block-Jacobi preconditioner.  Block b
+        covers the rows b p .. min(n, (b + 1) p) - 1 of X; a shorter last block uses the leading part of its triangle.
+        sweep '1' solves F^T Y = B, '2' solves F Z = Y, 'B' (the default) both, bit for bit '1' then '2'.  Every column of
+        a block is bit for bit what extrsv_dev / extrsm_dev give on that block.  X: a 2-D float64 tensor with
+        stride(1) == 1 and stride(0) >= k (a view of a wider block is fine: its padding is not touched; anything else
+        is refused, not copied).  The info words of the factorisation are NOT consulted: a block whose factorisation
+        broke down is the caller's concern.  fpe: 0, 1 or 2..8.  Returns X."""
+        args = _potrs_batched_args(R, X, uplo, sweep, fpe, early_exit)
+        _check(load_library().exblas_expotrs_batched_ctx(self.handle, *args, _stream_ptr(_torch())), "expotrs_batched")
+        return X
+
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
         """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
         [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
@@ -1118,6 +1316,7 @@ exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbd
 exbgemm_dev = _default.exbgemm
 exbtrsm_dev = _default.exbtrsm
 expotrf_dev = _default.expotrf
+expotrf_batched_dev, expotrs_batched_dev = _default.expotrf_batched, _default.expotrs_batched
 
 
 def excholqr_dev(X, fpe=8, early_exit=True):  # noqa: N803
@@ -1428,6 +1627,48 @@ def expotrf(G, uplo="U", fpe=8, early_exit=True):  # noqa: N803
     _require_gpu()
     _check(load_library().exblas_expotrf(u, p, _hptr(R), ldg, C.byref(info), fpe, int(bool(early_exit))), "expotrf")
     return R, int(info.value)
+
+
+def _batched_host(who, name, a):
+    """the 3-D operand `name` of a host batched routine as an array whose matrices are C- or Fortran-ordered and packed
+    (anything else is copied to C order); always a copy"""
+    a = _dense_host(who, name, a, 3)
+    at = a.transpose(0, 2, 1)
+    if at.flags.c_contiguous and not a.flags.c_contiguous:   # every matrix Fortran-ordered: the copy keeps that
+        return np.array(at, dtype=np.float64, copy=True, order="C").transpose(0, 2, 1)
+    return np.array(a, dtype=np.float64, copy=True, order="C")
+
+
+def expotrf_batched(G, uplo="U", fpe=8, early_exit=True):  # noqa: N803
+    """Batched ExPOTRF on a host array: G float64 of shape (batch, p, p), every matrix C-ordered, or Fortran-ordered as
+    np.transpose of a C-ordered batch gives it (anything else is copied to C order; `uplo` names the triangle of
+    G[b, i, j]); returns (R, info): a new array with the factors in that triangle (the other triangle as it was in G; G is
+    not changed) and the batch info words as an int32 array."""
+    R = _batched_host("expotrf_batched", "G", G)
+    u, batch, p, ldg, stride = _batched_triangles("expotrf_batched", "G", R.shape, _HostStrides(R), uplo)
+    fpe = _fpe_0_to_8("expotrf_batched", fpe)
+    info = np.zeros(batch, dtype=np.int32)
+    _require_gpu()
+    _check(load_library().exblas_expotrf_batched(u, p, batch, _hptr(R), ldg, stride, _hptr(info), fpe,
+                                                 int(bool(early_exit))), "expotrf_batched")
+    return R, info
+
+
+def expotrs_batched(R, B, uplo="U", sweep="B", fpe=8, early_exit=True):  # noqa: N803
+    """Batched ExPOTRS on host arrays: R float64 of shape (ceil(n / p), p, p) as expotrf_batched returns it, B float64 of
+    shape (n, k); returns the solution (a new n x k float64 array; B is not changed)."""
+    R = _batched_host("expotrs_batched", "R", R)
+    u, batch, p, ldr, stride = _batched_triangles("expotrs_batched", "R", R.shape, _HostStrides(R), uplo)
+    s = _potrs_sweep(sweep)
+    B = _dense_host("expotrs_batched", "B", B, 2, " (n x k, one column per right-hand side)")
+    X = np.array(B, dtype=np.float64, copy=True, order="C")
+    n, k = int(X.shape[0]), int(X.shape[1])
+    _potrs_blocks(n, p, batch)
+    fpe = _fpe_0_to_8("expotrs_batched", fpe)
+    _require_gpu()
+    _check(load_library().exblas_expotrs_batched(u, s, p, n, k, _hptr(R), ldr, stride, _hptr(X), max(k, 1), fpe,
+                                                 int(bool(early_exit))), "expotrs_batched")
+    return X
 
 
 from .dist import (Comm, exsum_allreduce, exdot_allreduce, allreduce_finish, allreduce_record,  # noqa: E402,F401

@@ -323,6 +323,8 @@ void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
 void exblas_set_bgemm_path(int mode) { set_path(&CtxKnobs::bgemm_path, mode, 3); }
 void exblas_set_btrsm_path(int mode) { set_path(&CtxKnobs::btrsm_path, mode, 3); }
 void exblas_set_potrf_path(int mode) { set_path(&CtxKnobs::potrf_path, mode, 3); }
+void exblas_set_potrf_batched_path(int mode) { set_path(&CtxKnobs::potrf_batched_path, mode, 3); }
+void exblas_set_potrs_batched_path(int mode) { set_path(&CtxKnobs::potrs_batched_path, mode, 3); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -405,6 +407,12 @@ int exblas_last_btrsm_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::bt
 
 // the same for ExPOTRF: out[0] + out[1] is the number of entries the call fixed (the radicand of a breakdown included)
 int exblas_last_potrf_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::potrf_slots, out4); }
+
+// the same for the batched ExPOTRF: out[0] + out[1] is the number of entries fixed over the whole batch
+int exblas_last_potrf_batched_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::potrf_batched_slots, out4); }
+
+// the same for the batched ExPOTRS: out[0] + out[1] is n * k per sweep
+int exblas_last_potrs_batched_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::potrs_batched_slots, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -659,6 +667,59 @@ static int expotrf_on(Ctx &c, char uplo, int p, double *d_g, int ldg, int *d_inf
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)expotrf_dispatch(c, uplo, p, d_g, ldg, d_info, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of the batched ExPOTRF, on host or device pointers alike, before a device is touched.  *empty:
+// p == 0 or batch == 0, which is decided before the pointers are looked at.
+static int potrf_batched_check_args(char uplo, int p, int64_t batch, const double *g, int ldg, int64_t stride, const int *info,
+                                    int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(uplo, "LlUu") || p < 0 || batch < 0 || p > EXBLAS_POTRF_BATCHED_MAX_P || ldg < (p > 1 ? p : 1) || fpe < 0)
+        return (int)hipErrorInvalidValue;
+    if (batch > 1 && stride < (int64_t)ldg * p) return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = p == 0 || batch == 0;
+    if (!*empty && (!g || !info)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int expotrf_batched_on(Ctx &c, char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride, int *d_info,
+                              int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // an empty call goes on: it counts as the device's last one, and the dispatch launches nothing
+    if (int rc = potrf_batched_check_args(uplo, p, batch, d_g, ldg, stride, d_info, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)expotrf_batched_dispatch(c, uplo, p, batch, d_g, ldg, stride, d_info, fpe, early_exit, round_mode(), st);
+}
+
+// The argument checks of the batched ExPOTRS, on host or device pointers alike, before a device is touched.  *empty:
+// n == 0 or k == 0, which is decided before the pointers are looked at.
+static int potrs_batched_check_args(char uplo, char sweep, int p, int64_t n, int k, const double *r, int ldr, int64_t stride,
+                                    const double *x, int64_t ldx, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(uplo, "LlUu") || !one_of(sweep, "12Bb")) return (int)hipErrorInvalidValue;
+    if (n < 0 || k < 0 || p < 0 || p > EXBLAS_POTRF_BATCHED_MAX_P || (p < 1 && n > 0) || fpe < 0 || ldx < k)
+        return (int)hipErrorInvalidValue;
+    if (ldr < (p > 1 ? p : 1)) return (int)hipErrorInvalidValue;
+    if (p > 0 && n > p && stride < (int64_t)ldr * p) return (int)hipErrorInvalidValue;   // more than one block
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = n == 0 || k == 0;
+    if (!*empty && (!r || !x)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int expotrs_batched_on(Ctx &c, char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr,
+                              int64_t stride, double *d_x, int64_t ldx, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // an empty call goes on: it counts as the device's last one, and the dispatch launches nothing
+    if (int rc = potrs_batched_check_args(uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)expotrs_batched_dispatch(c, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, round_mode(),
+                                         st);
 }
 
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
@@ -934,6 +995,24 @@ int exblas_expotrf_ctx(exblas_ctx_t *h, char uplo, int p, double *d_g, int ldg, 
     return expotrf_on(*cp, uplo, p, d_g, ldg, d_info, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_expotrf_batched_ctx(exblas_ctx_t *h, char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride,
+                               int *d_info, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = potrf_batched_check_args(uplo, p, batch, d_g, ldg, stride, d_info, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return expotrf_batched_on(*cp, uplo, p, batch, d_g, ldg, stride, d_info, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_expotrs_batched_ctx(exblas_ctx_t *h, char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr,
+                               int64_t stride, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = potrs_batched_check_args(uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return expotrs_batched_on(*cp, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -1011,6 +1090,18 @@ int exblas_exbtrsm_dev(char uplo, char transt, char diag, int64_t n, int p, doub
 int exblas_expotrf_dev(char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit, void *stream)
 {
     return exblas_expotrf_ctx(nullptr, uplo, p, d_g, ldg, d_info, fpe, early_exit, stream);
+}
+
+int exblas_expotrf_batched_dev(char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride, int *d_info, int fpe,
+                               int early_exit, void *stream)
+{
+    return exblas_expotrf_batched_ctx(nullptr, uplo, p, batch, d_g, ldg, stride, d_info, fpe, early_exit, stream);
+}
+
+int exblas_expotrs_batched_dev(char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr, int64_t stride,
+                               double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    return exblas_expotrs_batched_ctx(nullptr, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, stream);
 }
 
 int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
@@ -1608,6 +1699,43 @@ int exblas_expotrf(char uplo, int p, double *g, int ldg, int *info, int fpe, int
     const int rc = expotrf_on(hc.c, uplo, p, d_g, ldg, d_info, fpe, early_exit, hc.c.stream);
     if (rc == 0 && info) EXB_CHECK(hipMemcpyAsync(info, d_info, sizeof(int), hipMemcpyDeviceToHost, hc.c.stream));
     return hc.out(rc, g, d_g, gbytes);
+}
+
+// the matrices travel as one span, from the first entry of the first to the p-th entry of the last column of the last
+// (padding, gaps and the other triangles included), and come back the same way; info (when given) receives the batch words
+int exblas_expotrf_batched(char uplo, int p, int64_t batch, double *g, int ldg, int64_t stride, int *info, int fpe,
+                           int early_exit)
+{
+    bool empty;
+    int dummy = 0;
+    const int bad = potrf_batched_check_args(uplo, p, batch, g, ldg, stride, &dummy, fpe, &empty);
+    if (bad || empty) return bad;   // (nothing to do: info is not written either)
+    HostCall hc("exblas_expotrf_batched");
+    const size_t gbytes = ((size_t)(batch - 1) * (size_t)stride + (size_t)ldg * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    const size_t ibytes = (size_t)batch * sizeof(int);
+    double *d_g = hc.in(0, gbytes, g, gbytes);
+    int *d_info = (int *)hc.in(1, ibytes, nullptr, 0);
+    const int rc = expotrf_batched_on(hc.c, uplo, p, batch, d_g, ldg, stride, d_info, fpe, early_exit, hc.c.stream);
+    if (rc == 0 && info) EXB_CHECK(hipMemcpyAsync(info, d_info, ibytes, hipMemcpyDeviceToHost, hc.c.stream));
+    return hc.out(rc, g, d_g, gbytes);
+}
+
+// the triangles travel as one span (as above), and whole rows of X (the last one only up to its k-th entry), which come
+// back the same way: the padding of X returns as it went
+int exblas_expotrs_batched(char uplo, char sweep, int p, int64_t n, int k, const double *r, int ldr, int64_t stride, double *x,
+                           int64_t ldx, int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = potrs_batched_check_args(uplo, sweep, p, n, k, r, ldr, stride, x, ldx, fpe, &empty);
+    if (bad || empty) return bad;
+    HostCall hc("exblas_expotrs_batched");
+    const size_t nblocks = (size_t)((n + p - 1) / p);
+    const size_t rbytes = ((nblocks - 1) * (size_t)stride + (size_t)ldr * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)k) * sizeof(double);
+    double *d_r = hc.in(0, rbytes, r, rbytes);
+    double *d_x = hc.in(1, xbytes, x, xbytes);
+    return hc.out(expotrs_batched_on(hc.c, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, hc.c.stream), x,
+                  d_x, xbytes);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

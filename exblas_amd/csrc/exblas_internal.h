@@ -41,6 +41,10 @@ struct CtxKnobs {
                              // block of one column, 3 4 rows per wave item and chunks of 4 rows and columns of T
     int potrf_path = 0;      // exblas_set_potrf_path: 0 automatic, 1 every output rounded from the accumulator, 2 a register
                              // block of one row, 3 column tiles of 4 and no staging in LDS
+    int potrf_batched_path = 0;   // exblas_set_potrf_batched_path: 0 automatic, 1 every output rounded from the accumulator,
+                                  // 2 one matrix per wave, 3 one matrix per workgroup item and a handful of workgroups
+    int potrs_batched_path = 0;   // exblas_set_potrs_batched_path: 0 automatic, 1 every output rounded from the accumulator,
+                                  // 2 one block per wave, 3 column tiles of 4
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -66,6 +70,7 @@ struct CtxWsPtrs {
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
     SlotInfo bgemm_slots, btrsm_slots, potrf_slots;   // of the last ExBGEMM, ExBTRSM and ExPOTRF (one workgroup) call
+    SlotInfo potrf_batched_slots, potrs_batched_slots;   // of the last batched ExPOTRF and batched ExPOTRS call
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -243,6 +248,15 @@ hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long
 // potrf.hip
 hipError_t expotrf_dispatch(Ctx &c, char uplo, int p, double *g, int ldg, int *info, int fpe, int early_exit, int round_mode,
                             hipStream_t st);
+
+// potrf_batched.hip
+hipError_t expotrf_batched_dispatch(Ctx &c, char uplo, int p, long long batch, double *g, int ldg, long long stride, int *info,
+                                    int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// potrs_batched.hip
+hipError_t expotrs_batched_dispatch(Ctx &c, char uplo, char sweep, int p, long long n, int k, const double *r, int ldr,
+                                    long long stride, double *x, long long ldx, int fpe, int early_exit, int round_mode,
+                                    hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
 struct I8Plan {

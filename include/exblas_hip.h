@@ -546,7 +546,7 @@ int exblas_last_btrsm_info(int64_t *out4);
  * ONE stream-ordered launch of ONE workgroup and nothing else: no memset, no mailbox, no ticket, no host synchronisation.
  * The only workspace is that of the two counters (16 bytes).  Capturable into a hipGraph after one call on the context (or
  * exblas_reserve_workspace).  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
- * Not provided: batched factorisations, pivoting, a shifted CholQR, LDL^T, fp32, more than one workgroup, p > 512. */
+ * Not provided: pivoting, a shifted CholQR, LDL^T, fp32, more than one workgroup, p > 512. */
 int exblas_expotrf_dev(char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit, void *stream);
 /* Test hook for ExPOTRF (same bits on every path): 0 automatic, 1 every output rounded from the integer accumulator,
  * 2 a register block of one row, 3 column tiles of 4 and no staging in LDS (the seams between tiles, slices and row
@@ -558,6 +558,78 @@ void exblas_set_potrf_path(int mode);
  * that launched nothing.  The workgroup stores them with plain stores: valid after each graph replay.  Synchronises the
  * device; valid until the next call that uses the workspace.  Returns 0 or a hipError_t. */
 int exblas_last_potrf_info(int64_t *out4);
+/* Batched ExPOTRF: the exact-sum Cholesky factorisation of `batch` independent small matrices (the diagonal blocks of a
+ * block-Jacobi preconditioner) in ONE launch, on device pointers.  Matrix b is the p x p COLUMN-MAJOR triangle at
+ * d_g + b * stride (ldg >= max(1, p); stride >= ldg * p when batch > 1; all offsets 64-bit) and is factored IN PLACE exactly
+ * as exblas_expotrf_dev(uplo, p, d_g + b * stride, ldg, d_info + b, ...) defines: the same row-by-row contract, one rounding
+ * per exact sum, then ONE correctly rounded square root or ONE IEEE division per entry, and LAPACK's breakdown rule PER
+ * MATRIX (the radicand that is not > 0 is stored at its pivot, the rest of that matrix stays as it was, d_info[b] = j + 1,
+ * else 0).  d_info[b] is written for every b by every call that launches, with plain stores.  Bit for bit, every matrix is
+ * what the single routine gives.
+ * The bits of a matrix depend on its data, uplo and the rounding mode only: not on batch, its position in the batch, its
+ * neighbours, ldg, stride, the path (exblas_set_potrf_batched_path), fpe (0 or 2..8), early_exit, the context or the
+ * stream.  Matrices are independent: a NaN matrix or a breakdown changes no bit of another one.  The other triangle, the
+ * ldg padding of a column and the gap between matrices (stride > ldg * p) are neither read nor written.
+ * fpe == 0 rounds every output from an integer accumulator; fpe == 1 is the plain fp64 factorisation (s = g_ji, then
+ * s -= r_kj r_ki for k ascending; deterministic, not exact; counters 0); fpe >= 9: EXBLAS_UNSUPPORTED, nothing is touched.
+ * REFUSED with hipErrorInvalidValue before the device is touched: p > EXBLAS_POTRF_BATCHED_MAX_P, a bad uplo, p < 0,
+ * batch < 0, ldg < max(1, p), batch > 1 with stride < ldg * p, fpe < 0, and a null d_g or d_info when anything would be
+ * launched.  p == 0 or batch == 0: success, nothing is launched, d_info is not written.
+ * ONE stream-ordered kernel launch and nothing else: no memset, no mailbox, no ticket, no host synchronisation.  One wave
+ * walks a matrix (no workgroup barrier in the pivot chain); for p <= 32 a wave carries 64 / pw matrices, pw = p rounded up
+ * to a power of two, its lanes being (matrix, column) pairs.  The only workspace is that of the counters (16 bytes per
+ * workgroup).  Capturable into a hipGraph after one call on the context (the first call raises the kernel's dynamic-LDS
+ * limit).  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: variable block sizes, p > 64, pivoting / LDL^T, a batched LU, fp32. */
+#define EXBLAS_POTRF_BATCHED_MAX_P 64
+int exblas_expotrf_batched_dev(char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride, int *d_info, int fpe,
+                               int early_exit, void *stream);
+/* Test hook for the batched ExPOTRF (same bits on every path): 0 automatic, 1 every output rounded from the integer
+ * accumulator, 2 no packing (one matrix per wave), 3 one matrix per workgroup item on a handful of workgroups (the seams
+ * between the items of a workgroup then occur at a small batch). */
+void exblas_set_potrf_batched_path(int mode);
+/* The most recent batched ExPOTRF on this device: out[0] entries rounded in registers, out[1] entries rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  For fpe != 1, out[0] + out[1] is the sum over the batch of the entries each
+ * matrix fixed (as exblas_last_potrf_info counts them); both 0 for fpe == 1; all 0 after a call that launched nothing.
+ * Synchronises the device; valid until the next call that uses the workspace.  Returns 0 or a hipError_t. */
+int exblas_last_potrf_batched_info(int64_t *out4);
+/* Batched ExPOTRS, the apply of a block-Jacobi preconditioner, on device pointers: d_x is an n x k ROW-MAJOR block
+ * (ldx >= k), solved IN PLACE.  Block b covers the rows b p .. min(n, (b + 1) p) - 1 (batch = ceil(n / p)); its factor is the
+ * p x p column-major triangle at d_r + b * stride exactly as the batched ExPOTRF leaves it (ldr >= max(1, p); stride >=
+ * ldr * p with more than one block).  A last block of pl = n - (batch - 1) p < p rows uses the leading pl x pl part of its
+ * triangle (the factor of a leading submatrix is the leading part of the factor); the rest of that triangle is not read.
+ * With G_b = F^T F, F = R for uplo 'U' and F = L^T for 'L':
+ *     sweep '1'  F^T Y = B  by substitution, rows ascending
+ *     sweep '2'  F Z = Y    rows descending
+ *     sweep 'B'  '1' then '2' in one launch (X read and written once, the triangle read once); bit for bit '1', then '2'.
+ * Every output follows ExTRSV's row step, x_ij = fl( Round( b_ij - sum_{c before i} op(F)(i, c) x_cj ) / F(i, i) ): the sum
+ * exact over the already fixed doubles and rounded ONCE in the current rounding mode, then ONE IEEE division (never a
+ * multiplication by a reciprocal).  Column j of block b is bit for bit what exblas_extrsv_dev writes for (uplo, diag 'N',
+ * the block's row count, the block's triangle, ldr) on the vector at X + b p ldx + j with incx = ldx, sweep '1' being trans
+ * 'T' for 'U' and 'N' for 'L', sweep '2' the other trans; so is what exblas_extrsm_dev gives on the block.  Every stored
+ * entry of the strict triangle counts: zero times Inf is NaN.
+ * Never touched: the other triangle, the padding of R (ldr, stride), the padding of a row of X, the unused trailing part of
+ * the last block's triangle.  Columns and blocks are independent.  The bits do not depend on k, ldx, the column tile, the
+ * number of blocks a wave carries, the grid, the path, fpe (0 or 2..8), early_exit, the context or the stream.
+ * The info word of the factorisation is NOT consulted: solving with a block whose factorisation broke down is the
+ * caller's concern (read the batched ExPOTRF's d_info first).
+ * fpe == 0 / 1 / >= 9 as for the batched ExPOTRF (fpe == 1: s = b_i, then s -= F x over the solved rows ascending).
+ * REFUSED with hipErrorInvalidValue before the device is touched: p > 64, p < 1 with n > 0, a bad uplo or sweep (1, 2, B or
+ * b), negative sizes, ldr < max(1, p), stride < ldr * p with more than one block, ldx < k, fpe < 0, null pointers when
+ * anything would be launched.  n == 0 or k == 0: success, nothing is launched.
+ * ONE launch, no mailbox; capturable after one call.  Lanes own (block, column) pairs: with the column tile kc = min(k, 64)
+ * rounded up to a power of two a wave carries 64 / kc consecutive blocks, fewer where its share of LDS does not hold their
+ * triangles and its panel of X.  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: variable block sizes, p > 64, fusing the apply into ExSpMM, a device-side check of the factor's info. */
+int exblas_expotrs_batched_dev(char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr, int64_t stride,
+                               double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
+/* Test hook for the batched ExPOTRS (same bits on every path): 0 automatic, 1 every output rounded from the integer
+ * accumulator, 2 one block per wave, 3 column tiles of 4 (the seams between tiles then occur at small k). */
+void exblas_set_potrs_batched_path(int mode);
+/* The most recent batched ExPOTRS on this device: out[0] outputs rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == n * k for one sweep and 2 n k for 'B' (both 0 for
+ * fpe == 1); all 0 after a call that launched nothing.  Synchronises the device.  Returns 0 or a hipError_t. */
+int exblas_last_potrs_batched_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -625,6 +697,10 @@ int exblas_exbtrsm_ctx(exblas_ctx_t *ctx, char uplo, char transt, char diag, int
                        const double *d_t, int ldt, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
 int exblas_expotrf_ctx(exblas_ctx_t *ctx, char uplo, int p, double *d_g, int ldg, int *d_info, int fpe, int early_exit,
                        void *stream);
+int exblas_expotrf_batched_ctx(exblas_ctx_t *ctx, char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride,
+                               int *d_info, int fpe, int early_exit, void *stream);
+int exblas_expotrs_batched_ctx(exblas_ctx_t *ctx, char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr,
+                               int64_t stride, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
 int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
 int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
@@ -802,6 +878,16 @@ int exblas_exbtrsm(char uplo, char transt, char diag, int64_t n, int p, double a
  * back as they went); *info (may be NULL) receives the info word: staged through the device, synchronous.  Returns 0,
  * hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
 int exblas_expotrf(char uplo, int p, double *g, int ldg, int *info, int fpe, int early_exit);
+/* exblas_expotrf_batched_dev on host arrays (g: the batch matrices, stride apart, factored in place; padding, gaps and the
+ * other triangles come back as they went); info (may be NULL) receives the batch info words: staged through the device,
+ * synchronous.  Returns 0, hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
+int exblas_expotrf_batched(char uplo, int p, int64_t batch, double *g, int ldg, int64_t stride, int *info, int fpe,
+                           int early_exit);
+/* exblas_expotrs_batched_dev on host arrays (r: the ceil(n / p) triangles, stride apart; x: the n x k row-major block with
+ * leading dimension ldx, B on entry, the solution on return; its padding comes back as it went): staged through the
+ * device, synchronous.  Returns 0, hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
+int exblas_expotrs_batched(char uplo, char sweep, int p, int64_t n, int k, const double *r, int ldr, int64_t stride, double *x,
+                           int64_t ldx, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
