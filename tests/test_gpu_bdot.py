@@ -289,6 +289,8 @@ def test_fpe1_error_bound(ex, oracle, mode, n, p, q):
 
 
 def test_graph_capture(ex, oracle):
+    """(Four replays on new data, several batches and ExGEMV's sums over the same bytes between replays:
+    tests/test_gpu_graph_replay_solves.py.)"""
     import torch
     n, p, q = 5000, 6, 5
     X, Y = _blocks(oracle, 1, n, p, q)

@@ -329,6 +329,8 @@ def test_degenerate_sizes_and_refusals(ex):
 
 
 def test_graph_capture_of_export_and_round(ex, oracle):
+    """(Four replays on new data at 65 x 65 outputs, with a dirty workspace between replays:
+    tests/test_gpu_graph_replay_solves.py.)"""
     import torch
     n, p, q = 5000, 6, 5
     X, Y = _blocks(oracle, 1, n, p, q)

@@ -14,7 +14,10 @@ no result equals; every other output is filled with -1.
 
 The census.  `test_node_census` captures every device routine once with the HIP runtime's own capture calls, counts
 the nodes of the graph by kind and holds them to CENSUS: no routine puts a memset node into a graph, and none may start
-to (on this stack graphs with memset nodes lost the clear, or faulted, on a replay)."""
+to (on this stack graphs with memset nodes lost the clear, or faulted, on a replay).
+
+The mailbox solves with several right-hand sides (ExTRSM, ExSpTRSV, ExSpTRSM) and ExBDOT have the same protocol in
+tests/test_gpu_graph_replay_solves.py."""
 import ctypes as C
 import functools
 from fractions import Fraction
@@ -493,13 +496,16 @@ CENSUS = {
     "exgemv_dev T": (2, 0),
     "extrsv_dev": (2, 0),
     "extrsm_dev": (2, 0),
+    "extrsm_dev, path 3, k = 9": (6, 0),           # three panels of 4, 4, 1 columns: a preset and a solve kernel each
     "exgemm_dev, digit-slice shape": (19, 0),      # 130 x 75 x 200; the scan, the decision, slices, passes, the finish
     "exgemm_dev, residue shape": (11, 0),          # 200 x 260 x 96
     "exspmv_dev": (7, 0),
     "exspmm_dev": (8, 0),
     "exsptrsv_dev": (2, 0),
     "exsptrsm_dev": (2, 0),
+    "exsptrsm_dev, path 3, k = 9": (6, 0),         # three panels
     "exbdot_dev": (3, 0),
+    "exbdot_dev G, 65 x 65": (12, 0),              # batches of 64 x 64, 64 x 1, 1 x 64 and 1 x 1 outputs, three kernels each
     "exbdot_export_dev": (3, 0),
     "exbdot_round_dev": (1, 0),
     "exbgemm_dev": (1, 0),
@@ -549,6 +555,17 @@ def _count_nodes(hip, stream, fn):
         assert hip.hipGraphDestroy(graph) == 0
 
 
+def _on_path_3(set_path, fn):
+    """fn() with the routine's path knob at 3 (panels and tiles of 4 columns), the knob restored"""
+    def call():
+        set_path(3)
+        try:
+            fn()
+        finally:
+            set_path(0)
+    return call
+
+
 def _census_calls(ex):
     """{row of CENSUS: a call with every output preallocated}, small shapes, plain data"""
     import torch
@@ -573,6 +590,8 @@ def _census_calls(ex):
     dl, b, B = _cuda(L), gen(n, 8), gen(n * 8, 9).reshape(n, 8)
     calls["extrsv_dev"] = lambda: ex.extrsv_dev("U", "T", "N", n, dl, n, b, 8, True)     # (row-major L: column-major U)
     calls["extrsm_dev"] = lambda: ex.extrsm_dev(dl, B, "L", "N")
+    B9 = gen(n * 9, 15).reshape(n, 9)
+    calls["extrsm_dev, path 3, k = 9"] = _on_path_3(ex.set_trsm_path, lambda: ex.extrsm_dev(dl, B9, "L", "N"))
     nz = np.nonzero(L)
     crow = np.concatenate([[0], np.cumsum(np.bincount(nz[0], minlength=n))]).astype(np.int64)
     S = (_cuda(crow), _cuda(nz[1].astype(np.int64)), _cuda(L[nz]), (n, n))
@@ -581,6 +600,7 @@ def _census_calls(ex):
     calls["exspmm_dev"] = lambda: ex.exspmm_dev(S, B, 1.0, 0.0, sY)
     calls["exsptrsv_dev"] = lambda: ex.exsptrsv_dev(S, b, "L", "N")
     calls["exsptrsm_dev"] = lambda: ex.exsptrsm_dev(S, B, "L", "N")
+    calls["exsptrsm_dev, path 3, k = 9"] = _on_path_3(ex.set_sptrsm_path, lambda: ex.exsptrsm_dev(S, B9, "L", "N"))
     # the two shapes of the smoke run: digit slices, and from 192 x 192 up the residue path
     for name, (m, k, q) in (("digit-slice", (130, 200, 75)), ("residue", (200, 96, 260))):
         ga, gb = _cuda(O.gen("fpuniform", m * k, 10, 10, 0)), _cuda(O.gen("fpuniform", k * q, 11, 10, 0))
@@ -591,6 +611,8 @@ def _census_calls(ex):
     G, sets = f64(8, 8), torch.empty((64, 72), dtype=torch.int64, device="cuda")
     info = torch.zeros(1, dtype=torch.int32, device="cuda")
     calls["exbdot_dev"] = lambda: ex.exbdot_dev(X, out=G)
+    X65, G65 = gen(1000 * 65, 16).reshape(1000, 65), f64(65, 65)
+    calls["exbdot_dev G, 65 x 65"] = lambda: ex.exbdot_dev(X65, out=G65)
     calls["exbdot_export_dev"] = lambda: ex.exbdot_export_dev(X, sets=sets)
     calls["exbdot_round_dev"] = lambda: ex.exbdot_round_dev(sets, "G", 8, 8, out=G)
     calls["exbgemm_dev"] = lambda: ex.exbgemm_dev(X, Cm, 1.0, 0.0, Yb)

@@ -443,6 +443,8 @@ def test_runs_contexts_streams_and_host_arrays_agree(ex):
 
 
 def test_graph_capture_after_one_warm_call(ex):
+    """(Four replays on a changing triangle, several panels and a dirty workspace between replays:
+    tests/test_gpu_graph_replay_solves.py.)"""
     import torch
     n, W, mbits, filler = X.TRSV_CASES[4]
     c, blk = _block(4, False, max(KS))

@@ -375,6 +375,8 @@ def test_host_entry_keeps_the_padding_of_x(ex):
 
 
 def test_graph_capture_after_one_warm_call(ex):
+    """(Four replays on a changing triangle, several panels and a dirty workspace between replays:
+    tests/test_gpu_graph_replay_solves.py.)"""
     import torch
     c, blk = _block(4, False, max(KS))
     n, k = c.n, 65
