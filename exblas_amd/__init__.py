@@ -61,6 +61,10 @@ C_ABI_SYMBOLS = [
     "exblas_last_potrf_batched_info",
     "exblas_expotrs_batched_dev", "exblas_expotrs_batched_ctx", "exblas_expotrs_batched", "exblas_set_potrs_batched_path",
     "exblas_last_potrs_batched_info",
+    "exblas_exgetrf_batched_dev", "exblas_exgetrf_batched_ctx", "exblas_exgetrf_batched", "exblas_set_getrf_batched_path",
+    "exblas_last_getrf_batched_info",
+    "exblas_exgetrs_batched_dev", "exblas_exgetrs_batched_ctx", "exblas_exgetrs_batched", "exblas_set_getrs_batched_path",
+    "exblas_last_getrs_batched_info",
 ]
 
 # host-transport callback types of include/exblas_hip.h
@@ -250,6 +254,18 @@ def load_library():
     L.exblas_set_potrs_batched_path.argtypes = [i32]
     L.exblas_set_potrs_batched_path.restype = None
     L.exblas_last_potrs_batched_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exgetrf_batched_dev.argtypes = [C.c_char, i32, i64, vp, i32, i64, vp, vp, i32, i32, vp]
+    L.exblas_exgetrf_batched_ctx.argtypes = [vp] + L.exblas_exgetrf_batched_dev.argtypes
+    L.exblas_exgetrf_batched.argtypes = [C.c_char, i32, i64, vp, i32, i64, vp, vp, i32, i32]
+    L.exblas_set_getrf_batched_path.argtypes = [i32]
+    L.exblas_set_getrf_batched_path.restype = None
+    L.exblas_last_getrf_batched_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exgetrs_batched_dev.argtypes = [C.c_char, i32, i64, i32, vp, i32, i64, vp, vp, i64, i32, i32, vp]
+    L.exblas_exgetrs_batched_ctx.argtypes = [vp] + L.exblas_exgetrs_batched_dev.argtypes
+    L.exblas_exgetrs_batched.argtypes = [C.c_char, i32, i64, i32, vp, i32, i64, vp, vp, i64, i32, i32]
+    L.exblas_set_getrs_batched_path.argtypes = [i32]
+    L.exblas_set_getrs_batched_path.restype = None
+    L.exblas_last_getrs_batched_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -1032,6 +1048,129 @@ def last_potrs_batched_info():
     return _last_info("potrs_batched")
 
 
+GETRF_BATCHED_MAX_P = 64  # EXBLAS_GETRF_BATCHED_MAX_P: a wider block is refused
+
+
+def _batched_matrices(who, name, shape, stride_of):
+    """The rules of the 3-D operand `name` ([batch, p, p]) of the batched LU routines, device or host: those of
+    _batched_triangles (one unit stride among the last two dimensions of every matrix, stride(0) the batch stride, no
+    overlap), but a general matrix has no other triangle to flip to: the unit stride picks the C routine's `order`, 'C'
+    for stride(1) == 1 and 'R' for stride(2) == 1.  Returns (order, batch, p, ld, stride) for the C call."""
+    if len(shape) != 3:
+        raise ValueError(f"{who}: {name} must be 3-D [batch, p, p]")
+    batch, p = int(shape[0]), int(shape[1])
+    if shape[2] != p:
+        raise ValueError(f"{who}: the matrices of {name} must be square, got shape {tuple(shape)}")
+    if p > GETRF_BATCHED_MAX_P:
+        raise ValueError(f"{who}: p = {p} exceeds EXBLAS_GETRF_BATCHED_MAX_P = {GETRF_BATCHED_MAX_P}")
+    last2 = _Last2(shape, stride_of)
+    if batch == 0:
+        last2._strides = (p, 1)                     # no matrix: any strides do
+    u, _, ld = _trsm_layout(last2, "U", "N", who)   # 'U' comes back flipped for a row-major matrix
+    ld = max(ld, 1)
+    stride = int(stride_of.stride(0))
+    if batch > 1 and stride < ld * p:
+        raise ValueError(f"{who}: the matrices of {name} overlap: stride(0) = {stride} < {ld * p}")
+    return (b"C" if u == "U" else b"R"), batch, p, ld, (stride if batch > 1 else ld * max(p, 1))
+
+
+def _getrf_batched_args(A, ipiv, info, fpe, early_exit):
+    """Validates a device batched ExGETRF call before anything is launched (no GPU needed for that); returns (ipiv, info,
+    the C arguments up to the stream).  A is never copied; ipiv and info are allocated when None."""
+    torch = _torch()
+    if not isinstance(A, torch.Tensor) or A.dtype != torch.float64:
+        raise ValueError("exgetrf_batched: A must be a float64 torch tensor")
+    order, batch, p, lda, stride = _batched_matrices("exgetrf_batched", "A", tuple(A.shape), A)
+    fpe = _fpe_0_to_8("exgetrf_batched", fpe)
+    if ipiv is not None:
+        _getrf_pivots("exgetrf_batched", ipiv, batch, p, A)
+    if info is not None:
+        if (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.dim() != 1 or info.numel() != batch
+                or (batch > 1 and info.stride(0) != 1)):
+            raise ValueError(f"exgetrf_batched: info must be a contiguous int32 torch tensor of batch = {batch} words")
+        if info.device != A.device:
+            raise ValueError("exgetrf_batched: A, info must be on one device")
+    _on_gpu("exgetrf_batched", A=A)
+    if ipiv is None:
+        ipiv = torch.zeros((batch, p), dtype=torch.int32, device=A.device)
+    if info is None:
+        info = torch.zeros(batch, dtype=torch.int32, device=A.device)
+    return ipiv, info, (order, p, batch, _ptr(A), lda, stride, _ptr(ipiv), _ptr(info), fpe, int(bool(early_exit)))
+
+
+def _getrf_pivots(who, ipiv, batch, p, like):
+    """ipiv of the batched LU routines: a contiguous int32 torch tensor [batch, p] on the device of `like`"""
+    torch = _torch()
+    if (not isinstance(ipiv, torch.Tensor) or ipiv.dtype != torch.int32 or tuple(ipiv.shape) != (batch, p)
+            or not ipiv.is_contiguous()):
+        raise ValueError(f"{who}: ipiv must be a contiguous int32 torch tensor of shape [batch, p] = [{batch}, {p}]")
+    if ipiv.device != like.device:
+        raise ValueError(f"{who}: ipiv must be on the device of the matrices")
+
+
+def _getrs_blocks(n, p, batch):
+    """n rows in blocks of p need ceil(n / p) factored blocks"""
+    if n > 0 and p < 1:
+        raise ValueError("exgetrs_batched: the blocks of LU are empty (p = 0) but X has rows")
+    want = -(-n // p) if p > 0 else 0
+    if batch != want:
+        raise ValueError(f"exgetrs_batched: LU holds {batch} blocks of p = {p}, X with n = {n} rows needs {want}")
+
+
+def _getrs_batched_args(LU, ipiv, X, fpe, early_exit):
+    """Validates a device batched ExGETRS call before anything is launched (no GPU needed for that); returns the C
+    arguments up to the stream.  No operand is copied."""
+    torch = _torch()
+    for name, t in (("LU", LU), ("X", X)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"exgetrs_batched: {name} must be a float64 torch tensor")
+    if X.dim() != 2:
+        raise ValueError("exgetrs_batched: X must be 2-D (n x k, one column per right-hand side)")
+    order, batch, p, ldlu, stride = _batched_matrices("exgetrs_batched", "LU", tuple(LU.shape), LU)
+    _getrf_pivots("exgetrs_batched", ipiv, batch, p, LU)
+    n, k = int(X.shape[0]), int(X.shape[1])
+    _getrs_blocks(n, p, batch)
+    # a block that does not conform is refused, not copied: it is solved in place
+    if n > 0 and k > 0 and ((k > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < k)):
+        raise ValueError("exgetrs_batched: X must be row-major with stride(1) == 1 and stride(0) >= k (its rows must not "
+                         "overlap; it is solved in place)")
+    fpe = _fpe_0_to_8("exgetrs_batched", fpe)
+    if LU.device != X.device:
+        raise ValueError("exgetrs_batched: LU, X must be on one device")
+    if batch > 0 and n > 0 and k > 0:
+        r0, x0 = LU.data_ptr(), X.data_ptr()
+        r1 = r0 + 8 * ((batch - 1) * stride + (p - 1) * ldlu + p)
+        x1 = x0 + 8 * ((n - 1) * _ld(X, k) + k)
+        if r0 < x1 and x0 < r1:
+            raise ValueError("exgetrs_batched: X overlaps LU (X is solved in place while LU is read)")
+    _on_gpu("exgetrs_batched", LU=LU, X=X)
+    return (order, p, n, k, _ptr(LU), ldlu, stride, _ptr(ipiv), _ptr(X), _ld(X, max(k, 1)), fpe, int(bool(early_exit)))
+
+
+def set_getrf_batched_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one matrix per wave (no packing),
+    3 one matrix per workgroup item on a handful of workgroups.  Same bits on every path."""
+    _set_path("getrf_batched", mode)
+
+
+def last_getrf_batched_info():
+    """(roundings done in registers, roundings done from the accumulator, 0, 0) of the last batched ExGETRF; their sum is
+    p^2 per complete matrix, sum_{s<j} (2 (p - s) - 1) + (p - j) for a matrix that broke down at step j."""
+    return _last_info("getrf_batched")
+
+
+def set_getrs_batched_path(mode):
+    """Test hook: 0 automatic, 1 every output rounded from the integer accumulator, 2 one block per wave, 3 column tiles
+    of 4.  Same bits on every path."""
+    _set_path("getrs_batched", mode)
+
+
+def last_getrs_batched_info():
+    """(outputs rounded in registers, outputs rounded from the accumulator, 0, 0) of the last batched ExGETRS; their sum is
+    2 n k."""
+    return _last_info("getrs_batched")
+
+
 def csr_diag_blocks_dev(A, p):
     """The dense diagonal blocks of a square CSR operand (as for exspmv_dev: a torch.sparse_csr_tensor or a (crow, col, val,
     shape) tuple of torch tensors) as a float64 tensor [ceil(n / p), p, p] on A's device: block b holds A[b p : (b + 1) p,
@@ -1281,6 +1420,37 @@ class Context:
         _check(load_library().exblas_expotrs_batched_ctx(self.handle, *args, _stream_ptr(_torch())), "expotrs_batched")
         return X
 
+    def exgetrf_batched(self, A, ipiv=None, info=None, fpe=8, early_exit=True):  # noqa: N803
+        """Batched ExGETRF: the exact-sum LU factorisation with partial pivoting of the batch general matrices of A
+        ([batch, p, p] float64, p <= 64), in place, in one stream-ordered launch that never synchronises: the factor step of
+        a block-Jacobi preconditioner whose blocks are not symmetric positive definite.  Storage follows LAPACK: the
+        unit-lower L strictly below the diagonal of A[b], U on and above it, ipiv[b, j] the 1-based row exchanged with row j
+        at step j.  Every entry is one exact sum rounded once (the entries of L then take ONE IEEE division); the pivot
+        is the first row with the largest candidate.  The bits of a matrix depend on its data and the rounding mode only.
+        Each matrix has one unit stride among its last two dimensions, column-major (stride(1) == 1) or row-major
+        (stride(2) == 1), and A.stride(0) is the batch stride (the matrices must not overlap); A is never copied, its
+        padding and gaps are not touched.  ipiv: a contiguous int32 device tensor [batch, p]; info: a contiguous int32
+        device tensor of batch words (each allocated when None).  info[b] receives 0, or j + 1 when the pivot of step j of
+        matrix b is zero or NaN: the candidates of that step are stored, ipiv[b, i] = i + 1 from there on, the rest of
+        that matrix stays as it was, and no other matrix is affected.  fpe: 0, 1 or 2..8.  Returns (A, ipiv, info)."""
+        ipiv, info, args = _getrf_batched_args(A, ipiv, info, fpe, early_exit)
+        _check(load_library().exblas_exgetrf_batched_ctx(self.handle, *args, _stream_ptr(_torch())), "exgetrf_batched")
+        return A, ipiv, info
+
+    def exgetrs_batched(self, LU, ipiv, X, fpe=8, early_exit=True):  # noqa: N803
+        """Batched ExGETRS: applies blockdiag(A_b)^-1 to the n x k row-major block X in place, with the factors LU
+        ([ceil(n / p), p, p]) and pivots ipiv as exgetrf_batched_dev leaves them (same layout rules), exact, reproducible
+        and rounded once per output, in one stream-ordered launch: the apply step of a block-Jacobi preconditioner.  Block
+        b covers the rows b p .. min(n, (b + 1) p) - 1 of X; a shorter last block uses the leading part of its factors
+        and its first pivots.  The rows are interchanged as ipiv says (an index outside the block is skipped), then the
+        unit-lower sweep runs forward and the upper sweep backward: every column of a block is bit for bit what
+        extrsv_dev gives twice on the permuted column.  X: a 2-D float64 tensor with stride(1) == 1 and stride(0) >= k
+        (anything else is refused, not copied).  The info words of the factorisation are NOT consulted.  fpe: 0, 1 or
+        2..8.  Returns X."""
+        args = _getrs_batched_args(LU, ipiv, X, fpe, early_exit)
+        _check(load_library().exblas_exgetrs_batched_ctx(self.handle, *args, _stream_ptr(_torch())), "exgetrs_batched")
+        return X
+
     def exbdot_export(self, X, Y=None, mode="G", sets=None, fpe=8, early_exit=True):
         """First half of a row-sharded ExBDOT: X and Y (as for exbdot_dev) are the rows of one shard.  Returns an int64 tensor
         [outputs, 72] (`sets`, or a new one) -- output i * q + j in mode 'G', output j in mode 'D': the exact sum of the
@@ -1317,6 +1487,7 @@ exbgemm_dev = _default.exbgemm
 exbtrsm_dev = _default.exbtrsm
 expotrf_dev = _default.expotrf
 expotrf_batched_dev, expotrs_batched_dev = _default.expotrf_batched, _default.expotrs_batched
+exgetrf_batched_dev, exgetrs_batched_dev = _default.exgetrf_batched, _default.exgetrs_batched
 
 
 def excholqr_dev(X, fpe=8, early_exit=True):  # noqa: N803
@@ -1668,6 +1839,43 @@ def expotrs_batched(R, B, uplo="U", sweep="B", fpe=8, early_exit=True):  # noqa:
     _require_gpu()
     _check(load_library().exblas_expotrs_batched(u, s, p, n, k, _hptr(R), ldr, stride, _hptr(X), max(k, 1), fpe,
                                                  int(bool(early_exit))), "expotrs_batched")
+    return X
+
+
+def exgetrf_batched(A, fpe=8, early_exit=True):  # noqa: N803
+    """Batched ExGETRF on a host array: A float64 of shape (batch, p, p), every matrix C-ordered, or Fortran-ordered as
+    np.transpose of a C-ordered batch gives it (anything else is copied to C order); returns (LU, ipiv, info): a new array
+    with L and U in LAPACK's storage (A is not changed), the 1-based pivots as an int32 array (batch, p) and the batch
+    info words as an int32 array."""
+    LU = _batched_host("exgetrf_batched", "A", A)
+    order, batch, p, lda, stride = _batched_matrices("exgetrf_batched", "A", LU.shape, _HostStrides(LU))
+    fpe = _fpe_0_to_8("exgetrf_batched", fpe)
+    ipiv = np.zeros((batch, p), dtype=np.int32)
+    info = np.zeros(batch, dtype=np.int32)
+    _require_gpu()
+    _check(load_library().exblas_exgetrf_batched(order, p, batch, _hptr(LU), lda, stride, _hptr(ipiv), _hptr(info), fpe,
+                                                 int(bool(early_exit))), "exgetrf_batched")
+    return LU, ipiv, info
+
+
+def exgetrs_batched(LU, ipiv, B, fpe=8, early_exit=True):  # noqa: N803
+    """Batched ExGETRS on host arrays: LU float64 of shape (ceil(n / p), p, p) and ipiv int32 of shape (ceil(n / p), p) as
+    exgetrf_batched returns them, B float64 of shape (n, k); returns the solution (a new n x k float64 array; B is not
+    changed)."""
+    LU = _batched_host("exgetrs_batched", "LU", LU)
+    order, batch, p, ldlu, stride = _batched_matrices("exgetrs_batched", "LU", LU.shape, _HostStrides(LU))
+    ipiv = np.asarray(ipiv)
+    if ipiv.dtype != np.int32 or ipiv.shape != (batch, p):
+        raise ValueError(f"exgetrs_batched: ipiv must be an int32 array of shape (batch, p) = ({batch}, {p})")
+    ipiv = np.ascontiguousarray(ipiv)
+    B = _dense_host("exgetrs_batched", "B", B, 2, " (n x k, one column per right-hand side)")
+    X = np.array(B, dtype=np.float64, copy=True, order="C")
+    n, k = int(X.shape[0]), int(X.shape[1])
+    _getrs_blocks(n, p, batch)
+    fpe = _fpe_0_to_8("exgetrs_batched", fpe)
+    _require_gpu()
+    _check(load_library().exblas_exgetrs_batched(order, p, n, k, _hptr(LU), ldlu, stride, _hptr(ipiv), _hptr(X), max(k, 1),
+                                                 fpe, int(bool(early_exit))), "exgetrs_batched")
     return X
 
 

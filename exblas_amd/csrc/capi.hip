@@ -325,6 +325,8 @@ void exblas_set_btrsm_path(int mode) { set_path(&CtxKnobs::btrsm_path, mode, 3);
 void exblas_set_potrf_path(int mode) { set_path(&CtxKnobs::potrf_path, mode, 3); }
 void exblas_set_potrf_batched_path(int mode) { set_path(&CtxKnobs::potrf_batched_path, mode, 3); }
 void exblas_set_potrs_batched_path(int mode) { set_path(&CtxKnobs::potrs_batched_path, mode, 3); }
+void exblas_set_getrf_batched_path(int mode) { set_path(&CtxKnobs::getrf_batched_path, mode, 3); }
+void exblas_set_getrs_batched_path(int mode) { set_path(&CtxKnobs::getrs_batched_path, mode, 3); }
 
 // the 8-word workspace header of a context's last sparse call (zeros when it launched nothing, or on failure); synchronises
 static int sparse_header(const long long *info_dev, long long (&h)[8])
@@ -413,6 +415,12 @@ int exblas_last_potrf_batched_info(int64_t *out4) { return last_slot_info(&CtxWs
 
 // the same for the batched ExPOTRS: out[0] + out[1] is n * k per sweep
 int exblas_last_potrs_batched_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::potrs_batched_slots, out4); }
+
+// the same for the batched ExGETRF: out[0] + out[1] is the number of roundings over the whole batch (p^2 per complete matrix)
+int exblas_last_getrf_batched_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::getrf_batched_slots, out4); }
+
+// the same for the batched ExGETRS: out[0] + out[1] is 2 n k
+int exblas_last_getrs_batched_info(int64_t *out4) { return last_slot_info(&CtxWsPtrs::getrs_batched_slots, out4); }
 
 // ---- implementations on an explicit context (layer 0 for the *_dev entry points, a private one for host calls) ----
 static int exsum_accumulate_on(Ctx &c, const double *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
@@ -722,6 +730,60 @@ static int expotrs_batched_on(Ctx &c, char uplo, char sweep, int p, int64_t n, i
                                          st);
 }
 
+// The argument checks of the batched ExGETRF, on host or device pointers alike, before a device is touched.  *empty:
+// p == 0 or batch == 0, which is decided before the pointers are looked at.
+static int getrf_batched_check_args(char order, int p, int64_t batch, const double *a, int lda, int64_t stride, const int *ipiv,
+                                    const int *info, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(order, "CcRr") || p < 0 || batch < 0 || p > EXBLAS_GETRF_BATCHED_MAX_P || lda < (p > 1 ? p : 1) || fpe < 0)
+        return (int)hipErrorInvalidValue;
+    if (batch > 1 && stride < (int64_t)lda * p) return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = p == 0 || batch == 0;
+    if (!*empty && (!a || !ipiv || !info)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int exgetrf_batched_on(Ctx &c, char order, int p, int64_t batch, double *d_a, int lda, int64_t stride, int *d_ipiv,
+                              int *d_info, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // an empty call goes on: it counts as the device's last one, and the dispatch launches nothing
+    if (int rc = getrf_batched_check_args(order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exgetrf_batched_dispatch(c, order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, early_exit, round_mode(),
+                                         st);
+}
+
+// The argument checks of the batched ExGETRS, on host or device pointers alike, before a device is touched.  *empty:
+// n == 0 or k == 0, which is decided before the pointers are looked at.
+static int getrs_batched_check_args(char order, int p, int64_t n, int k, const double *lu, int ldlu, int64_t stride,
+                                    const int *ipiv, const double *x, int64_t ldx, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(order, "CcRr")) return (int)hipErrorInvalidValue;
+    if (n < 0 || k < 0 || p < 0 || p > EXBLAS_GETRF_BATCHED_MAX_P || (p < 1 && n > 0) || fpe < 0 || ldx < k)
+        return (int)hipErrorInvalidValue;
+    if (ldlu < (p > 1 ? p : 1)) return (int)hipErrorInvalidValue;
+    if (p > 0 && n > p && stride < (int64_t)ldlu * p) return (int)hipErrorInvalidValue;   // more than one block
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = n == 0 || k == 0;
+    if (!*empty && (!lu || !ipiv || !x)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+static int exgetrs_batched_on(Ctx &c, char order, int p, int64_t n, int k, const double *d_lu, int ldlu, int64_t stride,
+                              const int *d_ipiv, double *d_x, int64_t ldx, int fpe, int early_exit, hipStream_t st)
+{
+    bool empty;   // an empty call goes on: it counts as the device's last one, and the dispatch launches nothing
+    if (int rc = getrs_batched_check_args(order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, &empty)) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exgetrs_batched_dispatch(c, order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, early_exit,
+                                         round_mode(), st);
+}
+
 static int exgemm_on(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
                      const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                      hipStream_t st, const GemmChunks *chunks = nullptr)
@@ -1013,6 +1075,26 @@ int exblas_expotrs_batched_ctx(exblas_ctx_t *h, char uplo, char sweep, int p, in
     return expotrs_batched_on(*cp, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_exgetrf_batched_ctx(exblas_ctx_t *h, char order, int p, int64_t batch, double *d_a, int lda, int64_t stride,
+                               int *d_ipiv, int *d_info, int fpe, int early_exit, void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = getrf_batched_check_args(order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return exgetrf_batched_on(*cp, order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_exgetrs_batched_ctx(exblas_ctx_t *h, char order, int p, int64_t n, int k, const double *d_lu, int ldlu,
+                               int64_t stride, const int *d_ipiv, double *d_x, int64_t ldx, int fpe, int early_exit,
+                               void *stream)
+{
+    bool empty;   // a bad argument is refused before the context, and with it the device, is looked up
+    if (int rc = getrs_batched_check_args(order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, &empty)) return rc;
+    EXB_HANDLE(h);
+    return exgetrs_batched_on(*cp, order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, early_exit,
+                              (hipStream_t)stream);
+}
+
 int exblas_exgemm_ctx(exblas_ctx_t *h, char transa, char transb, int m, int n, int k, double alpha, const double *d_a,
                       int lda, const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                       void *stream)
@@ -1102,6 +1184,18 @@ int exblas_expotrs_batched_dev(char uplo, char sweep, int p, int64_t n, int k, c
                                double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
 {
     return exblas_expotrs_batched_ctx(nullptr, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, stream);
+}
+
+int exblas_exgetrf_batched_dev(char order, int p, int64_t batch, double *d_a, int lda, int64_t stride, int *d_ipiv, int *d_info,
+                               int fpe, int early_exit, void *stream)
+{
+    return exblas_exgetrf_batched_ctx(nullptr, order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, early_exit, stream);
+}
+
+int exblas_exgetrs_batched_dev(char order, int p, int64_t n, int k, const double *d_lu, int ldlu, int64_t stride,
+                               const int *d_ipiv, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream)
+{
+    return exblas_exgetrs_batched_ctx(nullptr, order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, early_exit, stream);
 }
 
 int exblas_exbgemm_dev(int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx, const double *d_c,
@@ -1736,6 +1830,47 @@ int exblas_expotrs_batched(char uplo, char sweep, int p, int64_t n, int k, const
     double *d_x = hc.in(1, xbytes, x, xbytes);
     return hc.out(expotrs_batched_on(hc.c, uplo, sweep, p, n, k, d_r, ldr, stride, d_x, ldx, fpe, early_exit, hc.c.stream), x,
                   d_x, xbytes);
+}
+
+// the matrices travel as one span, from the first entry of the first to the last entry of the last (padding and gaps
+// included), and come back the same way; ipiv and info (when given) receive the batch * p pivots and the batch words
+int exblas_exgetrf_batched(char order, int p, int64_t batch, double *a, int lda, int64_t stride, int *ipiv, int *info, int fpe,
+                           int early_exit)
+{
+    bool empty;
+    int dummy = 0;
+    const int bad = getrf_batched_check_args(order, p, batch, a, lda, stride, &dummy, &dummy, fpe, &empty);
+    if (bad || empty) return bad;   // (nothing to do: ipiv and info are not written either)
+    HostCall hc("exblas_exgetrf_batched");
+    const size_t abytes = ((size_t)(batch - 1) * (size_t)stride + (size_t)lda * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    const size_t ibytes = (size_t)batch * sizeof(int), pbytes = ibytes * (size_t)p;
+    double *d_a = hc.in(0, abytes, a, abytes);
+    int *d_info = (int *)hc.in(1, ibytes, nullptr, 0);
+    int *d_ipiv = (int *)hc.in(2, pbytes, nullptr, 0);
+    const int rc = exgetrf_batched_on(hc.c, order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, early_exit, hc.c.stream);
+    if (rc == 0 && info) EXB_CHECK(hipMemcpyAsync(info, d_info, ibytes, hipMemcpyDeviceToHost, hc.c.stream));
+    if (rc == 0 && ipiv) EXB_CHECK(hipMemcpyAsync(ipiv, d_ipiv, pbytes, hipMemcpyDeviceToHost, hc.c.stream));
+    return hc.out(rc, a, d_a, abytes);
+}
+
+// the factors travel as one span (as above) with their pivots, and whole rows of X (the last one only up to its k-th
+// entry), which come back the same way: the padding of X returns as it went
+int exblas_exgetrs_batched(char order, int p, int64_t n, int k, const double *lu, int ldlu, int64_t stride, const int *ipiv,
+                           double *x, int64_t ldx, int fpe, int early_exit)
+{
+    bool empty;
+    const int bad = getrs_batched_check_args(order, p, n, k, lu, ldlu, stride, ipiv, x, ldx, fpe, &empty);
+    if (bad || empty) return bad;
+    HostCall hc("exblas_exgetrs_batched");
+    const size_t nblocks = (size_t)((n + p - 1) / p);
+    const size_t lbytes = ((nblocks - 1) * (size_t)stride + (size_t)ldlu * (size_t)(p - 1) + (size_t)p) * sizeof(double);
+    const size_t pbytes = nblocks * (size_t)p * sizeof(int);
+    const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)k) * sizeof(double);
+    double *d_lu = hc.in(0, lbytes, lu, lbytes);
+    double *d_x = hc.in(1, xbytes, x, xbytes);
+    const int *d_ipiv = (const int *)hc.in(2, pbytes, ipiv, pbytes);
+    return hc.out(exgetrs_batched_on(hc.c, order, p, n, k, d_lu, ldlu, stride, d_ipiv, d_x, ldx, fpe, early_exit, hc.c.stream),
+                  x, d_x, xbytes);
 }
 
 int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,

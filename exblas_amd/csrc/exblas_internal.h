@@ -45,6 +45,10 @@ struct CtxKnobs {
                                   // 2 one matrix per wave, 3 one matrix per workgroup item and a handful of workgroups
     int potrs_batched_path = 0;   // exblas_set_potrs_batched_path: 0 automatic, 1 every output rounded from the accumulator,
                                   // 2 one block per wave, 3 column tiles of 4
+    int getrf_batched_path = 0;   // exblas_set_getrf_batched_path: 0 automatic, 1 every output rounded from the accumulator,
+                                  // 2 one matrix per wave, 3 one matrix per workgroup item and a handful of workgroups
+    int getrs_batched_path = 0;   // exblas_set_getrs_batched_path: 0 automatic, 1 every output rounded from the accumulator,
+                                  // 2 one block per wave, 3 column tiles of 4
     int bdot_path = 0;       // exblas_set_bdot_path: 0 automatic, 1 the smallest row slab, 2 column panels and output tiles
                              // of width 4
 };
@@ -71,6 +75,7 @@ struct CtxWsPtrs {
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
     SlotInfo bgemm_slots, btrsm_slots, potrf_slots;   // of the last ExBGEMM, ExBTRSM and ExPOTRF (one workgroup) call
     SlotInfo potrf_batched_slots, potrs_batched_slots;   // of the last batched ExPOTRF and batched ExPOTRS call
+    SlotInfo getrf_batched_slots, getrs_batched_slots;   // of the last batched ExGETRF and batched ExGETRS call
 };
 
 // Lazily created, one per device.  Replaces the file-static kernel/buffer globals of the reference
@@ -256,6 +261,15 @@ hipError_t expotrf_batched_dispatch(Ctx &c, char uplo, int p, long long batch, d
 // potrs_batched.hip
 hipError_t expotrs_batched_dispatch(Ctx &c, char uplo, char sweep, int p, long long n, int k, const double *r, int ldr,
                                     long long stride, double *x, long long ldx, int fpe, int early_exit, int round_mode,
+                                    hipStream_t st);
+
+// getrf_batched.hip
+hipError_t exgetrf_batched_dispatch(Ctx &c, char order, int p, long long batch, double *a, int lda, long long stride, int *ipiv,
+                                    int *info, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// getrs_batched.hip
+hipError_t exgetrs_batched_dispatch(Ctx &c, char order, int p, long long n, int k, const double *lu, int ldlu, long long stride,
+                                    const int *ipiv, double *x, long long ldx, int fpe, int early_exit, int round_mode,
                                     hipStream_t st);
 
 // blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)

@@ -580,7 +580,8 @@ int exblas_last_potrf_info(int64_t *out4);
  * to a power of two, its lanes being (matrix, column) pairs.  The only workspace is that of the counters (16 bytes per
  * workgroup).  Capturable into a hipGraph after one call on the context (the first call raises the kernel's dynamic-LDS
  * limit).  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
- * Not provided: variable block sizes, p > 64, pivoting / LDL^T, a batched LU, fp32. */
+ * Not provided: variable block sizes, p > 64, LDL^T, fp32.  General (nonsymmetric or indefinite) blocks: the batched
+ * ExGETRF below, an LU with partial pivoting. */
 #define EXBLAS_POTRF_BATCHED_MAX_P 64
 int exblas_expotrf_batched_dev(char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride, int *d_info, int fpe,
                                int early_exit, void *stream);
@@ -630,6 +631,74 @@ void exblas_set_potrs_batched_path(int mode);
  * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == n * k for one sweep and 2 n k for 'B' (both 0 for
  * fpe == 1); all 0 after a call that launched nothing.  Synchronises the device.  Returns 0 or a hipError_t. */
 int exblas_last_potrs_batched_info(int64_t *out4);
+/* Batched ExGETRF: the exact-sum LU factorisation with partial pivoting of `batch` independent small GENERAL matrices (the
+ * diagonal blocks of a block-Jacobi preconditioner of a nonsymmetric or indefinite operator) in ONE launch, on device
+ * pointers, IN PLACE.  order 'C': element (i, j) of matrix b is at d_a[b * stride + i + j * lda]; order 'R': at
+ * d_a[b * stride + i * lda + j] (lda >= max(1, p); stride >= lda * p when batch > 1; all offsets 64-bit).  The LU of A^T is
+ * not the LU of A: `order` says which of the two is meant.  Storage follows LAPACK: the unit-lower L strictly below the
+ * diagonal, U on and above it, d_ipiv[b * p + j] the 1-based row that step j exchanged with row j (int32, batch * p words,
+ * contiguous), d_info[b] = 0 or the breakdown step + 1.
+ * The definition is the compact (Doolittle) LU, every entry ONE exact sum over already fixed doubles, rounded once in the
+ * current rounding mode.  Step j = 0 .. p - 1 on the working matrix W (A on entry, rows swapped as the steps go):
+ *   1. candidates  c_i = Round( w_ij - sum_{k<j} l_ik u_kj )  for every i >= j
+ *   2. pivot       piv = the smallest i >= j at which |c_i| is largest (a NaN ranks above +Inf); d_ipiv[j] = piv + 1
+ *   3. breakdown   c_piv is 0 (either sign) or NaN: the candidates are stored in column j, rows j .. p - 1, with no swap at
+ *                  this step, d_ipiv[i] = i + 1 for i >= j, d_info[b] = j + 1, the rest of the matrix stays as it is (the
+ *                  original entries in the row order reached so far).  An infinite pivot is no breakdown: IEEE goes on.
+ *   4. column of L rows j and piv of W are swapped whole; u_jj = c_piv; l_ij = fl( c_i / u_jj ), ONE IEEE division, i > j
+ *   5. row of U    u_ji = Round( w_ji - sum_{k<j} l_jk u_ki )  for i > j
+ * Every stored entry counts (0 * Inf is NaN).  d_ipiv and d_info are written for every matrix by every call that launches,
+ * with plain stores.  The bits of a matrix depend on its data and the rounding mode only: not on batch, its position, its
+ * neighbours, order, lda, stride, the path (exblas_set_getrf_batched_path), fpe (0 or 2..8), early_exit, the context or the
+ * stream.  A NaN matrix or a breakdown changes no bit of another matrix.  The lda padding and the gap between matrices are
+ * neither read nor written.
+ * fpe == 0 rounds every output from an integer accumulator; fpe == 1 is the plain fp64 factorisation of the same structure
+ * (s = w, then s -= l * u for k ascending; deterministic, not exact; counters 0); fpe >= 9: EXBLAS_UNSUPPORTED.
+ * REFUSED with hipErrorInvalidValue before the device is touched: p > EXBLAS_GETRF_BATCHED_MAX_P, an order other than C, c,
+ * R, r, p < 0, batch < 0, lda < max(1, p), batch > 1 with stride < lda * p, fpe < 0, and a null d_a, d_ipiv or d_info when
+ * anything would be launched.  p == 0 or batch == 0: success, nothing is launched, nothing is written.
+ * ONE stream-ordered kernel launch and nothing else: no memset, no mailbox, no spin-wait, no host synchronisation.  One wave
+ * walks a matrix; for p <= 32 a wave carries 64 / pw matrices, pw = p rounded up to a power of two.  The only workspace is
+ * that of the counters (16 bytes per workgroup).  Capturable into a hipGraph after one call on the context.  Returns 0,
+ * EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: A^T solves, p > 64, variable block sizes, complete or rook pivoting, LAPACK's continue-after-zero-pivot
+ * rule, a non-batched entry (batch = 1 serves), fp32. */
+#define EXBLAS_GETRF_BATCHED_MAX_P 64
+int exblas_exgetrf_batched_dev(char order, int p, int64_t batch, double *d_a, int lda, int64_t stride, int *d_ipiv, int *d_info,
+                               int fpe, int early_exit, void *stream);
+/* Test hook for the batched ExGETRF (same bits on every path): 0 automatic, 1 every output rounded from the integer
+ * accumulator, 2 no packing (one matrix per wave), 3 one matrix per workgroup item on a handful of workgroups. */
+void exblas_set_getrf_batched_path(int mode);
+/* The most recent batched ExGETRF on this device: out[0] roundings done in registers, out[1] roundings done from the
+ * integer accumulator, out[2] = out[3] = 0.  For fpe != 1, out[0] + out[1] is the number of roundings: p^2 for a complete
+ * matrix, sum_{s<j} (2 (p - s) - 1) + (p - j) for a breakdown at step j; both 0 for fpe == 1; all 0 after a call that
+ * launched nothing.  Synchronises the device; valid until the next call that uses the workspace. */
+int exblas_last_getrf_batched_info(int64_t *out4);
+/* Batched ExGETRS, the apply of a block-Jacobi preconditioner with general blocks, on device pointers: d_x is an n x k
+ * ROW-MAJOR block (ldx >= k), solved IN PLACE, X_b := A_b^-1 X_b for every block b of p rows (batch = ceil(n / p)).  d_lu,
+ * ldlu, stride, order and d_ipiv are what the batched ExGETRF left.  A last block of rows = n - (batch - 1) p < p rows uses
+ * the leading rows x rows part of its factors and its first `rows` pivots.
+ *   1. interchanges  for j = 0 .. rows - 1 in order, rows j and d_ipiv[b * p + j] - 1 of the block are swapped.  An index
+ *                    outside 1 .. rows is skipped and never dereferenced: garbage pivots read and write nothing out of bounds.
+ *   2. forward       y_i = Round( b_i - sum_{c<i} l_ic y_c ), unit diagonal, no division
+ *   3. backward      z_i = fl( Round( y_i - sum_{c>i} u_ic z_c ) / u_ii ), ONE IEEE division
+ * This is ExTRSV's row step: column j of block b is bit for bit what exblas_extrsv_dev ('L', 'N', 'U') followed by ('U', 'N',
+ * 'N') gives on the permuted column.  The info words of the factorisation are NOT consulted.  The bits do not depend on k,
+ * ldx, order, the column tile, the grid, the path, fpe (0 or 2..8), early_exit, the context or the stream.
+ * REFUSED with hipErrorInvalidValue before the device is touched: p > 64, p < 1 with n > 0, a bad order, negative sizes,
+ * ldlu < max(1, p), stride < ldlu * p with more than one block, ldx < k, fpe < 0, null pointers when anything would be
+ * launched.  n == 0 or k == 0: success, nothing is launched.  fpe >= 9: EXBLAS_UNSUPPORTED.
+ * ONE launch, no mailbox; capturable after one call.  Returns 0, EXBLAS_UNSUPPORTED or a hipError_t.
+ * Not provided: A^T solves, variable block sizes, p > 64, fusing the apply into ExSpMM. */
+int exblas_exgetrs_batched_dev(char order, int p, int64_t n, int k, const double *d_lu, int ldlu, int64_t stride,
+                               const int *d_ipiv, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
+/* Test hook for the batched ExGETRS (same bits on every path): 0 automatic, 1 every output rounded from the integer
+ * accumulator, 2 one block per wave, 3 column tiles of 4. */
+void exblas_set_getrs_batched_path(int mode);
+/* The most recent batched ExGETRS on this device: out[0] outputs rounded in registers, out[1] outputs rounded from the
+ * integer accumulator, out[2] = out[3] = 0.  out[0] + out[1] == 2 n k (both 0 for fpe == 1); all 0 after a call that
+ * launched nothing.  Synchronises the device.  Returns 0 or a hipError_t. */
+int exblas_last_getrs_batched_info(int64_t *out4);
 /* ExGEMM on device pointers, row-major (ExGEMM.Launcher.hpp; kernel gemm, ExGEMM.Superacc.cl:200-283). */
 int exblas_exgemm_dev(char transa, char transb, int m, int n, int k, double alpha,
                       const double *d_a, int lda, const double *d_b, int ldb, double beta,
@@ -701,6 +770,11 @@ int exblas_expotrf_batched_ctx(exblas_ctx_t *ctx, char uplo, int p, int64_t batc
                                int *d_info, int fpe, int early_exit, void *stream);
 int exblas_expotrs_batched_ctx(exblas_ctx_t *ctx, char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr,
                                int64_t stride, double *d_x, int64_t ldx, int fpe, int early_exit, void *stream);
+int exblas_exgetrf_batched_ctx(exblas_ctx_t *ctx, char order, int p, int64_t batch, double *d_a, int lda, int64_t stride,
+                               int *d_ipiv, int *d_info, int fpe, int early_exit, void *stream);
+int exblas_exgetrs_batched_ctx(exblas_ctx_t *ctx, char order, int p, int64_t n, int k, const double *d_lu, int ldlu,
+                               int64_t stride, const int *d_ipiv, double *d_x, int64_t ldx, int fpe, int early_exit,
+                               void *stream);
 int exblas_exbdot_export_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                              const double *d_y, int64_t ldy, int64_t *d_sets, int fpe, int early_exit, void *stream);
 int exblas_exbdot_round_ctx(exblas_ctx_t *ctx, char mode, int p, int q, const int64_t *d_sets, int nsets, double *d_c,
@@ -888,6 +962,16 @@ int exblas_expotrf_batched(char uplo, int p, int64_t batch, double *g, int ldg, 
  * device, synchronous.  Returns 0, hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
 int exblas_expotrs_batched(char uplo, char sweep, int p, int64_t n, int k, const double *r, int ldr, int64_t stride, double *x,
                            int64_t ldx, int fpe, int early_exit);
+/* exblas_exgetrf_batched_dev on host arrays (a: the batch matrices, stride apart, factored in place; padding and gaps come
+ * back as they went); ipiv (batch * p words) and info (batch words) may each be NULL: staged through the device,
+ * synchronous.  Returns 0, hipErrorInvalidValue or EXBLAS_UNSUPPORTED (fpe >= 9: nothing is touched). */
+int exblas_exgetrf_batched(char order, int p, int64_t batch, double *a, int lda, int64_t stride, int *ipiv, int *info, int fpe,
+                           int early_exit);
+/* exblas_exgetrs_batched_dev on host arrays (lu, ipiv: the ceil(n / p) factored blocks and their pivots; x: the n x k
+ * row-major block with leading dimension ldx, B on entry, the solution on return; its padding comes back as it went):
+ * staged through the device, synchronous.  Returns 0, hipErrorInvalidValue or EXBLAS_UNSUPPORTED. */
+int exblas_exgetrs_batched(char order, int p, int64_t n, int k, const double *lu, int ldlu, int64_t stride, const int *ipiv,
+                           double *x, int64_t ldx, int fpe, int early_exit);
 /* as exblas_exsum / exblas_exdot, additionally returning the full record (limbs, both roundings) */
 int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe, int early_exit,
                         int64_t *out_words);
