@@ -319,3 +319,52 @@ def restate(G):
             t = Fraction(float(G[j, i])) - sum(Fraction(float(R[k, j])) * Fraction(float(R[k, i])) for k in range(j))
             R[j, i] = np.float64(_round(t)) / np.float64(R[j, j])
     return R, 0
+
+
+# ---- the square root, the division and the range ---------------------------------------------------------------------
+def root_values():
+    """512 radicands: neighbours of perfect squares, perfect squares, 2^-1074, the largest double, 2^-1022 and its
+    predecessor, then random doubles over the whole range"""
+    rng = np.random.default_rng(512)
+    v = np.ldexp(rng.random(512) + 1.0, rng.integers(-1000, 1000, 512))
+    k = rng.integers(3, 2 ** 26, 120).astype(np.float64)
+    v[:120] = np.nextafter(k * k, np.where(np.arange(120) % 2 == 0, np.inf, 0.0))    # neighbours of perfect squares
+    v[120:160] = k[:40] * k[:40]
+    v[160], v[161], v[162], v[163] = 5e-324, np.finfo(np.float64).max, 2.0 ** -1022, np.nextafter(2.0 ** -1022, 0.0)
+    return v
+
+
+def range_cases():
+    """Inside the product domain of the solves (a product of two non-zero entries is at least 2^-968 in magnitude, so that
+    its error term is a double): totals and radicands that land among the subnormals, a total beyond the largest double,
+    and an infinite radicand."""
+    out = []
+    # r_01 r_02 = 2^-968 (1 + 3 2^-52 + 2^-103) against g_12 = its rounding: the total is the error term, -2^-1071
+    G = np.eye(3)
+    G[0, 1], G[0, 2] = (1 + 2.0 ** -52) * 2.0 ** -484, (1 + 2.0 ** -51) * 2.0 ** -484
+    G[1, 2] = G[0, 1] * G[0, 2]
+    out.append(("subnormal total", G))
+    # r_01^2 lies 2^27 - 1 units of 2^-1072 below the double g_11: the radicand is that, a subnormal
+    m = 2 ** 52 + 2 ** 26 - 1
+    G = np.eye(2)
+    G[0, 1] = float(Fraction(m, 2 ** 536))
+    G[1, 1] = float(Fraction(m * m + 2 ** 27 - 1, 2 ** 1072))
+    assert Fraction(G[1, 1]) - Fraction(G[0, 1]) ** 2 == Fraction(2 ** 27 - 1, 2 ** 1072)
+    out.append(("subnormal radicand", G))
+    # a total beyond the range: +Inf, which the last radicand then meets (-Inf: a breakdown at the last pivot)
+    big = 1.5 * 2.0 ** 1023
+    G = np.diag([1.0, big, big])
+    G[0, 1], G[0, 2], G[1, 2] = -1.5 * 2.0 ** 511, 1.5 * 2.0 ** 511, big
+    out.append(("overflow", G))
+    # +Inf passes as a radicand; its row becomes zeros
+    G = np.diag([1.0, np.inf, 9.0, 16.0])
+    G[0, 1], G[1, 2], G[1, 3], G[2, 3] = 3.0, 5.0, -7.0, 2.0
+    out.append(("inf", G))
+    out = [(name, np.triu(G) + np.triu(G, 1).T) for name, G in out]
+    # ... and the same inside a larger matrix, beyond the first tile
+    for name, G in list(out):
+        big = np.diag(np.arange(2.0, 72.0))
+        q = G.shape[0]
+        big[66:66 + q, 66:66 + q] = G
+        out.append((name + "@66", big))
+    return out

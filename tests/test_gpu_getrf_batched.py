@@ -2,7 +2,8 @@
 factorisation of getrf_cases (never against the code under test), at the seams of the packing, on every path and variant,
 both orders, padded leading dimensions and gaps between the matrices; the counters; planted ties, breakdowns and NaN
 matrices beside healthy ones; pivot ties and signed zeros; the plain variant, the reference rounding mode, refusals, contexts
-and host arrays.  A batch cycles seven distinct matrices."""
+and host arrays.  A batch cycles seven distinct matrices.  The ends of the double range (totals at the
+overflow threshold, around 2^1000, among the subnormals, zeros by cancellation) are in test_gpu_bjacobi_range.py."""
 import ctypes
 
 import numpy as np

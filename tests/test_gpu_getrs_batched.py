@@ -2,7 +2,8 @@
 substitution of exact_cases twice; never against the code under test), for every block size, at the seams of the blocks a wave
 carries and of the column tiles, with a short last block, on every path and variant, both orders and padded ldlu / stride /
 ldx; the counters; pivots out of range; ExTRSV as a second witness; the plain variant, refusals, contexts and host arrays.
-The blocks of a call cycle seven distinct factored blocks, its columns five patterns."""
+The blocks of a call cycle seven distinct factored blocks, its columns five patterns.  The ends of the double range (totals at the
+overflow threshold, around 2^1000, among the subnormals, zeros by cancellation) are in test_gpu_bjacobi_range.py."""
 import ctypes
 
 import numpy as np

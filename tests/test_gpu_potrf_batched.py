@@ -2,7 +2,8 @@
 of potrf_cases (never against the code under test), at the seams of the packing, on every path and variant, both
 triangles, both layouts, padded leading dimensions and gaps between the matrices; the counters; breakdowns and NaN matrices
 beside healthy ones; the plain variant, the reference rounding mode, the single routine as a second witness, refusals,
-contexts and host arrays.  A batch cycles seven distinct matrices (bjacobi_cases)."""
+contexts and host arrays.  A batch cycles seven distinct matrices (bjacobi_cases).  The ends of the double range (totals at the
+overflow threshold, around 2^1000, among the subnormals, zeros by cancellation) are in test_gpu_bjacobi_range.py."""
 import ctypes
 
 import numpy as np

@@ -3,7 +3,8 @@ index-reversed system; never against the code under test), for every block size,
 and of the column tiles, with a short last block, on every sweep, path and variant, both triangles, both layouts and padded
 ldr / stride / ldx; planted ties with the counters; 'B' against '1' then '2'; non-finite columns and blocks; ExTRSM as a
 second witness; the plain variant, the reference rounding mode, refusals, contexts and host arrays.  The blocks of a call
-cycle seven distinct factors, its columns five patterns (bjacobi_cases)."""
+cycle seven distinct factors, its columns five patterns (bjacobi_cases).  The ends of the double range (totals at the
+overflow threshold, around 2^1000, among the subnormals, zeros by cancellation) are in test_gpu_bjacobi_range.py."""
 import ctypes
 
 import numpy as np
