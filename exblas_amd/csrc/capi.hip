@@ -317,6 +317,7 @@ static void set_path(int CtxKnobs::*knob, int mode, int largest)
 void exblas_set_spmv_path(int mode) { set_path(&CtxKnobs::spmv_path, mode, 3); }
 void exblas_set_spmm_path(int mode) { set_path(&CtxKnobs::spmm_path, mode, 3); }
 void exblas_set_sptrsv_path(int mode) { set_path(&CtxKnobs::sptrsv_path, mode, 2); }
+void exblas_set_spilu0_path(int mode) { set_path(&CtxKnobs::spilu0_path, mode, 2); }
 void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3); }
 void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
@@ -371,6 +372,10 @@ int exblas_last_spmm_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::s
 // out[0] rows rounded in registers, out[1] rows rounded from their accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped; EXBLAS_SPTRSV_STALLED when the watchdog of that call was raised
 int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::sptrsv_info_dev, true, out4); }
+
+// out[0] entries rounded in registers, out[1] entries rounded from the accumulator, out[2] product terms summed, out[3] rows
+// in the several-entries-per-lane form; EXBLAS_SPTRSV_STALLED as above
+int exblas_last_spilu0_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::spilu0_info_dev, true, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
@@ -556,6 +561,18 @@ static int exsptrsv_on(Ctx &c, char uplo, char diag, int m, int index_bits, cons
     std::lock_guard<std::mutex> lk(c.mu);
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exsptrsv_dispatch(c, uplo, diag, m, index_bits, d_row_ptr, d_col_idx, d_val, d_x, fpe, early_exit,
+                                  round_mode(), st);
+}
+
+// m == 0 goes on: info is still zeroed, and the call counts as the device's last one
+static int exspilu0_on(Ctx &c, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                       double *d_lu, int64_t *d_info, int fpe, int early_exit, hipStream_t st)
+{
+    if (m < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64) || !d_info) return (int)hipErrorInvalidValue;
+    if (m > 0 && !d_row_ptr) return (int)hipErrorInvalidValue;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exspilu0_dispatch(c, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, (long long *)d_info, fpe, early_exit,
                                   round_mode(), st);
 }
 
@@ -1008,6 +1025,13 @@ int exblas_exsptrsv_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int in
                        (hipStream_t)stream);
 }
 
+int exblas_exspilu0_csr_ctx(exblas_ctx_t *h, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                            const double *d_val, double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream)
+{
+    EXB_HANDLE(h);
+    return exspilu0_on(*cp, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, d_info, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exsptrsm_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
                             const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
                             void *stream)
@@ -1224,6 +1248,12 @@ int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row
     return exblas_exspmm_csr_ctx(nullptr, m, n, k, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, ldx, beta, d_y, ldy,
                                  fpe, early_exit, stream);
 }
+int exblas_exspilu0_csr_dev(int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                            double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream)
+{
+    return exblas_exspilu0_csr_ctx(nullptr, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, d_info, fpe, early_exit, stream);
+}
+
 int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                             const double *d_val, double *d_x, int fpe, int early_exit, void *stream)
 {
@@ -1609,11 +1639,11 @@ int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int
 
 // The host-pointer CSR call: Y (m x k, row stride ldy) from X (n x k, row stride ldx); ExSpMV is k = 1, ldx = ldy = 1.
 // One staging block [row_ptr | col_idx | val | X | Y] goes to the device, launch(c, d_row_ptr, d_col_idx, d_val, d_x, d_y)
-// runs the routine on the context's stream, and Y comes back.
+// runs the routine on the context's stream, and Y comes back.  ywords != 0: Y is that many words, not an m x k block.
 template <class Launch>
 static int csr_host_call(const char *who, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
                          const double *val, const double *x, int64_t ldx, double *y, int64_t ldy, int fpe,
-                         Launch &&launch)
+                         Launch &&launch, size_t ywords = 0)
 {
     bool empty;
     const int bad = csr_check_args(m, n, k, index_bits, row_ptr, x, ldx, y, ldy, fpe, &empty);
@@ -1630,7 +1660,7 @@ static int csr_host_call(const char *who, int m, int n, int k, int index_bits, c
     HostCall hc(who);
     // whole rows of X and Y travel, padding included (the last row only up to its k-th entry)
     const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)k : 0;
-    const size_t yspan = (size_t)(m - 1) * (size_t)ldy + (size_t)k;
+    const size_t yspan = ywords ? ywords : (size_t)(m - 1) * (size_t)ldy + (size_t)k;
     const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
                  b_val = align_up((size_t)nnz * 8), b_x = align_up(xspan * 8), b_y = align_up(yspan * 8);
     char *d = (char *)hc.in(0, b_rp + b_ci + b_val + b_x + b_y, row_ptr, (size_t)(m + 1) * isz);
@@ -1688,6 +1718,33 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
                                                         c.stream);
                                  });
     return (rc || m == 0) ? rc : host_solve_status(&CtxWsPtrs::sptrsv_info_dev);
+}
+
+// the shared CSR host path with Y = [lu | info]: nnz values (they travel both ways, so that a refused structure leaves
+// lu as it was) and the two info words behind them
+int exblas_exspilu0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *lu,
+                        int64_t *info, int fpe, int early_exit)
+{
+    if (m < 0 || !info || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
+    info[0] = info[1] = 0;
+    if (m == 0) return fpe < 0 ? (int)hipErrorInvalidValue : 0;
+    if (!row_ptr) return (int)hipErrorInvalidValue;
+    long long nnz = 0;   // as csr_host_call counts them (it refuses a negative entry)
+    for (int i = 0; i <= m; ++i)
+        nnz = std::max(nnz, index_bits == 32 ? (long long)((const int32_t *)row_ptr)[i] : (long long)((const int64_t *)row_ptr)[i]);
+    if (nnz > 0 && !lu) return (int)hipErrorInvalidValue;
+    std::vector<double> y((size_t)nnz + 2, 0.0);
+    if (nnz > 0) memcpy(y.data(), lu, (size_t)nnz * sizeof(double));
+    const int rc = csr_host_call(
+        "exblas_exspilu0_csr", m, 0, 1, index_bits, row_ptr, col_idx, val, nullptr, 1, y.data(), 1, fpe,
+        [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *, double *d_y) {
+            return exspilu0_on(c, m, index_bits, d_rp, d_ci, d_val, d_y, (int64_t *)(d_y + nnz), fpe, early_exit, c.stream);
+        },
+        (size_t)nnz + 2);
+    if (rc) return rc;
+    if (nnz > 0) memcpy(lu, y.data(), (size_t)nnz * sizeof(double));
+    memcpy(info, y.data() + nnz, 2 * sizeof(int64_t));
+    return host_solve_status(&CtxWsPtrs::spilu0_info_dev);
 }
 
 // the same with a block: X (m x k, row stride ldx; B on entry, the solution on return) travels as the host path's Y

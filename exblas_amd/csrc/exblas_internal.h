@@ -31,6 +31,8 @@ struct CtxKnobs {
                              // 2 in-register rounding wherever certified (no row split), 3 every row split at a small chunk
     int sptrsv_path = 0;     // exblas_set_sptrsv_path: 0 automatic, 1 every row rounded from its integer accumulator,
                              // 2 every row in the one-row-per-wave form
+    int spilu0_path = 0;     // exblas_set_spilu0_path: 0 automatic, 1 every rounding from the wave's integer accumulator,
+                             // 2 every row in the several-entries-per-lane form
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
     int trsm_path = 0;       // exblas_set_trsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
@@ -71,6 +73,9 @@ struct CtxWsPtrs {
     const long long *spmv_info_dev = nullptr;    // header of the last ExSpMV call's workspace (exblas_last_spmv_info)
     const long long *spmm_info_dev = nullptr;    // header of the last ExSpMM call's workspace (exblas_last_spmm_info)
     const long long *sptrsv_info_dev = nullptr;  // header of the last ExSpTRSV call's workspace (nullptr: it launched nothing)
+    const long long *spilu0_info_dev = nullptr;  // header of the last ExSpILU0 call's workspace (nullptr: it launched nothing)
+    int spilu0_m = -1;                           // ... and what its mailbox was sized for: a call that is being captured
+    long long spilu0_nnz = 0;                    // cannot read row_ptr[m] and takes these (spilu0.hip)
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
     SlotInfo bgemm_slots, btrsm_slots, potrf_slots;   // of the last ExBGEMM, ExBTRSM and ExPOTRF (one workgroup) call
@@ -205,6 +210,10 @@ hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const vo
 // sptrsv.hip
 hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,
                              const double *val, double *x, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// spilu0.hip
+hipError_t exspilu0_dispatch(Ctx &c, int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                             double *lu, long long *info, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // sptrsm.hip
 hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *row_ptr,

@@ -342,6 +342,51 @@ void exblas_set_sptrsm_path(int mode);
  * the device; valid until the next call that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as
  * exblas_last_sptrsv_info does. */
 int exblas_last_sptrsm_info(int64_t *out4);
+/* ExSpILU0: the exact-sum ILU(0) factor of a square m x m CSR matrix A on device pointers (row_ptr[m+1], col_idx[nnz]
+ * int32 or int64, both the same width; val and lu contiguous fp64 of nnz entries).  Every row must have strictly ascending
+ * column indices and a stored diagonal; S is the set of stored positions and the factor has the same pattern.  For every
+ * stored (i, j), rows in ascending order,
+ *     c_ij = Round(a_ij - sum over k of l_ik * u_kj)      k < min(i, j), (i, k) in S, (k, j) in S
+ *     j <  i:  l_ij = c_ij / u_jj   (one IEEE fp64 quotient)          j >= i:  u_ij = c_ij
+ * the sum exact over the already fixed doubles (every TwoProd pair goes in) and rounded once, Round being the
+ * superaccumulator rounding of the current rounding mode (exblas_set_round_mode).  This is the step of
+ * exblas_exgetrf_batched_dev without the pivot search: on a dense pattern where partial pivoting never swaps, lu holds the
+ * bits that routine gives with batch = 1.  L has a unit diagonal and is stored strictly below it, U on and above it, both
+ * in ONE value array d_lu on A's own row_ptr / col_idx: exblas_exsptrsv_csr_dev('L', 'U', ..., d_lu, x) followed by
+ * exblas_exsptrsv_csr_dev('U', 'N', ..., d_lu, x) (or the ExSpTRSM pair) applies the factor as it is, each solve skipping
+ * the other triangle unread.  Non-finite operands and zero pivots follow IEEE arithmetic (Inf - Inf and 0 * Inf are NaN,
+ * c / 0 is what the division gives); the factorisation does not stop.  d_lu may be d_val (a_ij is read once, by the wave
+ * that writes lu_ij): same bits.
+ * d_info is int64[2] on the device, written in stream order.  info[0]: 0, or r + 1 for the smallest row r with a
+ * structural defect -- row_ptr decreasing (or a row outside [0, row_ptr[m]]), a column outside [0, m), columns not
+ * strictly ascending, no stored diagonal, more than EXBLAS_SPILU0_MAX_ROW entries -- and then d_lu is not written at all.
+ * info[1]: 0, or r + 1 for the smallest row whose pivot u_rr is zero or NaN (LAPACK's first zero pivot; an Inf pivot is
+ * not reported).  Both are order-independent minima.
+ * The bits depend on the data and the rounding mode only: not on the grid, the index width, the path
+ * (exblas_set_spilu0_path), fpe (0 or >= 2), early_exit, the context or the stream.  fpe == 0 rounds every entry from the
+ * integer accumulator; fpe == 1 is the plain fp64 form s = a_ij, then s -= l_ik * u_kj for k ascending (deterministic,
+ * not exact).
+ * One stream-ordered chain of three kernels (preset, structure check, one persistent factor kernel), no analysis phase.
+ * Context workspace: 256 + 8 m (rounded up to 256) + 8 nnz bytes (header, the diagonal position of every row, a mailbox of
+ * one double per stored entry).  The signature carries no nnz: a call outside a stream capture reads row_ptr[m] back (one
+ * word, one wait on the stream) to size the mailbox; info and lu are written without a host synchronisation.  A call that
+ * is being captured reads nothing back: it is capturable after exblas_reserve_workspace of that many bytes or one call of
+ * the same m and pattern, and on replay serves any values on a pattern of at most the nnz it was captured with (a row
+ * that does not fit the mailbox is reported in info[0]).  m == 0: info is zeroed, nothing else is launched.  m < 0,
+ * index_bits other than 32 / 64, fpe < 0 or d_info null: hipErrorInvalidValue.  Returns 0 or a hipError_t.
+ * Not provided: IC(0), fill (ILU(k), ILUT), modified ILU, pivoting, unsorted rows, BSR / CSC. */
+#define EXBLAS_SPILU0_MAX_ROW 512
+int exblas_exspilu0_csr_dev(int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                            double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream);
+/* Test hook for ExSpILU0 (same bits on every path): 0 automatic, 1 every rounding through the wave's integer accumulator,
+ * 2 every row in the several-entries-per-lane form (8 lanes share a row of at most 64 entries). */
+void exblas_set_spilu0_path(int mode);
+/* The most recent ExSpILU0 on this device: out[0] entries rounded in registers, out[1] entries rounded from the integer
+ * accumulator (out[0] + out[1] == nnz on a sound, completed call with fpe != 1; both 0 for fpe == 1), out[2] product terms
+ * l_ik * u_kj summed (the triples (i, k, j) of the definition), out[3] rows in the several-entries-per-lane form; all 0
+ * after a call that launched nothing or met a structural defect.  Synchronises the device; valid until the next call
+ * that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as exblas_last_sptrsv_info does. */
+int exblas_last_spilu0_info(int64_t *out4);
 /* ExTRSM: ExTRSV with k right-hand sides.  A is the n x n column-major triangle of exblas_extrsv_dev (lda >= max(1, n),
  * uplo 'L'/'U', transa 'N'/'T', diag 'N'/'U'); d_x is an n x k ROW-MAJOR block with leading dimension ldx >= k, as in
  * ExSpTRSM and ExBDOT, that holds B on entry and the solution on return.  For every column j, X[:, j] afterwards holds
@@ -749,6 +794,8 @@ int exblas_exgemm_ctx(exblas_ctx_t *ctx, char transa, char transb, int m, int n,
 int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, double beta,
                           double *d_y, int fpe, int early_exit, void *stream);
+int exblas_exspilu0_csr_ctx(exblas_ctx_t *ctx, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                            const double *d_val, double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream);
 int exblas_exsptrsv_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
                             const void *d_col_idx, const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
 int exblas_exsptrsm_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
@@ -919,6 +966,11 @@ int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const v
 int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
                       double alpha, const double *x, int64_t ldx, double beta, double *y, int64_t ldy, int fpe,
                       int early_exit);
+/* exblas_exspilu0_csr_dev on host arrays (lu: nnz values out, left as they are on a structural defect; info: two words):
+ * staged through the device, synchronous.  Returns 0, hipErrorInvalidValue (also for a negative row_ptr entry) or
+ * EXBLAS_SPTRSV_STALLED (see exblas_last_spilu0_info). */
+int exblas_exspilu0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *lu,
+                        int64_t *info, int fpe, int early_exit);
 /* exblas_exsptrsv_csr_dev on host arrays (x: b on entry, the solution on return): staged through the device, synchronous.
  * Returns 0, hipErrorInvalidValue (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see
  * exblas_last_sptrsv_info). */
