@@ -65,6 +65,15 @@ def round_away(t):
     return v
 
 
+def reference_round(t):
+    """the reference's rounding of an exact total: the oracle's restatement on the canonical limbs"""
+    import blas1_cases as B
+    from oracle import pyoracle
+    T = t * 2 ** 1074
+    assert T.denominator == 1 and B.canon_fits(T.numerator)
+    return float(pyoracle.round_limbs(B.canon_matrix([T.numerator])[0], pyoracle.ROUND_REFERENCE))
+
+
 def ilu0_exact(crow, col, val, detail=False, rounder=None, round_products=False):
     """(lu, info0, info1): the definition.  Every total is summed exactly (integers at a fixed binary scale), `rounder`
     (default: nearest even) does the one rounding, the quotient of two np.float64 the division.  A non-finite operand

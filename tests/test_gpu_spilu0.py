@@ -253,13 +253,7 @@ def test_graph_capture_of_factor_and_apply_replayed_on_new_values(ex):
 # ---------------------------------------------------------------------------------------------
 # 7. the reference rounding mode and the plain variant
 # ---------------------------------------------------------------------------------------------
-def _reference_round(t):
-    """the reference's rounding of an exact total: the oracle's restatement on the canonical limbs"""
-    import blas1_cases as B
-    from oracle import pyoracle
-    T = t * 2 ** 1074
-    assert T.denominator == 1 and B.canon_fits(T.numerator)
-    return float(pyoracle.round_limbs(B.canon_matrix([T.numerator])[0], pyoracle.ROUND_REFERENCE))
+_reference_round = S.reference_round      # (shared with the CPU tests of the edge cases)
 
 
 def test_reference_rounding_mode_follows_the_model_with_the_reference_rounding(ex):
