@@ -35,7 +35,8 @@ C_ABI_SYMBOLS = [
     "exblas_comm_unique_id", "exblas_comm_init_rccl", "exblas_comm_adopt_rccl", "exblas_comm_init_host",
     "exblas_comm_destroy", "exblas_comm_rank", "exblas_comm_size", "exblas_shard_range",
     "exblas_exsum_allreduce_dev", "exblas_exdot_allreduce_dev", "exblas_allreduce_finish_dev",
-    "exblas_exgemv_sharded_dev", "exblas_exgemm_sharded_dev", "exblas_last_gemm_info", "exblas_set_gemm_max_slices",
+    "exblas_exgemv_sharded_dev", "exblas_exgemm_sharded_dev", "exblas_last_gemm_info", "exblas_last_blas1_info",
+    "exblas_set_gemm_max_slices",
     "exblas_set_gemm_max_moduli", "exblas_crt_selftest",
     "exblas_set_host_devices", "exblas_workspace_bytes",
     "exblas_exsum_allreduce_pipelined_dev", "exblas_exdot_allreduce_pipelined_dev", "exblas_pipeline_drain_dev",
@@ -160,6 +161,7 @@ def load_library():
     L.exblas_last_gemm_info_ctx.argtypes = [vp, C.POINTER(C.c_int)]
     L.exblas_set_host_devices.argtypes = [i32, C.POINTER(C.c_int)]
     L.exblas_last_gemm_info.argtypes = [C.POINTER(C.c_int)]
+    L.exblas_last_blas1_info.argtypes = [C.POINTER(C.c_int)]
     L.exblas_set_gemm_max_slices.argtypes = [i32]
     L.exblas_set_gemm_max_slices.restype = None
     L.exblas_set_gemm_max_moduli.argtypes = [i32]
@@ -337,6 +339,15 @@ def set_launch_events(ev_start, ev_stop):
 def set_accumulator_slot(slot):
     """Select which of the context's two accumulator sets the next accumulate/finish calls use (pipelining)."""
     _check(load_library().exblas_set_accumulator_slot(int(slot)), "set_accumulator_slot")
+
+
+def last_blas1_info():
+    """(kernel, grid, group accumulators, compute units) of the last streaming ExSUM / ExDOT launch of the device's
+    default context: kernel 1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 0 before the first launch.
+    Host state recorded at launch; does not synchronise."""
+    v = (C.c_int * 8)()
+    _check(load_library().exblas_last_blas1_info(v), "last_blas1_info")
+    return tuple(int(x) for x in v[:4])
 
 
 def exsum_segmented_dev(values, offsets, fpe=8, early_exit=True, out=None):

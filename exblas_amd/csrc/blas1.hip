@@ -538,6 +538,7 @@ static void run_exsum(Ctx &c, const double *a, long long n, hipStream_t st)
     // an odd number of workgroups (one resident slot left idle): the tiles a workgroup has in flight are grid x 16 KiB
     // apart, and with an even grid they compete for the same HBM channels -- 865 against 855 Gelem/s at n = 2^28
     if (grid == c.num_cu * bpc && grid > 1 && !(grid & 1)) grid -= 1;
+    c.last_blas1_kernel = BLAS1_K_EXSUM, c.last_blas1_grid = grid;   // (exblas_last_blas1_info)
     EXB_LAUNCH_STREAMING(c, (k_exsum<N, EE, COPIES>), grid, st, a, n, c.gacc, c.gflags, c.ngroups);
 }
 
@@ -555,6 +556,7 @@ static hipError_t launch_exsum(Ctx &c, const double *a, long long n, long long i
         run_exsum<N, EE, COPIES>(c, a, n, st);
     } else {
         int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
+        c.last_blas1_kernel = BLAS1_K_EXSUM_STRIDED, c.last_blas1_grid = grid;
         EXB_LAUNCH_STREAMING(c, (k_exsum_strided<N, EE, COPIES>), grid, st, a, n, inca, c.gacc, c.gflags, c.ngroups);
     }
     return hipGetLastError();
@@ -578,6 +580,7 @@ static void run_exdot(Ctx &c, const double *a, const double *b, long long n, hip
     if (grid > c.num_cu && !(grid & 1)) grid += 1;
     // early-exit votes by one fp64 compare per residue (ZM = 1): median 0.658 ms against 0.699 by integer ORs at
     // n = 2^28 (tools/tune.py, same box)
+    c.last_blas1_kernel = BLAS1_K_EXDOT, c.last_blas1_grid = grid;
     EXB_LAUNCH_STREAMING(c, (k_exdot<N, EE, COPIES, SKIP_ZERO_LEVELS<EE> ? 1 : 0>), grid, st, a, b, n, c.gacc, c.gflags,
                          c.ngroups);
 }
@@ -592,6 +595,7 @@ static hipError_t launch_exdot(Ctx &c, const double *a, long long inca, const do
         run_exdot<N, EE, COPIES>(c, a, b, n, st);
     } else {
         int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
+        c.last_blas1_kernel = BLAS1_K_EXDOT_STRIDED, c.last_blas1_grid = grid;
         EXB_LAUNCH_STREAMING(c, (k_exdot_strided<N, EE, COPIES>), grid, st, a, inca, b, incb, n, c.gacc, c.gflags,
                              c.ngroups);
     }

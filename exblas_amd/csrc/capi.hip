@@ -305,6 +305,23 @@ int exblas_last_gemm_slices(void)
     return v[1] > v[2] ? v[1] : v[2];
 }
 
+// The last streaming ExSUM / ExDOT launch of the current device's default context (the *_dev entry points): out[0] the
+// kernel (1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided; 0: none yet), out[1] its grid, out[2] the group
+// accumulators, out[3] the compute units the geometry was sized for, out[4..7] reserved.  Host state only: nothing is
+// read from the device and nothing synchronises.
+int exblas_last_blas1_info(int *out)
+{
+    if (!out) return (int)hipErrorInvalidValue;
+    Ctx &c = ctx(-1);
+    std::lock_guard<std::mutex> lk(c.mu);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = c.last_blas1_kernel;
+    out[1] = c.last_blas1_grid;
+    out[2] = c.ngroups;
+    out[3] = c.num_cu;
+    return 0;
+}
+
 void exblas_set_gemm_max_slices(int s) { for_each_layer([&](Ctx &c) { c.gemm_max_slices = s; }); }
 void exblas_set_gemm_max_moduli(int l) { for_each_layer([&](Ctx &c) { c.gemm_max_moduli = l; }); }
 void exblas_set_gemm_path(int mode) { for_each_layer([&](Ctx &c) { c.gemm_path = mode; }); }

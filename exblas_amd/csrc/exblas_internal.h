@@ -96,6 +96,9 @@ struct Ctx : CtxKnobs, CtxWsPtrs {
     hipEvent_t launch_start_event = nullptr;
     int last_gemm_slices = 0;  // host-decided ExGEMM paths: 0 scalar kernel; 2..4: fp64-slice MFMA path with that many slices
     int gemm_ws_moduli = 0;  // moduli the last residue-path call actually reserved for (fewer after an out-of-memory retry)
+    // the last streaming ExSUM / ExDOT launch of this context (exblas_last_blas1_info), written on the host when it
+    // launches: kernel (BLAS1_K_*) and grid, both 0 before the first launch
+    int last_blas1_kernel = 0, last_blas1_grid = 0;
     long long *gacc = nullptr;   // ACTIVE accumulator set: [ngroups][NL] int64, zero between calls
     unsigned *gflags = nullptr;  // non-finite input flags of the active set, zero between calls
     // two sets, so that the finalize of step i (side stream) can overlap the streaming kernel of step i+1
@@ -177,6 +180,8 @@ bool select_variant(int fpe, int early_exit, F &&f)
 struct GemmChunks;
 
 // blas1.hip
+// Ctx::last_blas1_kernel: which streaming kernel the last ExSUM / ExDOT launch of the context was
+enum { BLAS1_K_EXSUM = 1, BLAS1_K_EXSUM_STRIDED = 2, BLAS1_K_EXDOT = 3, BLAS1_K_EXDOT_STRIDED = 4 };
 hipError_t exsum_dispatch(Ctx &c, const double *a, long long n, long long inca, int fpe, int early_exit,
                           hipStream_t st);
 hipError_t exdot_dispatch(Ctx &c, const double *a, long long inca, const double *b, long long incb, long long n,

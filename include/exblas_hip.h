@@ -122,6 +122,13 @@ void exblas_set_gemm_max_moduli(int l);
  * per element pair); out[4] = moduli the workspace was reserved for (39, fewer after an out-of-memory retry).  Synchronises the device when the decision was taken there.  exblas_last_gemm_slices() =
  * max(out[1], out[2]) for the slice paths, out[3] for residues, 0 for the scalar kernel. */
 int exblas_last_gemm_info(int *out8);
+/* The most recent streaming ExSUM / ExDOT launch of this device's default context (the *_dev entry points and
+ * exblas_*_ctx with a NULL handle): out[0] = kernel (1 contiguous ExSUM, 2 strided ExSUM, 3 contiguous 16-byte-aligned
+ * ExDOT, 4 strided or misaligned ExDOT, 0 nothing launched yet), out[1] = workgroups launched, out[2] = group
+ * accumulators (EXBLAS_NGROUPS / exblas_set_tuning), out[3] = compute units the geometry is sized for, out[4..7] = 0.
+ * Recorded on the host at launch: no synchronisation, nothing read from the device.  For tests and tuning tools that
+ * must know which launch geometry a size took.  Returns 0 or hipErrorInvalidValue (out8 NULL). */
+int exblas_last_blas1_info(int *out8);
 /* CPU-only self-test of the residue path's constant tables and reconstruction formulas: `cases` random integers per
  * modulus count through a host mirror of the device arithmetic; returns the number of failures (0 = pass). */
 int exblas_crt_selftest(int cases, unsigned seed);

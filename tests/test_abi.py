@@ -31,6 +31,16 @@ def test_c_abi_symbols_exported(lib):
         assert hasattr(lib, name), name
 
 
+def test_last_blas1_info_is_declared_exported_and_wrapped(lib):
+    """exblas_last_blas1_info (the launch report the stream-geometry tests rest on): in the header, in the symbol list, in
+    the library with its argument type, behind a Python wrapper; a NULL pointer is refused before any device is touched."""
+    import exblas_amd
+    assert "exblas_last_blas1_info" in _declared_c_symbols() and "exblas_last_blas1_info" in exblas_amd.C_ABI_SYMBOLS
+    assert lib.exblas_last_blas1_info.argtypes == [ctypes.POINTER(ctypes.c_int)]
+    assert callable(exblas_amd.last_blas1_info)
+    assert lib.exblas_last_blas1_info(None) == 1       # hipErrorInvalidValue
+
+
 def test_cxx_api_symbols_exported():
     """exsum/exdot/exgemv/extrsv/exgemm with the reference's C++ signatures (blas1.hpp:48,74; blas2.hpp:57,95; blas3.hpp:56)."""
     import exblas_amd
