@@ -989,17 +989,18 @@ class _Last2:
         return self._strides[i]
 
 
-def _batched_triangles(who, name, shape, stride_of, uplo):
+def _batched_squares(who, name, shape, stride_of, uplo, max_p, max_name):
     """The rules of the 3-D operand `name` ([batch, p, p]) of the batched routines, device or host: every matrix has one
     unit stride among its last two dimensions (_trsm_layout: a row-major matrix is the other triangle of its transpose),
-    stride(0) is the batch stride and the matrices do not overlap.  Returns (uplo, batch, p, ld, stride) for the C call."""
+    stride(0) is the batch stride and the matrices do not overlap.  Returns (uplo as _trsm_layout flipped it, batch, p, ld,
+    stride)."""
     if len(shape) != 3:
         raise ValueError(f"{who}: {name} must be 3-D [batch, p, p]")
     batch, p = int(shape[0]), int(shape[1])
     if shape[2] != p:
         raise ValueError(f"{who}: the matrices of {name} must be square, got shape {tuple(shape)}")
-    if p > POTRF_BATCHED_MAX_P:
-        raise ValueError(f"{who}: p = {p} exceeds EXBLAS_POTRF_BATCHED_MAX_P = {POTRF_BATCHED_MAX_P}")
+    if p > max_p:
+        raise ValueError(f"{who}: p = {p} exceeds {max_name} = {max_p}")
     last2 = _Last2(shape, stride_of)
     if batch == 0:
         last2._strides = (p, 1)                     # no matrix: any strides do
@@ -1008,7 +1009,54 @@ def _batched_triangles(who, name, shape, stride_of, uplo):
     stride = int(stride_of.stride(0))
     if batch > 1 and stride < ld * p:
         raise ValueError(f"{who}: the matrices of {name} overlap: stride(0) = {stride} < {ld * p}")
-    return u.encode(), batch, p, ld, (stride if batch > 1 else ld * max(p, 1))
+    return u, batch, p, ld, (stride if batch > 1 else ld * max(p, 1))
+
+
+def _batched_triangles(who, name, shape, stride_of, uplo):
+    """_batched_squares for the Cholesky routines; returns (uplo, batch, p, ld, stride) for the C call."""
+    u, *rest = _batched_squares(who, name, shape, stride_of, uplo, POTRF_BATCHED_MAX_P, "EXBLAS_POTRF_BATCHED_MAX_P")
+    return (u.encode(), *rest)
+
+
+def _batched_blocks(who, name, n, p, batch):
+    """n rows in blocks of p need ceil(n / p) factors in the operand `name`"""
+    if n > 0 and p < 1:
+        raise ValueError(f"{who}: the blocks of {name} are empty (p = 0) but X has rows")
+    want = -(-n // p) if p > 0 else 0
+    if batch != want:
+        raise ValueError(f"{who}: {name} holds {batch} blocks of p = {p}, X with n = {n} rows needs {want}")
+
+
+def _batched_apply_args(who, name, F, X, factors, fpe):  # noqa: N803
+    """What the device batched ExPOTRS and ExGETRS ask of their operands, in the order the checks are made: F (the operand
+    `name`) and X are float64 tensors, X is 2-D; factors() then holds F (and what goes with it) to its own rules and
+    returns a tuple that ends in (batch, p, ld, stride); X has a row per row of the blocks, is row-major and solved in
+    place, lies on F's device and does not overlap F.  Returns (what factors() returned, n, k, fpe)."""
+    torch = _torch()
+    for nm, t in ((name, F), ("X", X)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
+            raise ValueError(f"{who}: {nm} must be a float64 torch tensor")
+    if X.dim() != 2:
+        raise ValueError(f"{who}: X must be 2-D (n x k, one column per right-hand side)")
+    geo = factors()
+    batch, p, ld, stride = geo[-4:]
+    n, k = int(X.shape[0]), int(X.shape[1])
+    _batched_blocks(who, name, n, p, batch)
+    # a block that does not conform is refused, not copied: it is solved in place
+    if n > 0 and k > 0 and ((k > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < k)):
+        raise ValueError(f"{who}: X must be row-major with stride(1) == 1 and stride(0) >= k (its rows must not "
+                         "overlap; it is solved in place)")
+    fpe = _fpe_0_to_8(who, fpe)
+    if F.device != X.device:
+        raise ValueError(f"{who}: {name}, X must be on one device")
+    if batch > 0 and n > 0 and k > 0:
+        r0, x0 = F.data_ptr(), X.data_ptr()
+        r1 = r0 + 8 * ((batch - 1) * stride + (p - 1) * ld + p)
+        x1 = x0 + 8 * ((n - 1) * _ld(X, k) + k)
+        if r0 < x1 and x0 < r1:
+            raise ValueError(f"{who}: X overlaps {name} (X is solved in place while {name} is read)")
+    _on_gpu(who, **{name: F, "X": X})
+    return geo, n, k, fpe
 
 
 def _potrf_batched_args(G, uplo, info, fpe, early_exit):
@@ -1039,42 +1087,14 @@ def _potrs_sweep(sweep):
     return s.encode()
 
 
-def _potrs_blocks(n, p, batch):
-    """n rows in blocks of p need ceil(n / p) factors"""
-    if n > 0 and p < 1:
-        raise ValueError("expotrs_batched: the blocks of R are empty (p = 0) but X has rows")
-    want = -(-n // p) if p > 0 else 0
-    if batch != want:
-        raise ValueError(f"expotrs_batched: R holds {batch} blocks of p = {p}, X with n = {n} rows needs {want}")
-
-
 def _potrs_batched_args(R, X, uplo, sweep, fpe, early_exit):
     """Validates a device batched ExPOTRS call before anything is launched (no GPU needed for that); returns the C
     arguments up to the stream.  Neither operand is copied."""
-    torch = _torch()
-    for name, t in (("R", R), ("X", X)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise ValueError(f"expotrs_batched: {name} must be a float64 torch tensor")
-    if X.dim() != 2:
-        raise ValueError("expotrs_batched: X must be 2-D (n x k, one column per right-hand side)")
-    u, batch, p, ldr, stride = _batched_triangles("expotrs_batched", "R", tuple(R.shape), R, uplo)
-    s = _potrs_sweep(sweep)
-    n, k = int(X.shape[0]), int(X.shape[1])
-    _potrs_blocks(n, p, batch)
-    # a block that does not conform is refused, not copied: it is solved in place
-    if n > 0 and k > 0 and ((k > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < k)):
-        raise ValueError("expotrs_batched: X must be row-major with stride(1) == 1 and stride(0) >= k (its rows must not "
-                         "overlap; it is solved in place)")
-    fpe = _fpe_0_to_8("expotrs_batched", fpe)
-    if R.device != X.device:
-        raise ValueError("expotrs_batched: R, X must be on one device")
-    if batch > 0 and n > 0 and k > 0:
-        r0, x0 = R.data_ptr(), X.data_ptr()
-        r1 = r0 + 8 * ((batch - 1) * stride + (p - 1) * ldr + p)
-        x1 = x0 + 8 * ((n - 1) * _ld(X, k) + k)
-        if r0 < x1 and x0 < r1:
-            raise ValueError("expotrs_batched: X overlaps R (X is solved in place while R is read)")
-    _on_gpu("expotrs_batched", R=R, X=X)
+    def factors():
+        u, *geo = _batched_triangles("expotrs_batched", "R", tuple(R.shape), R, uplo)
+        return (u, _potrs_sweep(sweep), *geo)
+
+    (u, s, batch, p, ldr, stride), n, k, fpe = _batched_apply_args("expotrs_batched", "R", R, X, factors, fpe)
     return (u, s, p, n, k, _ptr(R), ldr, stride, _ptr(X), _ld(X, max(k, 1)), fpe, int(bool(early_exit)))
 
 
@@ -1106,26 +1126,11 @@ GETRF_BATCHED_MAX_P = 64  # EXBLAS_GETRF_BATCHED_MAX_P: a wider block is refused
 
 
 def _batched_matrices(who, name, shape, stride_of):
-    """The rules of the 3-D operand `name` ([batch, p, p]) of the batched LU routines, device or host: those of
-    _batched_triangles (one unit stride among the last two dimensions of every matrix, stride(0) the batch stride, no
-    overlap), but a general matrix has no other triangle to flip to: the unit stride picks the C routine's `order`, 'C'
-    for stride(1) == 1 and 'R' for stride(2) == 1.  Returns (order, batch, p, ld, stride) for the C call."""
-    if len(shape) != 3:
-        raise ValueError(f"{who}: {name} must be 3-D [batch, p, p]")
-    batch, p = int(shape[0]), int(shape[1])
-    if shape[2] != p:
-        raise ValueError(f"{who}: the matrices of {name} must be square, got shape {tuple(shape)}")
-    if p > GETRF_BATCHED_MAX_P:
-        raise ValueError(f"{who}: p = {p} exceeds EXBLAS_GETRF_BATCHED_MAX_P = {GETRF_BATCHED_MAX_P}")
-    last2 = _Last2(shape, stride_of)
-    if batch == 0:
-        last2._strides = (p, 1)                     # no matrix: any strides do
-    u, _, ld = _trsm_layout(last2, "U", "N", who)   # 'U' comes back flipped for a row-major matrix
-    ld = max(ld, 1)
-    stride = int(stride_of.stride(0))
-    if batch > 1 and stride < ld * p:
-        raise ValueError(f"{who}: the matrices of {name} overlap: stride(0) = {stride} < {ld * p}")
-    return (b"C" if u == "U" else b"R"), batch, p, ld, (stride if batch > 1 else ld * max(p, 1))
+    """_batched_squares for the LU routines.  A general matrix has no other triangle to flip to: the unit stride picks the C
+    routine's `order`, 'C' for stride(1) == 1 and 'R' for stride(2) == 1 ('U' comes back flipped for a row-major matrix).
+    Returns (order, batch, p, ld, stride) for the C call."""
+    u, *rest = _batched_squares(who, name, shape, stride_of, "U", GETRF_BATCHED_MAX_P, "EXBLAS_GETRF_BATCHED_MAX_P")
+    return ((b"C" if u == "U" else b"R"), *rest)
 
 
 def _getrf_batched_args(A, ipiv, info, fpe, early_exit):
@@ -1162,42 +1167,15 @@ def _getrf_pivots(who, ipiv, batch, p, like):
         raise ValueError(f"{who}: ipiv must be on the device of the matrices")
 
 
-def _getrs_blocks(n, p, batch):
-    """n rows in blocks of p need ceil(n / p) factored blocks"""
-    if n > 0 and p < 1:
-        raise ValueError("exgetrs_batched: the blocks of LU are empty (p = 0) but X has rows")
-    want = -(-n // p) if p > 0 else 0
-    if batch != want:
-        raise ValueError(f"exgetrs_batched: LU holds {batch} blocks of p = {p}, X with n = {n} rows needs {want}")
-
-
 def _getrs_batched_args(LU, ipiv, X, fpe, early_exit):
     """Validates a device batched ExGETRS call before anything is launched (no GPU needed for that); returns the C
     arguments up to the stream.  No operand is copied."""
-    torch = _torch()
-    for name, t in (("LU", LU), ("X", X)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64:
-            raise ValueError(f"exgetrs_batched: {name} must be a float64 torch tensor")
-    if X.dim() != 2:
-        raise ValueError("exgetrs_batched: X must be 2-D (n x k, one column per right-hand side)")
-    order, batch, p, ldlu, stride = _batched_matrices("exgetrs_batched", "LU", tuple(LU.shape), LU)
-    _getrf_pivots("exgetrs_batched", ipiv, batch, p, LU)
-    n, k = int(X.shape[0]), int(X.shape[1])
-    _getrs_blocks(n, p, batch)
-    # a block that does not conform is refused, not copied: it is solved in place
-    if n > 0 and k > 0 and ((k > 1 and X.stride(1) != 1) or (n > 1 and X.stride(0) < k)):
-        raise ValueError("exgetrs_batched: X must be row-major with stride(1) == 1 and stride(0) >= k (its rows must not "
-                         "overlap; it is solved in place)")
-    fpe = _fpe_0_to_8("exgetrs_batched", fpe)
-    if LU.device != X.device:
-        raise ValueError("exgetrs_batched: LU, X must be on one device")
-    if batch > 0 and n > 0 and k > 0:
-        r0, x0 = LU.data_ptr(), X.data_ptr()
-        r1 = r0 + 8 * ((batch - 1) * stride + (p - 1) * ldlu + p)
-        x1 = x0 + 8 * ((n - 1) * _ld(X, k) + k)
-        if r0 < x1 and x0 < r1:
-            raise ValueError("exgetrs_batched: X overlaps LU (X is solved in place while LU is read)")
-    _on_gpu("exgetrs_batched", LU=LU, X=X)
+    def factors():
+        geo = _batched_matrices("exgetrs_batched", "LU", tuple(LU.shape), LU)
+        _getrf_pivots("exgetrs_batched", ipiv, geo[1], geo[2], LU)
+        return geo
+
+    (order, _, p, ldlu, stride), n, k, fpe = _batched_apply_args("exgetrs_batched", "LU", LU, X, factors, fpe)
     return (order, p, n, k, _ptr(LU), ldlu, stride, _ptr(ipiv), _ptr(X), _ld(X, max(k, 1)), fpe, int(bool(early_exit)))
 
 
@@ -1930,7 +1908,7 @@ def expotrs_batched(R, B, uplo="U", sweep="B", fpe=8, early_exit=True):  # noqa:
     B = _dense_host("expotrs_batched", "B", B, 2, " (n x k, one column per right-hand side)")
     X = np.array(B, dtype=np.float64, copy=True, order="C")
     n, k = int(X.shape[0]), int(X.shape[1])
-    _potrs_blocks(n, p, batch)
+    _batched_blocks("expotrs_batched", "R", n, p, batch)
     fpe = _fpe_0_to_8("expotrs_batched", fpe)
     _require_gpu()
     _check(load_library().exblas_expotrs_batched(u, s, p, n, k, _hptr(R), ldr, stride, _hptr(X), max(k, 1), fpe,
@@ -1967,7 +1945,7 @@ def exgetrs_batched(LU, ipiv, B, fpe=8, early_exit=True):  # noqa: N803
     B = _dense_host("exgetrs_batched", "B", B, 2, " (n x k, one column per right-hand side)")
     X = np.array(B, dtype=np.float64, copy=True, order="C")
     n, k = int(X.shape[0]), int(X.shape[1])
-    _getrs_blocks(n, p, batch)
+    _batched_blocks("exgetrs_batched", "LU", n, p, batch)
     fpe = _fpe_0_to_8("exgetrs_batched", fpe)
     _require_gpu()
     _check(load_library().exblas_exgetrs_batched(order, p, n, k, _hptr(LU), ldlu, stride, _hptr(ipiv), _hptr(X), max(k, 1),

@@ -31,7 +31,6 @@
 //     term, then the division.
 #include "../../include/exblas_hip.h"
 #include "block_common.hip.h"
-#include <atomic>
 
 namespace exb {
 namespace {
@@ -260,19 +259,6 @@ __global__ void __launch_bounds__(SP_BLOCK) k_btrsm(BtArgs A, const double *__re
     blk_store_counters(cnt, n_reg, n_fb, slots, blockIdx.x);
 }
 
-// more than 64 KiB of dynamic LDS has to be asked for, once per device and instantiation (no stream operation)
-hipError_t bt_lds_optin(int device)
-{
-    static std::atomic<unsigned long long> done{0};
-    const unsigned long long bit = 1ull << (device & 63);
-    if (done.load() & bit) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_btrsm<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BT_LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_btrsm<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BT_LDS);
-    if (e == hipSuccess) done.fetch_or(bit);
-    return e;
-}
-
 }  // namespace
 
 // fpe: 0 every output from the integer accumulator, 1 the plain solve, 2..8 the expansions (the caller refused the rest
@@ -313,7 +299,8 @@ hipError_t exbtrsm_dispatch(Ctx &c, char uplo, char transt, char diag, long long
     A.nitems = (n + (long long)SP_WAVES * rw - 1) / ((long long)SP_WAVES * rw);
     const auto [grid, per] = blk_partition(c, A.nitems);
     A.per = per;
-    hipError_t e = bt_lds_optin(c.device);
+    static std::atomic<unsigned long long> optin{0};
+    hipError_t e = blk_lds_optin(optin, c.device, BT_LDS, {(const void *)k_btrsm<true>, (const void *)k_btrsm<false>});
     if (e != hipSuccess) return e;
     long long *slots = blk_reserve_slots(c, c.btrsm_slots, grid, st, &e);
     if (!slots) return e;

@@ -711,19 +711,34 @@ static int expotrf_on(Ctx &c, char uplo, int p, double *d_g, int ldg, int *d_inf
     return (int)expotrf_dispatch(c, uplo, p, d_g, ldg, d_info, fpe, early_exit, round_mode(), st);
 }
 
-// The argument checks of the batched ExPOTRF, on host or device pointers alike, before a device is touched.  *empty:
-// p == 0 or batch == 0, which is decided before the pointers are looked at.
+// The argument checks of the two batched factorisations (ExPOTRF: flag = uplo of "LlUu", ExGETRF: flag = order of "CcRr"),
+// on host or device pointers alike, before a device is touched.  outs: the output pointers (info; ipiv and info) are all
+// there.  *empty: p == 0 or batch == 0, which is decided before the pointers are looked at.
+static int bjacobi_factor_check_args(char flag, const char *flags, int p, int max_p, int64_t batch, const double *a, int lda,
+                                     int64_t stride, bool outs, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!one_of(flag, flags) || p < 0 || batch < 0 || p > max_p || lda < (p > 1 ? p : 1) || fpe < 0)
+        return (int)hipErrorInvalidValue;
+    if (batch > 1 && stride < (int64_t)lda * p) return (int)hipErrorInvalidValue;
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = p == 0 || batch == 0;
+    if (!*empty && (!a || !outs)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
 static int potrf_batched_check_args(char uplo, int p, int64_t batch, const double *g, int ldg, int64_t stride, const int *info,
                                     int fpe, bool *empty)
 {
-    *empty = false;
-    if (!one_of(uplo, "LlUu") || p < 0 || batch < 0 || p > EXBLAS_POTRF_BATCHED_MAX_P || ldg < (p > 1 ? p : 1) || fpe < 0)
-        return (int)hipErrorInvalidValue;
-    if (batch > 1 && stride < (int64_t)ldg * p) return (int)hipErrorInvalidValue;
-    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
-    *empty = p == 0 || batch == 0;
-    if (!*empty && (!g || !info)) return (int)hipErrorInvalidValue;
-    return 0;
+    return bjacobi_factor_check_args(uplo, "LlUu", p, EXBLAS_POTRF_BATCHED_MAX_P, batch, g, ldg, stride, info != nullptr, fpe,
+                                     empty);
+}
+
+static int getrf_batched_check_args(char order, int p, int64_t batch, const double *a, int lda, int64_t stride, const int *ipiv,
+                                    const int *info, int fpe, bool *empty)
+{
+    return bjacobi_factor_check_args(order, "CcRr", p, EXBLAS_GETRF_BATCHED_MAX_P, batch, a, lda, stride, ipiv && info, fpe,
+                                     empty);
 }
 
 static int expotrf_batched_on(Ctx &c, char uplo, int p, int64_t batch, double *d_g, int ldg, int64_t stride, int *d_info,
@@ -736,21 +751,35 @@ static int expotrf_batched_on(Ctx &c, char uplo, int p, int64_t batch, double *d
     return (int)expotrf_batched_dispatch(c, uplo, p, batch, d_g, ldg, stride, d_info, fpe, early_exit, round_mode(), st);
 }
 
-// The argument checks of the batched ExPOTRS, on host or device pointers alike, before a device is touched.  *empty:
-// n == 0 or k == 0, which is decided before the pointers are looked at.
+// The argument checks of the two batched applies (ExPOTRS: flags_ok = uplo of "LlUu" and sweep of "12Bb", ExGETRS: order of
+// "CcRr"), on host or device pointers alike, before a device is touched.  f: the factors; ins: every input pointer beside
+// them (none; ipiv) is there.  *empty: n == 0 or k == 0, which is decided before the pointers are looked at.
+static int bjacobi_apply_check_args(bool flags_ok, int p, int max_p, int64_t n, int k, const double *f, int ldf, int64_t stride,
+                                    bool ins, const double *x, int64_t ldx, int fpe, bool *empty)
+{
+    *empty = false;
+    if (!flags_ok) return (int)hipErrorInvalidValue;
+    if (n < 0 || k < 0 || p < 0 || p > max_p || (p < 1 && n > 0) || fpe < 0 || ldx < k) return (int)hipErrorInvalidValue;
+    if (ldf < (p > 1 ? p : 1)) return (int)hipErrorInvalidValue;
+    if (p > 0 && n > p && stride < (int64_t)ldf * p) return (int)hipErrorInvalidValue;   // more than one block
+    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
+    *empty = n == 0 || k == 0;
+    if (!*empty && (!f || !ins || !x)) return (int)hipErrorInvalidValue;
+    return 0;
+}
+
 static int potrs_batched_check_args(char uplo, char sweep, int p, int64_t n, int k, const double *r, int ldr, int64_t stride,
                                     const double *x, int64_t ldx, int fpe, bool *empty)
 {
-    *empty = false;
-    if (!one_of(uplo, "LlUu") || !one_of(sweep, "12Bb")) return (int)hipErrorInvalidValue;
-    if (n < 0 || k < 0 || p < 0 || p > EXBLAS_POTRF_BATCHED_MAX_P || (p < 1 && n > 0) || fpe < 0 || ldx < k)
-        return (int)hipErrorInvalidValue;
-    if (ldr < (p > 1 ? p : 1)) return (int)hipErrorInvalidValue;
-    if (p > 0 && n > p && stride < (int64_t)ldr * p) return (int)hipErrorInvalidValue;   // more than one block
-    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
-    *empty = n == 0 || k == 0;
-    if (!*empty && (!r || !x)) return (int)hipErrorInvalidValue;
-    return 0;
+    return bjacobi_apply_check_args(one_of(uplo, "LlUu") && one_of(sweep, "12Bb"), p, EXBLAS_POTRF_BATCHED_MAX_P, n, k, r, ldr,
+                                    stride, true, x, ldx, fpe, empty);
+}
+
+static int getrs_batched_check_args(char order, int p, int64_t n, int k, const double *lu, int ldlu, int64_t stride,
+                                    const int *ipiv, const double *x, int64_t ldx, int fpe, bool *empty)
+{
+    return bjacobi_apply_check_args(one_of(order, "CcRr"), p, EXBLAS_GETRF_BATCHED_MAX_P, n, k, lu, ldlu, stride,
+                                    ipiv != nullptr, x, ldx, fpe, empty);
 }
 
 static int expotrs_batched_on(Ctx &c, char uplo, char sweep, int p, int64_t n, int k, const double *d_r, int ldr,
@@ -764,21 +793,6 @@ static int expotrs_batched_on(Ctx &c, char uplo, char sweep, int p, int64_t n, i
                                          st);
 }
 
-// The argument checks of the batched ExGETRF, on host or device pointers alike, before a device is touched.  *empty:
-// p == 0 or batch == 0, which is decided before the pointers are looked at.
-static int getrf_batched_check_args(char order, int p, int64_t batch, const double *a, int lda, int64_t stride, const int *ipiv,
-                                    const int *info, int fpe, bool *empty)
-{
-    *empty = false;
-    if (!one_of(order, "CcRr") || p < 0 || batch < 0 || p > EXBLAS_GETRF_BATCHED_MAX_P || lda < (p > 1 ? p : 1) || fpe < 0)
-        return (int)hipErrorInvalidValue;
-    if (batch > 1 && stride < (int64_t)lda * p) return (int)hipErrorInvalidValue;
-    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
-    *empty = p == 0 || batch == 0;
-    if (!*empty && (!a || !ipiv || !info)) return (int)hipErrorInvalidValue;
-    return 0;
-}
-
 static int exgetrf_batched_on(Ctx &c, char order, int p, int64_t batch, double *d_a, int lda, int64_t stride, int *d_ipiv,
                               int *d_info, int fpe, int early_exit, hipStream_t st)
 {
@@ -788,23 +802,6 @@ static int exgetrf_batched_on(Ctx &c, char order, int p, int64_t batch, double *
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exgetrf_batched_dispatch(c, order, p, batch, d_a, lda, stride, d_ipiv, d_info, fpe, early_exit, round_mode(),
                                          st);
-}
-
-// The argument checks of the batched ExGETRS, on host or device pointers alike, before a device is touched.  *empty:
-// n == 0 or k == 0, which is decided before the pointers are looked at.
-static int getrs_batched_check_args(char order, int p, int64_t n, int k, const double *lu, int ldlu, int64_t stride,
-                                    const int *ipiv, const double *x, int64_t ldx, int fpe, bool *empty)
-{
-    *empty = false;
-    if (!one_of(order, "CcRr")) return (int)hipErrorInvalidValue;
-    if (n < 0 || k < 0 || p < 0 || p > EXBLAS_GETRF_BATCHED_MAX_P || (p < 1 && n > 0) || fpe < 0 || ldx < k)
-        return (int)hipErrorInvalidValue;
-    if (ldlu < (p > 1 ? p : 1)) return (int)hipErrorInvalidValue;
-    if (p > 0 && n > p && stride < (int64_t)ldlu * p) return (int)hipErrorInvalidValue;   // more than one block
-    if (fpe >= 9) return EXBLAS_UNSUPPORTED;
-    *empty = n == 0 || k == 0;
-    if (!*empty && (!lu || !ipiv || !x)) return (int)hipErrorInvalidValue;
-    return 0;
 }
 
 static int exgetrs_batched_on(Ctx &c, char order, int p, int64_t n, int k, const double *d_lu, int ldlu, int64_t stride,

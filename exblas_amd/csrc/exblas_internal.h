@@ -272,16 +272,14 @@ hipError_t expotrf_dispatch(Ctx &c, char uplo, int p, double *g, int ldg, int *i
 hipError_t expotrf_batched_dispatch(Ctx &c, char uplo, int p, long long batch, double *g, int ldg, long long stride, int *info,
                                     int fpe, int early_exit, int round_mode, hipStream_t st);
 
-// potrs_batched.hip
-hipError_t expotrs_batched_dispatch(Ctx &c, char uplo, char sweep, int p, long long n, int k, const double *r, int ldr,
-                                    long long stride, double *x, long long ldx, int fpe, int early_exit, int round_mode,
-                                    hipStream_t st);
-
 // getrf_batched.hip
 hipError_t exgetrf_batched_dispatch(Ctx &c, char order, int p, long long batch, double *a, int lda, long long stride, int *ipiv,
                                     int *info, int fpe, int early_exit, int round_mode, hipStream_t st);
 
-// getrs_batched.hip
+// bjacobi_apply.hip: the batched ExPOTRS and the batched ExGETRS, one kernel
+hipError_t expotrs_batched_dispatch(Ctx &c, char uplo, char sweep, int p, long long n, int k, const double *r, int ldr,
+                                    long long stride, double *x, long long ldx, int fpe, int early_exit, int round_mode,
+                                    hipStream_t st);
 hipError_t exgetrs_batched_dispatch(Ctx &c, char order, int p, long long n, int k, const double *lu, int ldlu, long long stride,
                                     const int *ipiv, double *x, long long ldx, int fpe, int early_exit, int round_mode,
                                     hipStream_t st);

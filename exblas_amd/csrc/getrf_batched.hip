@@ -24,8 +24,7 @@
 //   * A group that breaks down stores its candidates, notes j + 1 and idles to the end of the wave's chain; so does a group
 //     past the end of the batch.
 //   * fpe == 1: s = w, then s -= l * u for k ascending, in fp64.
-#include <atomic>
-
+// Host side: the argument struct and the plan are BjfArgs and bjf_plan of block_common.hip.h, shared with potrf_batched.hip.
 #include "../../include/exblas_hip.h"
 #include "block_common.hip.h"
 
@@ -33,12 +32,6 @@ namespace exb {
 namespace {
 
 constexpr int GF_U = 4;   // earlier steps per pass of the inner loop
-constexpr size_t GF_LDS = (size_t)SP_WAVES * 64 * 65 * sizeof(double);   // four staged matrices of p = 64
-
-struct GfArgs {
-    long long stride, batch, nitems, per;   // nitems workgroup items, `per` of them to a workgroup
-    int p, lda, rowmajor, lgpw, G, wpi, tsz, force, round_mode;   // wpi wave items per workgroup item, tsz doubles per wave
-};
 
 // What no lane could certify: Round(w_rc - sum_{k<j} l_rk u_kc) of the staged matrix M through the wave's accumulator.
 // (r, c) still holds w_rc.  Wave-uniform; every lane gets the value.
@@ -53,14 +46,14 @@ __device__ double gf_resolve(const double *M, int pitch, int j, int r, int c, in
 
 // the wave's G matrices between global memory and LDS, along the unit stride of `order`
 template <bool STORE>
-__device__ __forceinline__ void gf_move(const GfArgs &A, double *a, double *mat, long long m0)
+__device__ __forceinline__ void gf_move(const BjfArgs &A, double *a, double *mat, long long m0)
 {
     const int lane = threadIdx.x & 63, p = A.p, pp = p * p, pitch = p | 1, msz = p * pitch;
     for (int x = lane; x < A.G * pp; x += 64) {
         const int gg = x / pp, q = x - gg * pp, hi = q / p, lo = q - hi * p;
-        const int r = A.rowmajor ? hi : lo, c = A.rowmajor ? lo : hi;
+        const int r = A.hirow ? hi : lo, c = A.hirow ? lo : hi;   // hirow: row-major
         if (m0 + gg >= A.batch) continue;
-        double *at = a + (m0 + gg) * A.stride + (long long)hi * A.lda + lo;
+        double *at = a + (m0 + gg) * A.stride + (long long)hi * A.ld + lo;
         if constexpr (STORE) *at = mat[gg * msz + r * pitch + c];
         else mat[gg * msz + r * pitch + c] = *at;
     }
@@ -75,7 +68,7 @@ __device__ __forceinline__ unsigned long long gf_rank(bool act, double c)
 }
 
 template <bool PLAIN>
-__global__ void __launch_bounds__(SP_BLOCK) k_getrf_batched(GfArgs A, double *a, int *ipiv, int *info, long long *slots)
+__global__ void __launch_bounds__(SP_BLOCK) k_getrf_batched(BjfArgs A, double *a, int *ipiv, int *info, long long *slots)
 {
     extern __shared__ double gf_lds[];   // SP_WAVES x tsz: the waves' matrices
     __shared__ long long acc[SP_WAVES][NL];
@@ -194,19 +187,6 @@ __global__ void __launch_bounds__(SP_BLOCK) k_getrf_batched(GfArgs A, double *a,
     blk_store_counters(cnt, n_reg, n_fb, slots, blockIdx.x);
 }
 
-// more than 64 KiB of dynamic LDS has to be asked for, once per device and instantiation (no stream operation)
-hipError_t gf_lds_optin(int device)
-{
-    static std::atomic<unsigned long long> done{0};
-    const unsigned long long bit = 1ull << (device & 63);
-    if (done.load() & bit) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_getrf_batched<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_getrf_batched<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GF_LDS);
-    if (e == hipSuccess) done.fetch_or(bit);
-    return e;
-}
-
 }  // namespace
 
 // fpe: 0 every output from the integer accumulator, 1 the plain factorisation, 2..8 the expansions (the caller refused the
@@ -217,29 +197,12 @@ hipError_t exgetrf_batched_dispatch(Ctx &c, char order, int p, long long batch, 
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
     c.getrf_batched_slots = SlotInfo();
     if (p == 0 || batch == 0) return hipSuccess;
-    const int path = c.getrf_batched_path;
-    GfArgs A;
-    A.p = p, A.lda = lda, A.stride = stride, A.batch = batch;
-    A.rowmajor = (order == 'R' || order == 'r') ? 1 : 0;
-    A.lgpw = 0;
-    while ((1 << A.lgpw) < p) ++A.lgpw;
-    A.G = (path == 2 || path == 3) ? 1 : 64 >> A.lgpw;
-    const int msz = p * (p | 1);
-    while (A.G > 1 && (size_t)SP_WAVES * A.G * msz * sizeof(double) > GF_LDS) A.G >>= 1;   // the wave's share of LDS
-    A.wpi = path == 3 ? 1 : SP_WAVES;
-    A.tsz = A.G * msz;
-    const StRule rule = st_rule(fpe, path, round_mode);
-    A.force = rule.force_fb, A.round_mode = rule.round_mode;
-    const long long per_item = (long long)A.G * A.wpi;
-    A.nitems = (batch + per_item - 1) / per_item;
-    BlkPartition P = blk_partition(c, A.nitems);
-    if (path == 3) {   // a handful of workgroups: each walks several items already at a small batch
-        const long long most = min(5ll, A.nitems);
-        P.per = (A.nitems + most - 1) / most;
-        P.grid = (int)((A.nitems + P.per - 1) / P.per);
-    }
-    A.per = P.per;
-    hipError_t e = gf_lds_optin(c.device);
+    BjfArgs A;
+    const bool rowmajor = order == 'R' || order == 'r';
+    const BlkPartition P = bjf_plan(c, A, c.getrf_batched_path, p, batch, lda, stride, rowmajor, fpe, round_mode);
+    static std::atomic<unsigned long long> optin{0};
+    hipError_t e = blk_lds_optin(optin, c.device, BJF_LDS,
+                                 {(const void *)k_getrf_batched<true>, (const void *)k_getrf_batched<false>});
     if (e != hipSuccess) return e;
     long long *slots = blk_reserve_slots(c, c.getrf_batched_slots, P.grid, st, &e);
     if (!slots) return e;

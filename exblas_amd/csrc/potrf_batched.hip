@@ -21,8 +21,7 @@
 //   * The fall-back is wave-uniform: one output at a time through the wave's one accumulator (blk_resolve), over the ballot
 //     across all groups; the radicands are settled before the rest of their rows is counted.
 //   * fpe == 1: s = g_ji, then s -= r_kj * r_ki for k ascending, in fp64.
-#include <atomic>
-
+// Host side: the argument struct and the plan are BjfArgs and bjf_plan of block_common.hip.h, shared with getrf_batched.hip.
 #include "../../include/exblas_hip.h"
 #include "block_common.hip.h"
 
@@ -30,12 +29,6 @@ namespace exb {
 namespace {
 
 constexpr int PB_U = 4;   // earlier rows per step of the inner loop
-constexpr size_t PB_LDS = (size_t)SP_WAVES * 64 * 65 * sizeof(double);   // four staged triangles of p = 64
-
-struct PbArgs {
-    long long stride, batch, nitems, per;   // nitems workgroup items, `per` of them to a workgroup
-    int p, ldg, lower, lgpw, G, wpi, tsz, force, round_mode;   // wpi wave items per workgroup item, tsz doubles per wave
-};
 
 // What no lane could certify: Round(g_ji - sum_{k<j} r_kj r_ki) of the staged matrix M through the wave's accumulator.
 // (j, i) still holds g_ji.  Wave-uniform; every lane gets the value.
@@ -51,14 +44,14 @@ __device__ double pb_resolve(const double *M, int pitch, int j, int i, int round
 // the wave's G triangles between global memory and LDS, along the unit stride of G.  STORE: only what was fixed goes back
 // (the rows before a breakdown and its pivot)
 template <bool STORE>
-__device__ __forceinline__ void pb_move(const PbArgs &A, double *g, double *tri, long long m0, const int *stop)
+__device__ __forceinline__ void pb_move(const BjfArgs &A, double *g, double *tri, long long m0, const int *stop)
 {
     const int lane = threadIdx.x & 63, p = A.p, pp = p * p, pitch = p | 1, msz = p * pitch;
     for (int x = lane; x < A.G * pp; x += 64) {
         const int gg = x / pp, r = x - gg * pp, a = r / p, b = r - a * p;
-        const int k = A.lower ? a : b, c = A.lower ? b : a;
+        const int k = A.hirow ? a : b, c = A.hirow ? b : a;   // hirow: 'L'
         if (m0 + gg >= A.batch || k > c) continue;
-        double *at = g + (m0 + gg) * A.stride + (long long)a * A.ldg + b;
+        double *at = g + (m0 + gg) * A.stride + (long long)a * A.ld + b;
         if constexpr (STORE) {
             const int st = stop[gg], nfix = st ? st - 1 : p;
             if (k < nfix || (k == c && k == nfix)) *at = tri[gg * msz + k * pitch + c];
@@ -69,7 +62,7 @@ __device__ __forceinline__ void pb_move(const PbArgs &A, double *g, double *tri,
 }
 
 template <bool PLAIN>
-__global__ void __launch_bounds__(SP_BLOCK) k_potrf_batched(PbArgs A, double *g, int *info, long long *slots)
+__global__ void __launch_bounds__(SP_BLOCK) k_potrf_batched(BjfArgs A, double *g, int *info, long long *slots)
 {
     extern __shared__ double pb_lds[];   // SP_WAVES x tsz: the waves' triangles
     __shared__ long long acc[SP_WAVES][NL];
@@ -174,19 +167,6 @@ __global__ void __launch_bounds__(SP_BLOCK) k_potrf_batched(PbArgs A, double *g,
     blk_store_counters(cnt, n_reg, n_fb, slots, blockIdx.x);
 }
 
-// more than 64 KiB of dynamic LDS has to be asked for, once per device and instantiation (no stream operation)
-hipError_t pb_lds_optin(int device)
-{
-    static std::atomic<unsigned long long> done{0};
-    const unsigned long long bit = 1ull << (device & 63);
-    if (done.load() & bit) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *)k_potrf_batched<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void *)k_potrf_batched<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PB_LDS);
-    if (e == hipSuccess) done.fetch_or(bit);
-    return e;
-}
-
 }  // namespace
 
 // fpe: 0 every output from the integer accumulator, 1 the plain factorisation, 2..8 the expansions (the caller refused the
@@ -197,29 +177,12 @@ hipError_t expotrf_batched_dispatch(Ctx &c, char uplo, int p, long long batch, d
     (void)early_exit;   // every (fpe >= 2, early_exit) gives the same bits: one expansion size serves them all
     c.potrf_batched_slots = SlotInfo();
     if (p == 0 || batch == 0) return hipSuccess;
-    const int path = c.potrf_batched_path;
-    PbArgs A;
-    A.p = p, A.ldg = ldg, A.stride = stride, A.batch = batch;
-    A.lower = (uplo == 'L' || uplo == 'l') ? 1 : 0;
-    A.lgpw = 0;
-    while ((1 << A.lgpw) < p) ++A.lgpw;
-    A.G = (path == 2 || path == 3) ? 1 : 64 >> A.lgpw;
-    const int msz = p * (p | 1);
-    while (A.G > 1 && (size_t)SP_WAVES * A.G * msz * sizeof(double) > PB_LDS) A.G >>= 1;   // the wave's share of LDS
-    A.wpi = path == 3 ? 1 : SP_WAVES;
-    A.tsz = A.G * msz;
-    const StRule rule = st_rule(fpe, path, round_mode);
-    A.force = rule.force_fb, A.round_mode = rule.round_mode;
-    const long long per_item = (long long)A.G * A.wpi;
-    A.nitems = (batch + per_item - 1) / per_item;
-    BlkPartition P = blk_partition(c, A.nitems);
-    if (path == 3) {   // a handful of workgroups: each walks several items already at a small batch
-        const long long most = min(5ll, A.nitems);
-        P.per = (A.nitems + most - 1) / most;
-        P.grid = (int)((A.nitems + P.per - 1) / P.per);
-    }
-    A.per = P.per;
-    hipError_t e = pb_lds_optin(c.device);
+    BjfArgs A;
+    const bool lower = uplo == 'L' || uplo == 'l';
+    const BlkPartition P = bjf_plan(c, A, c.potrf_batched_path, p, batch, ldg, stride, lower, fpe, round_mode);
+    static std::atomic<unsigned long long> optin{0};
+    hipError_t e = blk_lds_optin(optin, c.device, BJF_LDS,
+                                 {(const void *)k_potrf_batched<true>, (const void *)k_potrf_batched<false>});
     if (e != hipSuccess) return e;
     long long *slots = blk_reserve_slots(c, c.potrf_batched_slots, P.grid, st, &e);
     if (!slots) return e;
