@@ -3,7 +3,7 @@
 //
 // blas3_i8.hip writes every entry as sa (sb) base-256 digits and contracts all sa*sb digit pairs: 64 int8 products
 // per element pair for 53-bit mantissas with 10 binades of spread.  Here the fixed-point integers X_il = A'_il / 2^ua_i
-// and Y_lj = B_lj / 2^ub_j (|X| < 2^na, |Y| < 2^nb, exact: gemm_scan.hip.h) are reduced modulo L pairwise coprime
+// and Y_lj = B_lj / 2^ub_j (|X| < 2^na, |Y| < 2^nb, exact: gemm_scan in blas3.hip) are reduced modulo L pairwise coprime
 // moduli p_0 = 256, 255, 253, 251, 247, ... (<= 256, so every symmetric residue is an int8):
 //
 //   1. residues (k_crt_residues): x mod p_t for t < L, one int8 plane per modulus, same tile-major layout as the digit
@@ -569,13 +569,13 @@ __global__ void __launch_bounds__(256, 1) k_gemm_crt(int n, int row_end, int ty0
         constexpr int h = decltype(hc)::value, r = decltype(rc)::value;
         constexpr int rstage = h == 0 ? r : (r + 1) % 3, rks = h == 0 ? 1 : 0;
         constexpr int wset = (r + 2) % 3, lset = (r + 1) % 3;
-        static_for_i8<0, 8>([&](auto ic) {
+        static_for<0, 8>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (i < 4) nb[i] = lds[rstage][bbase + (i >> 1) * 256 + (i & 1) * 128 + fo[rks]];
             else na[i - 4] = lds[rstage][abase + ((i - 4) >> 1) * 256 + ((i - 4) & 1) * 128 + fo[rks]];
             if constexpr (i & 1) lwrite(std::integral_constant<int, wset>{}, std::integral_constant<int, h * 4 + i / 2>{});
             else gload(std::integral_constant<int, lset>{}, std::integral_constant<int, h * 4 + i / 2>{}, kc + 4);
-            static_for_i8<2 * i, 2 * i + 2>([&](auto mc) {
+            static_for<2 * i, 2 * i + 2>([&](auto mc) {
                 constexpr int mm = decltype(mc)::value, pu = mm >> 2, qu = mm & 3;
                 acc[mm] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ca[pu], cb[qu], acc[mm], 0, 0, 0);
             });
@@ -592,12 +592,12 @@ __global__ void __launch_bounds__(256, 1) k_gemm_crt(int n, int row_end, int ty0
         khalf(std::integral_constant<int, 1>{}, rc, fa1, fb1, fa0, fb0, kc);
     };
     // prologue: chunks 0 and 1 through registers into stages 0 and 1, chunks 2 and 3 into sets 2 and 0
-    static_for_i8<0, 8>([&](auto jc) { gload(std::integral_constant<int, 0>{}, jc, kc0); });
-    static_for_i8<0, 8>([&](auto jc) { gload(std::integral_constant<int, 1>{}, jc, kc0 + 1); });
-    static_for_i8<0, 8>([&](auto jc) { lwrite(std::integral_constant<int, 0>{}, jc); });
-    static_for_i8<0, 8>([&](auto jc) { lwrite(std::integral_constant<int, 1>{}, jc); });
-    static_for_i8<0, 8>([&](auto jc) { gload(std::integral_constant<int, 2>{}, jc, kc0 + 2); });
-    static_for_i8<0, 8>([&](auto jc) { gload(std::integral_constant<int, 0>{}, jc, kc0 + 3); });
+    static_for<0, 8>([&](auto jc) { gload(std::integral_constant<int, 0>{}, jc, kc0); });
+    static_for<0, 8>([&](auto jc) { gload(std::integral_constant<int, 1>{}, jc, kc0 + 1); });
+    static_for<0, 8>([&](auto jc) { lwrite(std::integral_constant<int, 0>{}, jc); });
+    static_for<0, 8>([&](auto jc) { lwrite(std::integral_constant<int, 1>{}, jc); });
+    static_for<0, 8>([&](auto jc) { gload(std::integral_constant<int, 2>{}, jc, kc0 + 2); });
+    static_for<0, 8>([&](auto jc) { gload(std::integral_constant<int, 0>{}, jc, kc0 + 3); });
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     fload(0, 0, fa0, fb0);
     int kc = kc0;
@@ -748,10 +748,8 @@ static int crt_chunk_rows(int m) { return m > 3072 ? 2048 : ((m + 255) / 256) * 
 
 hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
                               const double *b, int ldb, double beta, double *cmat, int ldc, int round_mode,
-                              hipStream_t st, I8Plan *plan)
+                              hipStream_t st, GemmPlan *plan)
 {
-    plan->ok = false;
-    if (k <= 0 || m <= 0 || n <= 0) return hipSuccess;
     const int ta = (transa == 'T' || transa == 't'), tb = (transb == 'T' || transb == 't');
     const int gx = (n + I8_T - 1) / I8_T, KC = (k + I8_T - 1) / I8_T;
     int lcap = c.gemm_max_moduli > 0 ? c.gemm_max_moduli : CRT_LMAX;
@@ -760,19 +758,15 @@ hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, in
     while ((1ll << clog2k) < (long long)k) ++clog2k;
     const int chunk = crt_chunk_rows(m), ctiles = chunk / I8_T, cm4 = chunk / 4;
     const size_t plane_a = (size_t)ctiles * KC * I8_TILE, plane_b = (size_t)gx * KC * I8_TILE;
-    size_t off = 0, o_info = 0, o_e = 0, o_pa = 0, o_pb = 0, o_r = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    auto layout = [&](int l) {
-        off = 0;
-        o_info = take(sizeof(int) * INFO_WORDS);
-        o_e = take(sizeof(int) * 2 * ((size_t)m + n));
-        o_pb = take(plane_b * l);
-        o_pa = take(plane_a * l);
-        o_r = take((size_t)l * cm4 * n * sizeof(unsigned));
+    size_t o_info = 0, o_e = 0, o_pa = 0, o_pb = 0, o_r = 0;
+    auto layout = [&](int l) {   // bytes of the workspace for l moduli
+        WsCarve ws;
+        o_info = ws.take(sizeof(int) * INFO_WORDS);
+        o_e = ws.take(sizeof(int) * 2 * ((size_t)m + n));
+        o_pb = ws.take(plane_b * l);
+        o_pa = ws.take(plane_a * l);
+        o_r = ws.take((size_t)l * cm4 * n * sizeof(unsigned));
+        return ws.off;
     };
     // Out of memory: retry with fewer moduli (24 cover 53-bit mantissas with 30 binades of spread inside a row at
     // k = 8192, 18 what fpuniform(10) needs); data that needs more than were reserved takes the scalar kernel, decided
@@ -783,30 +777,16 @@ hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, in
     for (int t = 0; t < 4 && !base; ++t) {
         if (t > 0 && tries[t] >= lcap) continue;
         if (t > 0) lcap = tries[t];
-        layout(lcap);
-        base = (char *)workspace(c, off, st, &e);
+        base = (char *)workspace(c, layout(lcap), st, &e);
         if (!base && e == hipErrorStreamCaptureUnsupported) return e;  // the caller must reserve before capturing
     }
     c.gemm_ws_moduli = base ? lcap : 0;
     if (!base) return hipSuccess;  // out of memory even for 12 moduli: the caller falls back (digit path, scalar kernel)
     int *info = (int *)(base + o_info);
-    int *EA = (int *)(base + o_e), *EB = EA + m, *LA = EB + n, *LB = LA + m;
+    int *EA = (int *)(base + o_e), *EB = EA + m;
     signed char *PA = (signed char *)(base + o_pa), *PB = (signed char *)(base + o_pb);
 
-    hipLaunchKernelGGL(k_scan_init, dim3((m + n + 255) / 256), dim3(256), 0, st, m + n, EA, LA, info);
-    const int ysplit = k >= 2048 ? 32 : (k >= 256 ? 8 : 1);
-    if (!ta)
-        hipLaunchKernelGGL(k_scan_contig, dim3(m), dim3(256), 0, st, a, (long long)lda, m, k, alpha, EA, LA, info);
-    else
-        hipLaunchKernelGGL(k_scan_strided, dim3((m + 255) / 256, ysplit), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
-                           EA, LA, info);
-    if (!tb)
-        hipLaunchKernelGGL(k_scan_strided, dim3((n + 255) / 256, ysplit), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
-                           EB, LB, info);
-    else
-        hipLaunchKernelGGL(k_scan_contig, dim3(n), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0, EB, LB, info);
-    hipLaunchKernelGGL(k_scan_finish, dim3((m + 255) / 256), dim3(256), 0, st, m, EA, LA, info, INFO_NEED_A);
-    hipLaunchKernelGGL(k_scan_finish, dim3((n + 255) / 256), dim3(256), 0, st, n, EB, LB, info, INFO_NEED_B);
+    gemm_scan(st, ta, tb, m, n, k, alpha, a, lda, b, ldb, info, EA);
     hipLaunchKernelGGL(k_crt_decide, dim3(1), dim3(64), 0, st, info, clog2k, lcap);
 
     // B's residues once for all row chunks; A's per chunk (exgemm_crt_rows)
@@ -816,55 +796,55 @@ hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, in
     else
         hipLaunchKernelGGL((k_crt_residues<true>), dim3(KC, gx), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0, EB, info,
                            1, PB, plane_b, 0);
-    plan->ok = true;
-    plan->crt = true;
+    plan->path = PATH_CRT;
     plan->m = m; plan->n = n; plan->KC = KC;
     plan->info = info; plan->EA = EA; plan->EB = EB; plan->PA = PA; plan->PB = PB;
-    plan->R = (unsigned *)(base + o_r);
-    plan->plane_a = plane_a; plan->plane_b = plane_b; plan->lcap = lcap; plan->m4 = cm4;
-    plan->chunk_rows = chunk; plan->a = a; plan->lda = lda; plan->alpha = alpha; plan->ta = ta; plan->k = k;
-    plan->num_cu = c.num_cu;
     plan->beta = beta; plan->c = cmat; plan->ldc = ldc; plan->round_mode = round_mode;
-    c.gemm_info_dev = info;
+    auto &q = plan->crt;
+    q.R = (unsigned *)(base + o_r);
+    q.plane_a = plane_a; q.plane_b = plane_b; q.lcap = lcap; q.m4 = cm4;
+    q.chunk_rows = chunk; q.a = a; q.lda = lda; q.alpha = alpha; q.ta = ta; q.k = k;
+    q.num_cu = c.num_cu;
     return hipGetLastError();
 }
 
-// rows [row0, row1) of C, row0 a multiple of 64; internally in chunks of plan.chunk_rows rows
-hipError_t exgemm_crt_rows(const I8Plan &p, int row0, int row1, hipStream_t st)
+// rows [row0, row1) of C, row0 a multiple of 64; internally in chunks of plan.crt.chunk_rows rows
+hipError_t exgemm_crt_rows(const GemmPlan &p, int row0, int row1, hipStream_t st)
 {
+    const auto &q = p.crt;
     const int gx = (p.n + I8_T - 1) / I8_T, bx_cnt = (gx + 3) / 4;
-    for (int c0 = row0; c0 < row1; c0 += p.chunk_rows) {
-        const int c1 = min(row1, c0 + p.chunk_rows);
+    for (int c0 = row0; c0 < row1; c0 += q.chunk_rows) {
+        const int c1 = min(row1, c0 + q.chunk_rows);
         const int ty0 = c0 / I8_T, ty_cnt = (c1 - c0 + I8_T - 1) / I8_T, by_cnt = (ty_cnt + 3) / 4;
         // residues of this chunk's rows of A' = fl(alpha * A)
-        if (!p.ta)
-            hipLaunchKernelGGL((k_crt_residues<true>), dim3(p.KC, ty_cnt), dim3(256), 0, st, p.a, (long long)p.lda, p.m, p.k,
-                               p.alpha, p.EA, p.info, 0, p.PA, p.plane_a, ty0);
+        if (!q.ta)
+            hipLaunchKernelGGL((k_crt_residues<true>), dim3(p.KC, ty_cnt), dim3(256), 0, st, q.a, (long long)q.lda, p.m, q.k,
+                               q.alpha, p.EA, p.info, 0, p.PA, q.plane_a, ty0);
         else
-            hipLaunchKernelGGL((k_crt_residues<false>), dim3(ty_cnt, p.KC), dim3(256), 0, st, p.a, (long long)p.lda, p.m,
-                               p.k, p.alpha, p.EA, p.info, 0, p.PA, p.plane_a, ty0);
+            hipLaunchKernelGGL((k_crt_residues<false>), dim3(ty_cnt, p.KC), dim3(256), 0, st, q.a, (long long)q.lda, p.m,
+                               q.k, q.alpha, p.EA, p.info, 0, p.PA, q.plane_a, ty0);
         // A few moduli per launch.  The workgroups of an XCD share their A / B tile streams through its L2 only while
         // they run in step; they start in step at the beginning of a launch and drift apart afterwards: about 12 rounds
         // of one workgroup per CU per launch (8192^3, whole-matrix launches: 15 GB through the fabric per call with 12
         // rounds, 30.5 GB with 72).  Launches for moduli the data does not need exit at once.
         const long long tiles = (long long)by_cnt * bx_cnt;
-        const int per = (int)max(1ll, min((long long)p.lcap, (12ll * p.num_cu) / max(1ll, tiles)));
+        const int per = (int)max(1ll, min((long long)q.lcap, (12ll * q.num_cu) / max(1ll, tiles)));
         for (int kc0 = 0; kc0 < p.KC; kc0 += CRT_KPASS)
-            for (int mod0 = 0; mod0 < p.lcap; mod0 += per) {
-                const int nm = min(per, p.lcap - mod0);
+            for (int mod0 = 0; mod0 < q.lcap; mod0 += per) {
+                const int nm = min(per, q.lcap - mod0);
                 hipLaunchKernelGGL(k_gemm_crt, dim3((unsigned)(nm * by_cnt * bx_cnt)), dim3(256), 0, st, p.n, c1, ty0, ty_cnt,
-                                   gx, p.KC, kc0, min(p.KC, kc0 + CRT_KPASS), p.PA, p.PB, p.plane_a, p.plane_b, p.info,
-                                   p.R, p.m4, mod0);
+                                   gx, p.KC, kc0, min(p.KC, kc0 + CRT_KPASS), p.PA, p.PB, q.plane_a, q.plane_b, p.info,
+                                   q.R, q.m4, mod0);
             }
         const long long groups = (c1 - c0 + 3) / 4;
 #define CRT_FIN(NLB, ALL)                                                                                                \
     do {                                                                                                                 \
         if (p.round_mode)                                                                                                \
             hipLaunchKernelGGL((k_crt_finish<NLB, 1>), dim3((unsigned)((groups * p.n + 255) / 256)), dim3(256), 0, st, c0, \
-                               c1, p.n, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, p.R, p.m4, ALL);              \
+                               c1, p.n, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, q.R, q.m4, ALL);              \
         else                                                                                                             \
             hipLaunchKernelGGL((k_crt_finish<NLB, 0>), dim3((unsigned)((groups * p.n + 255) / 256)), dim3(256), 0, st, c0, \
-                               c1, p.n, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, p.R, p.m4, ALL);              \
+                               c1, p.n, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, q.R, q.m4, ALL);              \
     } while (0)
         if (groups * p.n < (1 << 18)) {
             CRT_FIN(CRT_NL24, 1);  // small products are launch-bound: one kernel (12 limbs) for every width

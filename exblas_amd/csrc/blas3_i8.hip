@@ -6,9 +6,9 @@
 // but the O(mnk) work runs on v_mfma_i32_32x32x32_i8 (5 Pop/s dense on MI355X, 64x the fp64 matrix rate) and only the
 // O(mn) carry-propagate + round touches a long accumulator:
 //
-//   1. scan (gemm_scan.hip.h): per row i of A' = fl(alpha*A) a scale ea_i with |A'_il| < 2^ea_i and the lowest set bit;
-//      likewise per column j of B.  k_i8_decide turns the widest span into slice counts sa, sb ON THE DEVICE.
-//   2. slice ONCE (k_i8_slice_*): every entry is the integer X = x / 2^ua_i (ua_i = ea_i - 8*sa + 2), |X| < 2^(8sa-2),
+//   1. scan (gemm_scan, blas3.hip): per row i of A' = fl(alpha*A) a scale ea_i with |A'_il| < 2^ea_i and the lowest set
+//      bit; likewise per column j of B.  k_i8_decide turns the widest span into slice counts sa, sb ON THE DEVICE.
+//   2. slice ONCE (k_i8_slice): every entry is the integer X = x / 2^ua_i (ua_i = ea_i - 8*sa + 2), |X| < 2^(8sa-2),
 //      written as sa balanced base-256 digits d_t in [-128, 127], X = sum_t d_t 256^t -- integer shifts only, no
 //      rounding anywhere.  Digit t of all entries forms an int8 "plane".  Planes are stored tile-major
 //      ([64-row tile][64-byte k chunk][plane][4 KiB]) so that the GEMM kernel's global->LDS traffic is linear 4 KiB
@@ -95,58 +95,26 @@ __device__ __forceinline__ void digits(I128 X, int s, signed char (&d)[S])
     }
 }
 
-// Source vectors CONTIGUOUS along k (A for 'N', B for 'T'): element (v, l) at src[v*ld + l].
-// One workgroup per (64-vector tile, 64-k chunk); thread = (vector tid/4, 16 consecutive k).
-template <int S>
-__global__ void __launch_bounds__(256) k_i8_slice_contig(const double *__restrict__ src, long long ld, int nvec, int len,
-                                                         double scale, const int *__restrict__ E,
-                                                         const int *__restrict__ info, int which,
-                                                         signed char *__restrict__ planes)
+// One workgroup per (64-vector tile, 64-k chunk).  CONTIG: source vectors contiguous along k (A for 'N', B for 'T'),
+// element (v, l) at src[v*ld + l], thread = (vector tid/4, 16 consecutive k).  Otherwise strided along k (A for 'T', B
+// for 'N'), element (v, l) at src[l*ld + v]; adjacent vectors are contiguous, so a wave reads 64 vectors x one l per
+// load: thread = (vector tid%64, 16 consecutive k).
+template <bool CONTIG, int S>
+__global__ void __launch_bounds__(256) k_i8_slice(const double *__restrict__ src, long long ld, int nvec, int len,
+                                                  double scale, const int *__restrict__ E, const int *__restrict__ info,
+                                                  int which, signed char *__restrict__ planes)
 {
     if (info[INFO_PATH] != PATH_I8) return;
     const int s = info[which ? INFO_SB : INFO_SA];
     const int kc = blockIdx.x, vt = blockIdx.y, KC = gridDim.x;
-    const int r = threadIdx.x >> 2, seg = threadIdx.x & 3;
+    const int r = CONTIG ? threadIdx.x >> 2 : threadIdx.x & 63, seg = CONTIG ? threadIdx.x & 3 : threadIdx.x >> 6;
     const int v = vt * I8_T + r, l0 = kc * I8_T + seg * 16;
     const int u = (v < nvec ? E[v] : 0) - 8 * s + 2;
     signed char dg[16][S];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         const int l = l0 + e;
-        const double x = (v < nvec && l < len) ? scale * src[(long long)v * ld + l] : 0.0;
-        digits<S>(to_fixed(x, u), s, dg[e]);
-    }
-    signed char *tile = planes + ((size_t)vt * KC + kc) * (size_t)s * I8_TILE;
-#pragma unroll
-    for (int t = 0; t < S; ++t) {
-        if (t < s) {
-            union { v4i_t v; signed char b[16]; } pk;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) pk.b[e] = dg[e][t];
-            *(v4i_t *)(tile + (size_t)t * I8_TILE + tile_off(r, seg * 16)) = pk.v;
-        }
-    }
-}
-
-// Source vectors STRIDED along k (A for 'T', B for 'N'): element (v, l) at src[l*ld + v]; adjacent vectors are
-// contiguous, so a wave reads 64 vectors x one l per load.  thread = (vector tid%64, 16 consecutive k).
-template <int S>
-__global__ void __launch_bounds__(256) k_i8_slice_strided(const double *__restrict__ src, long long ld, int nvec, int len,
-                                                          double scale, const int *__restrict__ E,
-                                                          const int *__restrict__ info, int which,
-                                                          signed char *__restrict__ planes)
-{
-    if (info[INFO_PATH] != PATH_I8) return;
-    const int s = info[which ? INFO_SB : INFO_SA];
-    const int kc = blockIdx.x, vt = blockIdx.y, KC = gridDim.x;
-    const int r = threadIdx.x & 63, seg = threadIdx.x >> 6;
-    const int v = vt * I8_T + r, l0 = kc * I8_T + seg * 16;
-    const int u = (v < nvec ? E[v] : 0) - 8 * s + 2;
-    signed char dg[16][S];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int l = l0 + e;
-        const double x = (v < nvec && l < len) ? scale * src[(long long)l * ld + v] : 0.0;
+        const double x = (v < nvec && l < len) ? scale * src[CONTIG ? (long long)v * ld + l : (long long)l * ld + v] : 0.0;
         digits<S>(to_fixed(x, u), s, dg[e]);
     }
     signed char *tile = planes + ((size_t)vt * KC + kc) * (size_t)s * I8_TILE;
@@ -187,7 +155,7 @@ __device__ __forceinline__ void i8_epilogue(const PassArgs &a, const v16i_t (&ac
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         unsigned long long w3[3] = {0ull, 0ull, 0ull};
-        static_for_i8<0, G>([&](auto gc) {
+        static_for<0, G>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             wide_add_c<3, 8 * g>(w3, (long long)acc[g][r]);
         });
@@ -267,7 +235,7 @@ __device__ __forceinline__ void i8_pass_exact(const PassArgs &a, LdsBuf lds)
                 (const __attribute__((address_space(1))) void *)(pb + kc * stride_b + (size_t)(i - B) * I8_TILE),
                 (__attribute__((address_space(3))) void *)&lds[buf][(I8_XMAX + i - B) * 256 + wave * 64], 16, 0, 0);
     };
-    auto dma = [&](int kc, int buf) { static_for_i8<0, NMEM>([&](auto ic) { dma_piece(ic, kc, buf); }); };
+    auto dma = [&](int kc, int buf) { static_for<0, NMEM>([&](auto ic) { dma_piece(ic, kc, buf); }); };
     auto fload = [&](int buf, int ks, v4i_t (&fa)[B], v4i_t (&fb)[B]) {
 #pragma unroll
         for (int q = 0; q < B; ++q) fb[q] = lds[buf][(I8_XMAX + q) * 256 + boff[ks]];
@@ -277,13 +245,13 @@ __device__ __forceinline__ void i8_pass_exact(const PassArgs &a, LdsBuf lds)
     auto kstep = [&](const v4i_t (&ca)[B], const v4i_t (&cb)[B], v4i_t (&na)[B], v4i_t (&nb)[B], int rbuf, int rks,
                      bool with_dma, int dkc, int dbuf) {
         constexpr int PER = B * B / NMEM, EXTRA = B * B % NMEM;
-        static_for_i8<0, NMEM>([&](auto ic) {
+        static_for<0, NMEM>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if constexpr (i < B) nb[i] = lds[rbuf][(I8_XMAX + i) * 256 + boff[rks]];
             else na[i - B] = lds[rbuf][(i - B) * 256 + aoff[rks]];
             if (with_dma) dma_piece(ic, dkc, dbuf);
             constexpr int m0 = i * PER + (i < EXTRA ? i : EXTRA), m1 = m0 + PER + (i < EXTRA ? 1 : 0);
-            static_for_i8<m0, m1>([&](auto mc) {
+            static_for<m0, m1>([&](auto mc) {
                 constexpr int mm = decltype(mc)::value, p = mm / B, q = mm % B;
                 acc[p + q] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ca[p], cb[q], acc[p + q], 0, 0, 0);
             });
@@ -480,24 +448,16 @@ __global__ void __launch_bounds__(256) k_i8_zero_w(long long words, const int *_
 // host side: a pure sequence of launches
 // ---------------------------------------------------------------------------------------------
 // exgemm_i8_prepare: scan, decide, slice, zero the accumulators -- everything that concerns the WHOLE operands.  On
-// return plan->ok says whether the int8 path was enqueued (it may still decide, on the device, to leave the work to
-// the scalar kernel: the caller enqueues that one predicated on plan->info[INFO_PATH]); !ok: not attempted (k == 0,
-// workspace unavailable) -> the caller runs the scalar kernel unconditionally.
+// return plan->path == PATH_I8 says that the path was enqueued (it may still decide, on the device, to leave the work
+// to the scalar kernel: the caller enqueues that one predicated on plan->info[INFO_PATH]); otherwise the workspace
+// was unavailable -> the caller runs the scalar kernel unconditionally.
 // exgemm_i8_rows: the contraction passes (and the rounding of multi-pass accumulators) for the rows [row0, row1) of
 // C, row0 a multiple of 64.  A row-sharded caller (comm.hip) runs it chunk by chunk and ships every finished chunk
 // while the next one is computed; the operands are scanned and sliced once for all chunks.
 hipError_t exgemm_i8_prepare(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
                              const double *b, int ldb, double beta, double *cmat, int ldc, int round_mode,
-                             hipStream_t st, I8Plan *plan)
+                             hipStream_t st, GemmPlan *plan)
 {
-    plan->ok = false;
-    if (k <= 0 || m <= 0 || n <= 0) return hipSuccess;
-    if (c.gemm_path == 4 || (c.gemm_path == 0 && m >= CRT_MIN_EDGE && n >= CRT_MIN_EDGE)) {
-        hipError_t e = exgemm_crt_prepare(c, transa, transb, m, n, k, alpha, a, lda, b, ldb, beta, cmat, ldc, round_mode, st,
-                                          plan);
-        // not enqueued although nothing failed = no memory even for 12 moduli: try the digit-slice workspace below
-        if (e != hipSuccess || plan->ok || c.gemm_path == 4) return e;
-    }
     const int ta = (transa == 'T' || transa == 't'), tb = (transb == 'T' || transb == 't');
     const int gy = (m + I8_T - 1) / I8_T, gx = (n + I8_T - 1) / I8_T, KC = (k + I8_T - 1) / I8_T;
     int scap = c.gemm_max_slices > 0 ? c.gemm_max_slices : I8_SCAP;
@@ -505,98 +465,79 @@ hipError_t exgemm_i8_prepare(Ctx &c, char transa, char transb, int m, int n, int
     const int kpasses = (k + I8_KPASS - 1) / I8_KPASS;
     const bool maybe_multi = scap > I8_SMAX || kpasses > 1;
     // workspace: info | EA EB LA LB | planes of A | planes of B | W
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    const size_t o_info = take(sizeof(int) * INFO_WORDS);
-    const size_t o_e = take(sizeof(int) * 2 * ((size_t)m + n));
-    const size_t o_pa = take((size_t)gy * KC * scap * I8_TILE);
-    const size_t o_pb = take((size_t)gx * KC * scap * I8_TILE);
-    const size_t o_w = take(maybe_multi ? (size_t)m * n * I8_NWG * sizeof(unsigned long long) : 0);
+    WsCarve ws;
+    const size_t o_info = ws.take(sizeof(int) * INFO_WORDS);
+    const size_t o_e = ws.take(sizeof(int) * 2 * ((size_t)m + n));
+    const size_t o_pa = ws.take((size_t)gy * KC * scap * I8_TILE);
+    const size_t o_pb = ws.take((size_t)gx * KC * scap * I8_TILE);
+    const size_t o_w = ws.take(maybe_multi ? (size_t)m * n * I8_NWG * sizeof(unsigned long long) : 0);
     hipError_t e = hipSuccess;
-    char *base = (char *)workspace(c, off, st, &e);
+    char *base = (char *)workspace(c, ws.off, st, &e);
     if (!base) {
         if (e == hipErrorStreamCaptureUnsupported) return e;  // the caller must reserve before capturing
         return hipSuccess;                                    // out of memory: scalar kernel
     }
     int *info = (int *)(base + o_info);
-    int *EA = (int *)(base + o_e), *EB = EA + m, *LA = EB + n, *LB = LA + m;
+    int *EA = (int *)(base + o_e), *EB = EA + m;
     signed char *PA = (signed char *)(base + o_pa), *PB = (signed char *)(base + o_pb);
     unsigned long long *W = (unsigned long long *)(base + o_w);
 
-    // ---- scan (shared with the fp64-slice path) ----
-    hipLaunchKernelGGL(k_scan_init, dim3((m + n + 255) / 256), dim3(256), 0, st, m + n, EA, LA, info);
-    const int ysplit = k >= 2048 ? 32 : (k >= 256 ? 8 : 1);
-    if (!ta)
-        hipLaunchKernelGGL(k_scan_contig, dim3(m), dim3(256), 0, st, a, (long long)lda, m, k, alpha, EA, LA, info);
-    else
-        hipLaunchKernelGGL(k_scan_strided, dim3((m + 255) / 256, ysplit), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
-                           EA, LA, info);
-    if (!tb)
-        hipLaunchKernelGGL(k_scan_strided, dim3((n + 255) / 256, ysplit), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
-                           EB, LB, info);
-    else
-        hipLaunchKernelGGL(k_scan_contig, dim3(n), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0, EB, LB, info);
-    hipLaunchKernelGGL(k_scan_finish, dim3((m + 255) / 256), dim3(256), 0, st, m, EA, LA, info, INFO_NEED_A);
-    hipLaunchKernelGGL(k_scan_finish, dim3((n + 255) / 256), dim3(256), 0, st, n, EB, LB, info, INFO_NEED_B);
+    gemm_scan(st, ta, tb, m, n, k, alpha, a, lda, b, ldb, info, EA);
     hipLaunchKernelGGL(k_i8_decide, dim3(1), dim3(64), 0, st, info, scap);
 
     // ---- slice once ----
     if (!ta)
-        hipLaunchKernelGGL((k_i8_slice_contig<I8_SCAP>), dim3(KC, gy), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
+        hipLaunchKernelGGL((k_i8_slice<true, I8_SCAP>), dim3(KC, gy), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
                            EA, info, 0, PA);
     else
-        hipLaunchKernelGGL((k_i8_slice_strided<I8_SCAP>), dim3(KC, gy), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
+        hipLaunchKernelGGL((k_i8_slice<false, I8_SCAP>), dim3(KC, gy), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
                            EA, info, 0, PA);
     if (!tb)
-        hipLaunchKernelGGL((k_i8_slice_strided<I8_SCAP>), dim3(KC, gx), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
+        hipLaunchKernelGGL((k_i8_slice<false, I8_SCAP>), dim3(KC, gx), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
                            EB, info, 1, PB);
     else
-        hipLaunchKernelGGL((k_i8_slice_contig<I8_SCAP>), dim3(KC, gx), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
+        hipLaunchKernelGGL((k_i8_slice<true, I8_SCAP>), dim3(KC, gx), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
                            EB, info, 1, PB);
     const int force_multi = kpasses > 1 ? 1 : 0;
     if (maybe_multi)
         hipLaunchKernelGGL(k_i8_zero_w, dim3(c.num_cu * 8), dim3(256), 0, st, (long long)m * n * I8_NWG, info,
                            force_multi, W);
-    plan->ok = true;
-    plan->m = m; plan->n = n; plan->KC = KC; plan->kpasses = kpasses;
-    plan->dblocks = (scap + I8_SMAX - 1) / I8_SMAX;
-    plan->force_multi = force_multi; plan->maybe_multi = maybe_multi ? 1 : 0;
-    plan->info = info; plan->EA = EA; plan->EB = EB; plan->PA = PA; plan->PB = PB; plan->W = W;
+    plan->path = PATH_I8;
+    plan->m = m; plan->n = n; plan->KC = KC;
+    plan->info = info; plan->EA = EA; plan->EB = EB; plan->PA = PA; plan->PB = PB;
     plan->beta = beta; plan->c = cmat; plan->ldc = ldc; plan->round_mode = round_mode;
-    c.gemm_info_dev = info;
+    plan->i8.kpasses = kpasses;
+    plan->i8.dblocks = (scap + I8_SMAX - 1) / I8_SMAX;
+    plan->i8.force_multi = force_multi; plan->i8.maybe_multi = maybe_multi ? 1 : 0;
+    plan->i8.W = W;
     return hipGetLastError();
 }
 
 // contraction passes over (digit block of A, digit block of B, k block) for the rows [row0, row1); the device skips
 // what the data does not need.  With one k pass and one digit block on both sides the (0, 0) pass rounds and writes C
 // itself; otherwise k_i8_finish rounds the 320-bit accumulators of these rows.
-hipError_t exgemm_i8_rows(const I8Plan &p, int row0, int row1, hipStream_t st)
+hipError_t exgemm_i8_rows(const GemmPlan &p, int row0, int row1, hipStream_t st)
 {
-    if (row1 <= row0) return hipSuccess;
-    if (p.crt) return exgemm_crt_rows(p, row0, row1, st);
+    const auto &q = p.i8;
     const int gx = (p.n + I8_T - 1) / I8_T;
     const int ty0 = row0 / I8_T, ty_cnt = (row1 - row0 + I8_T - 1) / I8_T;
-    for (int kp = 0; kp < p.kpasses; ++kp) {
+    for (int kp = 0; kp < q.kpasses; ++kp) {
         const int kc0 = kp * (I8_KPASS / I8_T), kc1 = min(p.KC, kc0 + I8_KPASS / I8_T);
-        for (int pa_ = 0; pa_ < p.dblocks; ++pa_)
-            for (int pb_ = 0; pb_ < p.dblocks; ++pb_)
+        for (int pa_ = 0; pa_ < q.dblocks; ++pa_)
+            for (int pb_ = 0; pb_ < q.dblocks; ++pb_)
             {
                 hipLaunchKernelGGL(k_gemm_i8, dim3(ty_cnt * gx), dim3(256), 0, st, p.m, p.n, ty0, ty_cnt, p.KC, kc0, kc1,
                                    pa_, pb_, p.PA, p.PB, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, p.round_mode,
-                                   p.force_multi ? 0 : 1, p.W);
+                                   q.force_multi ? 0 : 1, q.W);
                 hipLaunchKernelGGL(k_gemm_i8g, dim3(ty_cnt * gx), dim3(256), 0, st, p.m, p.n, ty0, ty_cnt, p.KC, kc0, kc1,
                                    pa_, pb_, p.PA, p.PB, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, p.round_mode,
-                                   p.force_multi ? 0 : 1, p.W);
+                                   q.force_multi ? 0 : 1, q.W);
             }
     }
-    if (p.maybe_multi)
+    if (q.maybe_multi)
         hipLaunchKernelGGL(k_i8_finish, dim3((unsigned)(((long long)(row1 - row0) * p.n + 255) / 256)), dim3(256), 0, st,
                            row0, row1, p.n, p.info, p.EA, p.EB, p.beta, p.c, (long long)p.ldc, p.round_mode,
-                           p.force_multi, p.W);
+                           q.force_multi, q.W);
     return hipGetLastError();
 }
 

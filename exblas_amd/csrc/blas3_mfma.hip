@@ -21,25 +21,11 @@
 // Result: bit-identical to k_gemm / the oracle / MPFR (tests/test_gpu_blas23.py), with the O(mnk) work on
 // the MFMA pipe.  On gfx950 the f64 MFMA rate equals the f64 VALU FMA rate (78.6 TFLOP/s), so the gain over
 // k_gemm is the ~30 VALU ops per product of the TwoProd+TwoSum chain against SA*SB MFMA-FMAs per product.
-#include "superacc.hip.h"
-#include "exblas_internal.h"
-#include "gemm_scan.hip.h"
-
-#include <type_traits>
+#include "gemm_fixed.hip.h"
 
 namespace exb {
 
 typedef double v4d_t __attribute__((ext_vector_type(4)));
-
-// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
 
 constexpr int MF_BETA = 21;
 constexpr int MF_KP = 512;    // k-block over which MFMA partial sums stay exact
@@ -69,59 +55,6 @@ __device__ __forceinline__ void slice(double x, int ea, double (&out)[S])
             out[p] = ldexp(x, -w);
         }
     }
-}
-
-// 256-bit accumulator += sign_extend(T) << SH   (SH is a compile-time constant after unrolling)
-template <int SH>
-__device__ __forceinline__ void wide_add(unsigned long long (&acc)[4], long long T)
-{
-    constexpr int w = SH >> 6, b = SH & 63;
-    const unsigned long long ext = (unsigned long long)(T >> 63);
-    const unsigned long long lo = (unsigned long long)T << b;
-    const unsigned long long hi = b ? (unsigned long long)(T >> (64 - b)) : ext;
-    unsigned long long v[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (i < w) ? 0ull : (i == w ? lo : (i == w + 1 ? hi : ext));
-    unsigned long long c = 0, cn;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        acc[i] = __builtin_addcll(acc[i], v[i], c, &cn);
-        c = cn;
-    }
-}
-
-// round the 256-bit two's-complement integer to nearest-even and scale by 2^unit_exp (result stays normal:
-// the host only takes this path when all scales are within +-400)
-__device__ inline double wide_round(const unsigned long long (&in)[4], int unit_exp)
-{
-    unsigned long long m[4] = {in[0], in[1], in[2], in[3]};
-    const bool neg = (long long)m[3] < 0;
-    if (neg) {
-        unsigned long long c = 1, cn;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            m[i] = __builtin_addcll(~m[i], 0ull, c, &cn);
-            c = cn;
-        }
-    }
-    int top = 3;
-    while (top > 0 && m[top] == 0) --top;
-    if (m[top] == 0) return 0.0;
-    const int lz = __builtin_clzll(m[top]);
-    const int msb = 64 * top + 63 - lz;
-    double r;
-    if (msb <= 52) {
-        r = ldexp((double)m[0], unit_exp);
-    } else {
-        const unsigned long long below = top > 0 ? m[top - 1] : 0ull;
-        unsigned long long w = lz ? ((m[top] << lz) | (below >> (64 - lz))) : m[top];
-        bool sticky = (w & 0x3ffull) != 0 || (lz ? (below << lz) != 0 : below != 0);
-        for (int i = top - 2; i >= 0; --i) sticky |= m[i] != 0;
-        unsigned long long mant = w >> 11;
-        if (((w >> 10) & 1ull) && (sticky || (mant & 1ull))) mant += 1;  // may reach 2^53: still exact in fp64
-        r = ldexp((double)mant, msb - 52 + unit_exp);
-    }
-    return neg ? -r : r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -266,7 +199,7 @@ __global__ void __launch_bounds__(MF_THREADS, WPS) k_gemm_mfma(int ta, int tb, i
                 for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        wide_add<MF_BETA * (D - (g + 2))>(wide[rt][ct][r], __double2ll_rn(acc[g][rt][ct][r]));
+                        wide_add_c<4, MF_BETA * (D - (g + 2))>(wide[rt][ct][r], __double2ll_rn(acc[g][rt][ct][r]));
         });
     }
     // epilogue: f64 MFMA C/D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
@@ -279,7 +212,7 @@ __global__ void __launch_bounds__(MF_THREADS, WPS) k_gemm_mfma(int ta, int tb, i
                 const int gi = i0 + wr + rt * 16 + (lane >> 4) + 4 * r;
                 const int gj = j0 + wc + ct * 16 + (lane & 15);
                 if (gi < m && gj < n) {
-                    const double s = wide_round(wide[rt][ct][r], EA[gi] + EB[gj] - MF_BETA * D);
+                    const double s = wide_round_n<4>(wide[rt][ct][r], EA[gi] + EB[gj] - MF_BETA * D);
                     double *cij = c + (long long)gi * ldc + gj;
                     *cij = (beta == 0.0) ? s : beta * (*cij) + s;
                 }
@@ -299,34 +232,21 @@ static void launch_mfma(int ta, int tb, int m, int n, int k, double alpha, const
 
 // The fp64-slice path (exblas_set_gemm_path(3)): kept as the literal "MFMA_F64 panel contraction" and as an A/B partner
 // of the int8 path (blas3_i8.hip), which is what exgemm uses by default.
-// Returns true when the MFMA path ran; false -> caller uses the scalar kernel.  Synchronises the stream once
-// (the slice counts are read back on the host), so this path cannot be captured into a hipGraph.
+// Returns true when the MFMA path ran (*slices = the slice count) or failed (*err); false -> caller uses the scalar
+// kernel.  Synchronises the stream once (the slice counts are read back on the host), so this path cannot be captured
+// into a hipGraph.
 bool exgemm_try_mfma(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
-                     const double *b, int ldb, double beta, double *cmat, int ldc, hipStream_t st, hipError_t *err)
+                     const double *b, int ldb, double beta, double *cmat, int ldc, hipStream_t st, hipError_t *err,
+                     int *slices)
 {
     *err = hipSuccess;
-    c.last_gemm_slices = 0;
+    *slices = 0;
     if (k <= 0) return false;
     const int ta = (transa == 'T' || transa == 't'), tb = (transb == 'T' || transb == 't');
     int *buf = (int *)workspace(c, sizeof(int) * (2 * ((size_t)m + n) + INFO_WORDS), st, err);
     if (!buf) return true;
-    int *info = buf, *EA = buf + INFO_WORDS, *EB = EA + m, *LA = EB + n, *LB = LA + m;
-    hipLaunchKernelGGL(k_scan_init, dim3((m + n + 255) / 256), dim3(256), 0, st, m + n, EA, LA, info);  // EA|EB and LA|LB are contiguous
-    const int ysplit = k >= 2048 ? 32 : (k >= 256 ? 8 : 1);
-    // rows of A' (reduction over l)
-    if (!ta)
-        hipLaunchKernelGGL(k_scan_contig, dim3(m), dim3(256), 0, st, a, (long long)lda, m, k, alpha, EA, LA, info);
-    else
-        hipLaunchKernelGGL(k_scan_strided, dim3((m + 255) / 256, ysplit), dim3(256), 0, st, a, (long long)lda, m, k, alpha,
-                           EA, LA, info);
-    // columns of B (reduction over l)
-    if (!tb)
-        hipLaunchKernelGGL(k_scan_strided, dim3((n + 255) / 256, ysplit), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0,
-                           EB, LB, info);
-    else
-        hipLaunchKernelGGL(k_scan_contig, dim3(n), dim3(256), 0, st, b, (long long)ldb, n, k, 1.0, EB, LB, info);
-    hipLaunchKernelGGL(k_scan_finish, dim3((m + 255) / 256), dim3(256), 0, st, m, EA, LA, info, INFO_NEED_A);
-    hipLaunchKernelGGL(k_scan_finish, dim3((n + 255) / 256), dim3(256), 0, st, n, EB, LB, info, INFO_NEED_B);
+    int *info = buf, *EA = buf + INFO_WORDS, *EB = EA + m;   // info | EA EB LA LB, not aligned
+    gemm_scan(st, ta, tb, m, n, k, alpha, a, lda, b, ldb, info, EA);
     int h[INFO_WORDS];
     if ((*err = hipMemcpyAsync(h, info, sizeof(h), hipMemcpyDeviceToHost, st)) != hipSuccess) return true;
     if ((*err = hipStreamSynchronize(st)) != hipSuccess) return true;
@@ -349,7 +269,7 @@ bool exgemm_try_mfma(Ctx &c, char transa, char transb, int m, int n, int k, doub
     else if (s == 3) MF_GO(3, 3, 1, 2, 2);
     else MF_GO(4, 4, 1, 2, 1);
 #undef MF_GO
-    c.last_gemm_slices = s < 2 ? 2 : s;
+    *slices = s < 2 ? 2 : s;
     *err = hipGetLastError();
     return true;
 }

@@ -268,25 +268,26 @@ int exblas_set_launch_events(void *ev_start, void *ev_stop)
 }
 
 // out[0] = implementation of the most recent exgemm on this device (0 scalar kernel, 1 fp64 slices on MFMA-F64,
-// 2 int8 slices on the int8 matrix cores), out[1] / out[2] = digits (slices) of A / B, out[3..7] reserved.
-// The int8 path decides on the device: this call then synchronises the device and reads the decision back.
+// 2 int8 digit slices, 4 int8 residues).  Slices: out[1] / out[2] = slices of A / B.  Residues: out[1] / out[2] = bits
+// of the fixed-point entries of A' / B, out[3] = moduli, out[4] = moduli the workspace was reserved for.  The rest 0.
+// The int8 paths decide on the device: this call then synchronises the device and reads the decision back.
 static int last_gemm_info_on(Ctx &c, int *out)
 {
     std::lock_guard<std::mutex> lk(c.mu);
     for (int i = 0; i < 8; ++i) out[i] = 0;
     if (c.gemm_info_dev) {
-        int h[16];
+        int h[INFO_WORDS];
         if (hipDeviceSynchronize() != hipSuccess) return -1;
         if (hipMemcpy(h, c.gemm_info_dev, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        out[0] = (h[7] == 2 || h[7] == 4) ? h[7] : 0;  // INFO_PATH
-        if (out[0] == 2) {
-            out[1] = h[5];           // INFO_SA
-            out[2] = h[6];           // INFO_SB
-        } else if (out[0] == 4) {
-            out[1] = h[11];          // INFO_CRT_NA: bits of the fixed-point entries of A'
-            out[2] = h[12];          // INFO_CRT_NB
-            out[3] = h[10];          // INFO_CRT_L: moduli = int8 GEMMs
-            out[4] = c.gemm_ws_moduli;  // moduli the workspace was reserved for (39 unless memory ran short)
+        out[0] = (h[INFO_PATH] == PATH_I8 || h[INFO_PATH] == PATH_CRT) ? h[INFO_PATH] : PATH_SCALAR;
+        if (out[0] == PATH_I8) {
+            out[1] = h[INFO_SA];
+            out[2] = h[INFO_SB];
+        } else if (out[0] == PATH_CRT) {
+            out[1] = h[INFO_CRT_NA];
+            out[2] = h[INFO_CRT_NB];
+            out[3] = h[INFO_CRT_L];     // moduli = int8 GEMMs
+            out[4] = c.gemm_ws_moduli;  // 39 unless memory ran short
         }
     } else if (c.last_gemm_slices > 0) {
         out[0] = 1;

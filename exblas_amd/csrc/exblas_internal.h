@@ -284,36 +284,52 @@ hipError_t exgetrs_batched_dispatch(Ctx &c, char order, int p, long long n, int 
                                     const int *ipiv, double *x, long long ldx, int fpe, int early_exit, int round_mode,
                                     hipStream_t st);
 
-// blas3_i8.hip: the int8 ExGEMM path in two steps (whole operands, then rows of C)
-struct I8Plan {
-    bool ok = false;
-    int m = 0, n = 0, KC = 0, kpasses = 0, dblocks = 0, force_multi = 0, maybe_multi = 0;
+// ExGEMM's info block: the words the operand scan and the device-side decisions of the int8 paths write into the
+// workspace, and the values of INFO_PATH (= exblas_last_gemm_info out[0]; the fp64-slice path, 1, decides on the host)
+enum {
+    INFO_NEED_A = 0, INFO_NEED_B = 1, INFO_FLAGS = 2, INFO_EMIN = 3, INFO_EMAX = 4,   // the scan (blas3.hip)
+    INFO_SA = 5, INFO_SB = 6, INFO_PATH = 7, INFO_BS = 8, INFO_EXACT = 9,           // digit slices (blas3_i8.hip)
+    INFO_CRT_L = 10, INFO_CRT_NA = 11, INFO_CRT_NB = 12,                           // residues (blas3_crt.hip)
+    INFO_WORDS = 16,
+    PATH_SCALAR = 0, PATH_I8 = 2, PATH_CRT = 4
+};
+
+// blas3.hip: the operand scan of the three matrix-core paths.  EA heads the block EA | EB | LA | LB of 2 (m + n) ints
+// (scale and lowest set bit per row of A' = fl(alpha A), then per column of B); info gets the scan's words.
+void gemm_scan(hipStream_t st, int ta, int tb, int m, int n, int k, double alpha, const double *a, int lda, const double *b,
+               int ldb, int *info, int *EA);
+
+// blas3_i8.hip / blas3_crt.hip: the two int8 ExGEMM paths, each in two steps (whole operands, then rows of C).  The
+// prepare of a path fills the plan and sets path when it has enqueued its work on the whole operands; the device may
+// still leave the product to the scalar kernel (info[INFO_PATH]).
+struct GemmPlan {
+    int path = PATH_SCALAR;   // PATH_I8 or PATH_CRT: that path's rows function runs; PATH_SCALAR: nothing was enqueued
+    int m = 0, n = 0, KC = 0;
     int *info = nullptr, *EA = nullptr, *EB = nullptr;
-    signed char *PA = nullptr, *PB = nullptr;
-    unsigned long long *W = nullptr;
-    // residue path (blas3_crt.hip): PA / PB hold one plane per modulus, R the residues of C
-    bool crt = false;
-    unsigned *R = nullptr;
-    size_t plane_a = 0, plane_b = 0;
-    int lcap = 0, m4 = 0, num_cu = 256;
-    // residue path: A' is reduced row chunk by row chunk (PA / R hold one chunk)
-    int chunk_rows = 0, lda = 0, ta = 0, k = 0;
-    const double *a = nullptr;
-    double alpha = 1.0;
+    signed char *PA = nullptr, *PB = nullptr;   // digit planes (residue path: one plane per modulus, of one row chunk of A')
     double beta = 0.0;
     double *c = nullptr;
     int ldc = 0, round_mode = 0;
+    struct {
+        int kpasses = 0, dblocks = 0, force_multi = 0, maybe_multi = 0;
+        unsigned long long *W = nullptr;
+    } i8;
+    struct {   // A' is reduced row chunk by row chunk; R holds the residues of the chunk's rows of C
+        unsigned *R = nullptr;
+        size_t plane_a = 0, plane_b = 0;
+        int lcap = 0, m4 = 0, num_cu = 256, chunk_rows = 0, lda = 0, ta = 0, k = 0;
+        const double *a = nullptr;
+        double alpha = 1.0;
+    } crt;
 };
-constexpr int I8_INFO_PATH = 7;  // info word holding the device-side decision: 0 scalar kernel, 2 int8 path
 hipError_t exgemm_i8_prepare(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
                              const double *b, int ldb, double beta, double *cmat, int ldc, int round_mode,
-                             hipStream_t st, I8Plan *plan);
-hipError_t exgemm_i8_rows(const I8Plan &plan, int row0, int row1, hipStream_t st);
-// blas3_crt.hip: same two steps on residues modulo 8-bit moduli (info word 7 then holds 4)
+                             hipStream_t st, GemmPlan *plan);
+hipError_t exgemm_i8_rows(const GemmPlan &plan, int row0, int row1, hipStream_t st);
 hipError_t exgemm_crt_prepare(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
                               const double *b, int ldb, double beta, double *cmat, int ldc, int round_mode,
-                              hipStream_t st, I8Plan *plan);
-hipError_t exgemm_crt_rows(const I8Plan &plan, int row0, int row1, hipStream_t st);
+                              hipStream_t st, GemmPlan *plan);
+hipError_t exgemm_crt_rows(const GemmPlan &plan, int row0, int row1, hipStream_t st);
 hipError_t crt_tables_upload();  // into the current device's tables; context creation only
 constexpr int CRT_MIN_EDGE = 192;  // gemm_path 0: the residue path serves products with min(m, n) >= this
 
@@ -329,8 +345,10 @@ struct GemmChunks {
 int exgemm_chunked_dev(char transa, char transb, int m, int n, int k, double alpha, const double *d_a, int lda,
                        const double *d_b, int ldb, double beta, double *d_c, int ldc, int fpe, int early_exit,
                        hipStream_t st, const GemmChunks *chunks);
+// blas3_mfma.hip: the fp64-slice path; *slices = the slice count it ran with (0: it did not)
 bool exgemm_try_mfma(Ctx &c, char transa, char transb, int m, int n, int k, double alpha, const double *a, int lda,
-                     const double *b, int ldb, double beta, double *cmat, int ldc, hipStream_t st, hipError_t *err);
+                     const double *b, int ldb, double beta, double *cmat, int ldc, hipStream_t st, hipError_t *err,
+                     int *slices);
 
 int round_mode();
 

@@ -1,14 +1,26 @@
-// gemm_fixed.hip.h -- pieces shared by the two int8 matrix-core ExGEMM paths (blas3_i8.hip: base-256 digit slices;
-// blas3_crt.hip: residues modulo pairwise coprime 8-bit moduli): the info block, the tile-major int8 plane layout, the
-// exact double -> fixed-point conversion, wide two's-complement integers with both roundings, the XCD-aware tile order.
+// gemm_fixed.hip.h -- pieces shared by the three matrix-core ExGEMM paths (blas3_i8.hip: base-256 digit slices;
+// blas3_crt.hip: residues modulo pairwise coprime 8-bit moduli; blas3_mfma.hip: 21-bit fp64 slices): the workspace
+// carve, the tile-major int8 plane layout, the exact double -> fixed-point conversion, wide two's-complement integers
+// with both roundings, the XCD-aware tile order.  The info block's words are named in exblas_internal.h.
 #pragma once
 #include "superacc.hip.h"
 #include "exblas_internal.h"
-#include "gemm_scan.hip.h"
 
 #include <type_traits>
 
 namespace exb {
+
+// consecutive regions of one workspace request, each starting on a 256-byte boundary: take(bytes) returns the offset
+// of the next region, off is the size of the whole request
+struct WsCarve {
+    size_t off = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
@@ -24,17 +36,13 @@ constexpr int I8_KPASS = 8192;   // k per pass: 8192 * 8 pairs * 2^14 = 2^30 < 2
 constexpr int I8_NWG = 5;        // 64-bit words of the per-entry accumulator in global memory (multi-pass)
 constexpr int I8_ERANGE = 300;   // |exponent| bound of the operands: keeps every rounded result a normal double
 
-enum { INFO_SA = 5, INFO_SB = 6, INFO_PATH = 7, INFO_BS = 8, INFO_EXACT = 9,     // extends the scan's info block
-       INFO_CRT_L = 10, INFO_CRT_NA = 11, INFO_CRT_NB = 12 };                    // residue path (blas3_crt.hip)
-static_assert(INFO_PATH == I8_INFO_PATH, "exblas_internal.h");
-enum { PATH_SCALAR = 0, PATH_I8 = 2, PATH_CRT = 4 };
-
+// compile-time loop: f(std::integral_constant<int, I>) for I in [B, E)
 template <int B, int E, class F>
-__device__ __forceinline__ void static_for_i8(F &&f)
+__device__ __forceinline__ void static_for(F &&f)
 {
     if constexpr (B < E) {
         f(std::integral_constant<int, B>{});
-        static_for_i8<B + 1, E>(f);
+        static_for<B + 1, E>(f);
     }
 }
 

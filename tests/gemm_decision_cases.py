@@ -1,6 +1,6 @@
 """Inputs that sit on the edges of ExGEMM's path decision and on the seams of its operand scan, with derived results.
 
-ExGEMM scans its operands (csrc/gemm_scan.hip.h) before it picks a contraction path: per vector (row of A' = fl(alpha A),
+ExGEMM scans its operands (k_scan_* in csrc/blas3.hip) before it picks a contraction path: per vector (row of A' = fl(alpha A),
 column of B) the top exponent and the lowest set bit, globally one flag for anything that is not a finite normal
 number or a zero.  k_i8_decide / k_crt_decide (device) and exgemm_try_mfma (host) turn that into "digit slices",
 "residues", "fp64 slices" or "leave it to the scalar kernel".  Every case here is a base pair of operands well inside

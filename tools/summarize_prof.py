@@ -37,8 +37,7 @@ def short(name):
     # longest names first: k_stream_read2 must not be averaged into k_stream_read (it reads twice the bytes)
     for k in ("k_stream_read2", "k_stream_read", "k_exsum_segmented", "k_exsum", "k_exdot", "k_finalize", "k_gen",
               "k_gemv_finish", "k_gemvN_fpe_sx", "k_gemvN_fpe", "k_gemvN_sa", "k_gemvT", "k_scale_x", "k_gemm_mfma", "k_gemm_crt", "k_crt_finish", "k_crt_residues", "k_crt_decide", "k_gemm_i8g",
-              "k_gemm_i8", "k_i8_slice_contig",
-              "k_i8_slice_strided", "k_i8_finish", "k_i8_zero_w", "k_i8_decide", "k_gemm", "k_trsv", "k_dtrsv",
+              "k_gemm_i8", "k_i8_slice", "k_i8_finish", "k_i8_zero_w", "k_i8_decide", "k_gemm", "k_trsv", "k_dtrsv",
               "k_scan"):
         if k + "<" in name or k + "(" in name:
             return k
