@@ -51,6 +51,7 @@ C_ABI_SYMBOLS = [
     "exblas_last_sptrsv_info",
     "exblas_exspilu0_csr_dev", "exblas_exspilu0_csr_ctx", "exblas_exspilu0_csr", "exblas_set_spilu0_path",
     "exblas_last_spilu0_info",
+    "exblas_exspic0_csr_dev", "exblas_exspic0_csr_ctx", "exblas_exspic0_csr", "exblas_set_spic0_path", "exblas_last_spic0_info",
     "exblas_exsptrsm_csr_dev", "exblas_exsptrsm_csr_ctx", "exblas_exsptrsm_csr", "exblas_set_sptrsm_path",
     "exblas_last_sptrsm_info",
     "exblas_extrsm_dev", "exblas_extrsm_ctx", "exblas_extrsm", "exblas_set_trsm_path", "exblas_last_trsm_info",
@@ -212,6 +213,12 @@ def load_library():
     L.exblas_set_spilu0_path.argtypes = [i32]
     L.exblas_set_spilu0_path.restype = None
     L.exblas_last_spilu0_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exspic0_csr_dev.argtypes = L.exblas_exspilu0_csr_dev.argtypes
+    L.exblas_exspic0_csr_ctx.argtypes = L.exblas_exspilu0_csr_ctx.argtypes
+    L.exblas_exspic0_csr.argtypes = L.exblas_exspilu0_csr.argtypes
+    L.exblas_set_spic0_path.argtypes = [i32]
+    L.exblas_set_spic0_path.restype = None
+    L.exblas_last_spic0_info.argtypes = [C.POINTER(i64)]
     L.exblas_exsptrsm_csr_dev.argtypes = [C.c_char, C.c_char, i32, i32, i32, vp, vp, vp, vp, i64, i32, i32, vp]
     L.exblas_exsptrsm_csr_ctx.argtypes = [vp] + L.exblas_exsptrsm_csr_dev.argtypes
     L.exblas_exsptrsm_csr.argtypes = [C.c_char, C.c_char, i32, i32, i32, vp, vp, vp, vp, i64, i32, i32]
@@ -522,21 +529,22 @@ def last_sptrsv_info():
     return _last_info("sptrsv")
 
 
-def _spilu0_args(A, out, info, fpe, early_exit):
-    """Validates a device ExSpILU0 call before anything is launched; returns (LU, info, the C arguments up to the stream)."""
+def _factor_args(who, A, out, info, fpe, early_exit):
+    """Validates a device ExSpILU0 / ExSpIC0 call (who: "exspilu0" / "exspic0") before anything is launched; returns
+    (the factor, info, the C arguments up to the stream)."""
     torch = _torch()
-    crow, col, val, m, _, bits = _csr_dev("exspilu0", A, square=True)
+    crow, col, val, m, _, bits = _csr_dev(who, A, square=True)
     given = {}
     if out is not None:
-        _dense_dev("exspilu0", "out", out, 1)
+        _dense_dev(who, "out", out, 1)
         if out.numel() != val.numel() or not out.is_contiguous():
-            raise ValueError(f"exspilu0: out must be a contiguous vector of nnz = {val.numel()} values")
+            raise ValueError(f"{who}: out must be a contiguous vector of nnz = {val.numel()} values")
         given["out"] = out
     if info is not None:
         if not isinstance(info, torch.Tensor) or info.dtype != torch.int64 or info.numel() != 2 or not info.is_contiguous():
-            raise ValueError("exspilu0: info must be a contiguous int64 torch tensor of 2 words")
+            raise ValueError(f"{who}: info must be a contiguous int64 torch tensor of 2 words")
         given["info"] = info
-    _on_gpu("exspilu0", crow=crow, col=col, val=val, **given)
+    _on_gpu(who, crow=crow, col=col, val=val, **given)
     if out is None:
         out = torch.empty_like(val)
     if info is None:
@@ -555,6 +563,19 @@ def last_spilu0_info():
     """(entries rounded in registers, entries rounded from the accumulator, product terms summed, rows in the
     several-entries-per-lane form) of the last ExSpILU0; raises when that call's watchdog was raised."""
     return _last_info("spilu0")
+
+
+def set_spic0_path(mode):
+    """Test hook: 0 automatic, 1 every rounding through the wave's integer accumulator, 2 every row in the
+    several-entries-per-lane form.  Same bits on every path."""
+    _set_path("spic0", mode)
+
+
+def last_spic0_info():
+    """(entries on and below the diagonal rounded in registers, ... rounded from the accumulator, product terms summed,
+    rows whose owned part is in the several-entries-per-lane form) of the last ExSpIC0; raises when that call's watchdog
+    was raised."""
+    return _last_info("spic0")
 
 
 def _sptrsm_args(A, X, uplo, diag, fpe, early_exit):
@@ -1375,7 +1396,7 @@ class Context:
         index tensors and holds L (unit diagonal, not stored) below and U on and above the diagonal; info[0] is 0 or r + 1
         for the first row with a structural defect (out is then untouched), info[1] 0 or r + 1 for the first zero or NaN
         pivot.  Apply it with exspilu0_apply_dev."""
-        LU, info, args = _spilu0_args(A, out, info, fpe, early_exit)
+        LU, info, args = _factor_args("exspilu0", A, out, info, fpe, early_exit)
         _check(load_library().exblas_exspilu0_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspilu0")
         return LU, info
 
@@ -1391,6 +1412,38 @@ class Context:
             raise ValueError("exspilu0_apply: X must be a vector or a 2-D block of right-hand sides")
         solve(LU, X, uplo="L", diag="U", fpe=fpe, early_exit=early_exit)
         return solve(LU, X, uplo="U", diag="N", fpe=fpe, early_exit=early_exit)
+
+    def exspic0(self, A, out=None, info=None, fpe=8, early_exit=True):
+        """ExSpIC0: the exact-sum IC(0) factor of the symmetric square CSR matrix A on its own pattern, reproducible bit for
+        bit, stream-ordered on the current stream.  Rows in ascending order, for every stored (i, j) with j <= i:
+        c_ij = Round(a_ij - sum_k l_ik l_jk) over the k < j stored in rows i and j, the sum exact and rounded once;
+        l_ij = c_ij / l_jj below the diagonal, l_ii = sqrt(c_ii) on it.  A as for exsptrsv_dev, with strictly ascending
+        columns, a stored diagonal in every row and a structurally symmetric pattern; values above the diagonal are never
+        read.  `out` (float64, nnz values; may be A's own values tensor) and `info` (int64, 2 words) are allocated when
+        None.  Returns (LL, info): LL = (crow, col, out, (m, m)) shares A's index tensors and holds L on and below the
+        diagonal and its mirror L^T above it; info[0] is 0 or r + 1 for the first row with a structural defect (phase 1:
+        ExSpILU0's defects; phase 2, when there is none: a stored (r, j) without (j, r); out is then untouched), info[1]
+        0 or r + 1 for the first radicand that is not > 0 (the factorisation goes on in IEEE arithmetic).  Apply it with
+        exspic0_apply_dev."""
+        if int(fpe) < 0:
+            raise ValueError(f"exspic0: fpe must be >= 0, got {fpe}")
+        LL, info, args = _factor_args("exspic0", A, out, info, fpe, early_exit)
+        _check(load_library().exblas_exspic0_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspic0")
+        return LL, info
+
+    def exspic0_apply(self, LL, X, fpe=8, early_exit=True):  # noqa: N803
+        """Applies the factor of exspic0_dev in place: X := L^-T L^-1 X, the lower sweep and then the upper one (the mirror
+        L^T), through ExSpTRSV for a 1-D X and ExSpTRSM for a 2-D block (each column bit for bit what the vector form
+        gives).  Returns X."""
+        if getattr(X, "ndim", None) == 1:
+            solve = self.exsptrsv
+        elif getattr(X, "ndim", None) == 2:
+            solve = self.exsptrsm
+        else:
+            _dense_dev("exspic0_apply", "X", X, 1)
+            raise ValueError("exspic0_apply: X must be a vector or a 2-D block of right-hand sides")
+        solve(LL, X, uplo="L", diag="N", fpe=fpe, early_exit=early_exit)
+        return solve(LL, X, uplo="U", diag="N", fpe=fpe, early_exit=early_exit)
 
     def exsptrsm(self, A, X, uplo="L", diag="N", fpe=8, early_exit=True):
         """ExSpTRSM: solves A X = B in place on the m x k block X (B on entry) for k right-hand sides at once, exact and
@@ -1542,6 +1595,7 @@ exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.
 extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
 exspilu0_dev, exspilu0_apply_dev = _default.exspilu0, _default.exspilu0_apply
+exspic0_dev, exspic0_apply_dev = _default.exspic0, _default.exspic0_apply
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
 exbgemm_dev = _default.exbgemm
 exbtrsm_dev = _default.exbtrsm
@@ -1721,18 +1775,30 @@ def exsptrsv(A, b, uplo="L", diag="N", fpe=8, early_exit=True):
     return x
 
 
+def _factor_host(who, A, fpe, early_exit):
+    crow, col, val, m, _, bits = _csr_host(who, A, square=True)
+    out = np.array(val, dtype=np.float64, copy=True)
+    info = np.zeros(2, dtype=np.int64)
+    _require_gpu()
+    _check_sparse(getattr(load_library(), f"exblas_{who}_csr")(m, bits, _hptr(crow), _hptr(col), _hptr(val), _hptr(out),
+                                                                C.c_void_p(info.ctypes.data), int(fpe),
+                                                                int(bool(early_exit))), who)
+    return out, (int(info[0]), int(info[1]))
+
+
 def exspilu0(A, fpe=8, early_exit=True):
     """ExSpILU0 on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv; strictly ascending
     columns and a stored diagonal in every row); returns (lu_values, (info0, info1)): the factor's values on A's pattern
     (a new float64 array, a copy of A's values when info0 reports a structural defect) and the two info words."""
-    crow, col, val, m, _, bits = _csr_host("exspilu0", A, square=True)
-    lu = np.array(val, dtype=np.float64, copy=True)
-    info = np.zeros(2, dtype=np.int64)
-    _require_gpu()
-    _check_sparse(load_library().exblas_exspilu0_csr(m, bits, _hptr(crow), _hptr(col), _hptr(val), _hptr(lu),
-                                                     C.c_void_p(info.ctypes.data), int(fpe), int(bool(early_exit))),
-                  "exspilu0")
-    return lu, (int(info[0]), int(info[1]))
+    return _factor_host("exspilu0", A, fpe, early_exit)
+
+
+def exspic0(A, fpe=8, early_exit=True):
+    """ExSpIC0 on host arrays: A = (row_ptr, col_idx, val, (m, m)) as numpy arrays (as for exspmv; strictly ascending
+    columns, a stored diagonal in every row, a structurally symmetric pattern); returns (ll_values, (info0, info1)): the
+    factor's values on A's pattern, L and its mirror (a new float64 array, a copy of A's values when info0 reports a
+    structural defect) and the two info words."""
+    return _factor_host("exspic0", A, fpe, early_exit)
 
 
 def exsptrsm(A, B, uplo="L", diag="N", fpe=8, early_exit=True):

@@ -336,6 +336,7 @@ void exblas_set_spmv_path(int mode) { set_path(&CtxKnobs::spmv_path, mode, 3); }
 void exblas_set_spmm_path(int mode) { set_path(&CtxKnobs::spmm_path, mode, 3); }
 void exblas_set_sptrsv_path(int mode) { set_path(&CtxKnobs::sptrsv_path, mode, 2); }
 void exblas_set_spilu0_path(int mode) { set_path(&CtxKnobs::spilu0_path, mode, 2); }
+void exblas_set_spic0_path(int mode) { set_path(&CtxKnobs::spic0_path, mode, 2); }
 void exblas_set_sptrsm_path(int mode) { set_path(&CtxKnobs::sptrsm_path, mode, 3); }
 void exblas_set_trsm_path(int mode) { set_path(&CtxKnobs::trsm_path, mode, 3); }
 void exblas_set_bdot_path(int mode) { set_path(&CtxKnobs::bdot_path, mode, 2); }
@@ -394,6 +395,10 @@ int exblas_last_sptrsv_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs:
 // out[0] entries rounded in registers, out[1] entries rounded from the accumulator, out[2] product terms summed, out[3] rows
 // in the several-entries-per-lane form; EXBLAS_SPTRSV_STALLED as above
 int exblas_last_spilu0_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::spilu0_info_dev, true, out4); }
+
+// out[0] entries rounded in registers, out[1] entries rounded from the accumulator (both on and below the diagonal only),
+// out[2] product terms summed, out[3] rows in the several-entries-per-lane form; EXBLAS_SPTRSV_STALLED as above
+int exblas_last_spic0_info(int64_t *out4) { return last_sparse_info(&CtxWsPtrs::spic0_info_dev, true, out4); }
 
 // out[0] outputs rounded in registers, out[1] outputs rounded from the accumulator, out[2] rows without a stored diagonal
 // under 'N', out[3] stored entries skipped (the structure counts once, whatever k); EXBLAS_SPTRSV_STALLED as above
@@ -592,6 +597,22 @@ static int exspilu0_on(Ctx &c, int m, int index_bits, const void *d_row_ptr, con
     if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
     return (int)exspilu0_dispatch(c, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, (long long *)d_info, fpe, early_exit,
                                   round_mode(), st);
+}
+
+// the checks of exspilu0_on, which need no context: the device entries make them before one is looked up
+static bool spic0_args_bad(int m, int index_bits, const void *d_row_ptr, const int64_t *d_info, int fpe)
+{
+    return m < 0 || fpe < 0 || (index_bits != 32 && index_bits != 64) || !d_info || (m > 0 && !d_row_ptr);
+}
+
+static int exspic0_on(Ctx &c, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                      double *d_ll, int64_t *d_info, int fpe, int early_exit, hipStream_t st)
+{
+    if (spic0_args_bad(m, index_bits, d_row_ptr, d_info, fpe)) return (int)hipErrorInvalidValue;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exspic0_dispatch(c, m, index_bits, d_row_ptr, d_col_idx, d_val, d_ll, (long long *)d_info, fpe, early_exit,
+                                 round_mode(), st);
 }
 
 static int exsptrsm_on(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
@@ -1047,6 +1068,14 @@ int exblas_exspilu0_csr_ctx(exblas_ctx_t *h, int m, int index_bits, const void *
     return exspilu0_on(*cp, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, d_info, fpe, early_exit, (hipStream_t)stream);
 }
 
+int exblas_exspic0_csr_ctx(exblas_ctx_t *h, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                           const double *d_val, double *d_ll, int64_t *d_info, int fpe, int early_exit, void *stream)
+{
+    if (spic0_args_bad(m, index_bits, d_row_ptr, d_info, fpe)) return (int)hipErrorInvalidValue;
+    EXB_HANDLE(h);
+    return exspic0_on(*cp, m, index_bits, d_row_ptr, d_col_idx, d_val, d_ll, d_info, fpe, early_exit, (hipStream_t)stream);
+}
+
 int exblas_exsptrsm_csr_ctx(exblas_ctx_t *h, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
                             const void *d_col_idx, const double *d_val, double *d_x, int64_t ldx, int fpe, int early_exit,
                             void *stream)
@@ -1267,6 +1296,11 @@ int exblas_exspilu0_csr_dev(int m, int index_bits, const void *d_row_ptr, const 
                             double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream)
 {
     return exblas_exspilu0_csr_ctx(nullptr, m, index_bits, d_row_ptr, d_col_idx, d_val, d_lu, d_info, fpe, early_exit, stream);
+}
+int exblas_exspic0_csr_dev(int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                           double *d_ll, int64_t *d_info, int fpe, int early_exit, void *stream)
+{
+    return exblas_exspic0_csr_ctx(nullptr, m, index_bits, d_row_ptr, d_col_idx, d_val, d_ll, d_info, fpe, early_exit, stream);
 }
 
 int exblas_exsptrsv_csr_dev(char uplo, char diag, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
@@ -1699,6 +1733,34 @@ static int host_solve_status(const long long *CtxWsPtrs::*info_dev)
     return solve_status(c.*info_dev, h);
 }
 
+// the shared CSR host path with Y = [factor | info]: nnz values (they travel both ways, so that a refused structure leaves
+// the factor as it was) and the two info words behind them; `on` is exspilu0_on or exspic0_on
+template <class On>
+static int csr_factor_host(const char *who, const long long *CtxWsPtrs::*info_dev, int m, int index_bits, const void *row_ptr,
+                           const void *col_idx, const double *val, double *out, int64_t *info, int fpe, On &&on)
+{
+    if (m < 0 || !info || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
+    info[0] = info[1] = 0;
+    if (m == 0) return fpe < 0 ? (int)hipErrorInvalidValue : 0;
+    if (!row_ptr) return (int)hipErrorInvalidValue;
+    long long nnz = 0;   // as csr_host_call counts them (it refuses a negative entry)
+    for (int i = 0; i <= m; ++i)
+        nnz = std::max(nnz, index_bits == 32 ? (long long)((const int32_t *)row_ptr)[i] : (long long)((const int64_t *)row_ptr)[i]);
+    if (nnz > 0 && !out) return (int)hipErrorInvalidValue;
+    std::vector<double> y((size_t)nnz + 2, 0.0);
+    if (nnz > 0) memcpy(y.data(), out, (size_t)nnz * sizeof(double));
+    const int rc = csr_host_call(
+        who, m, 0, 1, index_bits, row_ptr, col_idx, val, nullptr, 1, y.data(), 1, fpe,
+        [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *, double *d_y) {
+            return on(c, m, index_bits, d_rp, d_ci, d_val, d_y, (int64_t *)(d_y + nnz), c.stream);
+        },
+        (size_t)nnz + 2);
+    if (rc) return rc;
+    if (nnz > 0) memcpy(out, y.data(), (size_t)nnz * sizeof(double));
+    memcpy(info, y.data() + nnz, 2 * sizeof(int64_t));
+    return host_solve_status(info_dev);
+}
+
 extern "C" {
 
 int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
@@ -1735,31 +1797,24 @@ int exblas_exsptrsv_csr(char uplo, char diag, int m, int index_bits, const void 
     return (rc || m == 0) ? rc : host_solve_status(&CtxWsPtrs::sptrsv_info_dev);
 }
 
-// the shared CSR host path with Y = [lu | info]: nnz values (they travel both ways, so that a refused structure leaves
-// lu as it was) and the two info words behind them
 int exblas_exspilu0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *lu,
                         int64_t *info, int fpe, int early_exit)
 {
-    if (m < 0 || !info || (index_bits != 32 && index_bits != 64)) return (int)hipErrorInvalidValue;
-    info[0] = info[1] = 0;
-    if (m == 0) return fpe < 0 ? (int)hipErrorInvalidValue : 0;
-    if (!row_ptr) return (int)hipErrorInvalidValue;
-    long long nnz = 0;   // as csr_host_call counts them (it refuses a negative entry)
-    for (int i = 0; i <= m; ++i)
-        nnz = std::max(nnz, index_bits == 32 ? (long long)((const int32_t *)row_ptr)[i] : (long long)((const int64_t *)row_ptr)[i]);
-    if (nnz > 0 && !lu) return (int)hipErrorInvalidValue;
-    std::vector<double> y((size_t)nnz + 2, 0.0);
-    if (nnz > 0) memcpy(y.data(), lu, (size_t)nnz * sizeof(double));
-    const int rc = csr_host_call(
-        "exblas_exspilu0_csr", m, 0, 1, index_bits, row_ptr, col_idx, val, nullptr, 1, y.data(), 1, fpe,
-        [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *, double *d_y) {
-            return exspilu0_on(c, m, index_bits, d_rp, d_ci, d_val, d_y, (int64_t *)(d_y + nnz), fpe, early_exit, c.stream);
-        },
-        (size_t)nnz + 2);
-    if (rc) return rc;
-    if (nnz > 0) memcpy(lu, y.data(), (size_t)nnz * sizeof(double));
-    memcpy(info, y.data() + nnz, 2 * sizeof(int64_t));
-    return host_solve_status(&CtxWsPtrs::spilu0_info_dev);
+    return csr_factor_host("exblas_exspilu0_csr", &CtxWsPtrs::spilu0_info_dev, m, index_bits, row_ptr, col_idx, val, lu, info,
+                           fpe, [&](Ctx &c, int m_, int ib, const void *rp, const void *ci, const double *v, double *y,
+                                    int64_t *inf, hipStream_t st) {
+                               return exspilu0_on(c, m_, ib, rp, ci, v, y, inf, fpe, early_exit, st);
+                           });
+}
+
+int exblas_exspic0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *ll,
+                       int64_t *info, int fpe, int early_exit)
+{
+    return csr_factor_host("exblas_exspic0_csr", &CtxWsPtrs::spic0_info_dev, m, index_bits, row_ptr, col_idx, val, ll, info,
+                           fpe, [&](Ctx &c, int m_, int ib, const void *rp, const void *ci, const double *v, double *y,
+                                    int64_t *inf, hipStream_t st) {
+                               return exspic0_on(c, m_, ib, rp, ci, v, y, inf, fpe, early_exit, st);
+                           });
 }
 
 // the same with a block: X (m x k, row stride ldx; B on entry, the solution on return) travels as the host path's Y

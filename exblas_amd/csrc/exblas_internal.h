@@ -33,6 +33,8 @@ struct CtxKnobs {
                              // 2 every row in the one-row-per-wave form
     int spilu0_path = 0;     // exblas_set_spilu0_path: 0 automatic, 1 every rounding from the wave's integer accumulator,
                              // 2 every row in the several-entries-per-lane form
+    int spic0_path = 0;      // exblas_set_spic0_path: 0 automatic, 1 every rounding from the wave's integer accumulator,
+                             // 2 every row in the several-entries-per-lane form
     int sptrsm_path = 0;     // exblas_set_sptrsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
                              // per item, 3 column panels and tiles of 4 columns
     int trsm_path = 0;       // exblas_set_trsm_path: 0 automatic, 1 every output rounded from the accumulator, 2 one row
@@ -76,6 +78,9 @@ struct CtxWsPtrs {
     const long long *spilu0_info_dev = nullptr;  // header of the last ExSpILU0 call's workspace (nullptr: it launched nothing)
     int spilu0_m = -1;                           // ... and what its mailbox was sized for: a call that is being captured
     long long spilu0_nnz = 0;                    // cannot read row_ptr[m] and takes these (spilu0.hip)
+    const long long *spic0_info_dev = nullptr;   // the same for the last ExSpIC0 call (spic0.hip)
+    int spic0_m = -1;
+    long long spic0_nnz = 0;
     const long long *sptrsm_info_dev = nullptr;  // header of the last ExSpTRSM call's workspace (nullptr: it launched nothing)
     const long long *trsm_info_dev = nullptr;    // header of the last ExTRSM call's workspace (nullptr: it launched nothing)
     SlotInfo bgemm_slots, btrsm_slots, potrf_slots;   // of the last ExBGEMM, ExBTRSM and ExPOTRF (one workgroup) call
@@ -219,6 +224,10 @@ hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits
 // spilu0.hip
 hipError_t exspilu0_dispatch(Ctx &c, int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
                              double *lu, long long *info, int fpe, int early_exit, int round_mode, hipStream_t st);
+
+// spic0.hip
+hipError_t exspic0_dispatch(Ctx &c, int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
+                            double *ll, long long *info, int fpe, int early_exit, int round_mode, hipStream_t st);
 
 // sptrsm.hip
 hipError_t exsptrsm_dispatch(Ctx &c, char uplo, char diag, int m, int k, int index_bits, const void *row_ptr,

@@ -381,7 +381,7 @@ int exblas_last_sptrsm_info(int64_t *out4);
  * the same m and pattern, and on replay serves any values on a pattern of at most the nnz it was captured with (a row
  * that does not fit the mailbox is reported in info[0]).  m == 0: info is zeroed, nothing else is launched.  m < 0,
  * index_bits other than 32 / 64, fpe < 0 or d_info null: hipErrorInvalidValue.  Returns 0 or a hipError_t.
- * Not provided: IC(0), fill (ILU(k), ILUT), modified ILU, pivoting, unsorted rows, BSR / CSC. */
+ * Not provided: fill (ILU(k), ILUT), modified ILU, pivoting, unsorted rows, BSR / CSC.  The symmetric form is ExSpIC0. */
 #define EXBLAS_SPILU0_MAX_ROW 512
 int exblas_exspilu0_csr_dev(int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
                             double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream);
@@ -394,6 +394,55 @@ void exblas_set_spilu0_path(int mode);
  * after a call that launched nothing or met a structural defect.  Synchronises the device; valid until the next call
  * that uses the workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as exblas_last_sptrsv_info does. */
 int exblas_last_spilu0_info(int64_t *out4);
+/* ExSpIC0: the exact-sum IC(0) factor of a symmetric square m x m CSR matrix A on device pointers (row_ptr[m+1], col_idx[nnz]
+ * int32 or int64, both the same width; val and ll contiguous fp64 of nnz entries).  Every row must have strictly ascending
+ * column indices and a stored diagonal, and the pattern S must be structurally symmetric: (i, j) is stored exactly when
+ * (j, i) is (the full matrix a CG caller holds for ExSpMV).  Only the entries on and below the diagonal are read: values
+ * above it are never read, so a NaN there changes nothing.  For every stored (i, j) with j <= i, rows in ascending order,
+ *     c_ij = Round(a_ij - sum over k of l_ik * l_jk)      k < j, (i, k) in S, (j, k) in S   (for j = i: the l_ik^2)
+ *     j <  i:  l_ij = c_ij / l_jj   (one IEEE fp64 quotient)
+ *     j == i:  l_ii = sqrt(c_ii)    (one correctly rounded fp64 square root, as in exblas_expotrf_dev)
+ * the sum exact over the already fixed doubles (every TwoProd pair goes in) and rounded once, Round being the
+ * superaccumulator rounding of the current rounding mode (exblas_set_round_mode).  The output is ONE value array d_ll on
+ * A's own row_ptr / col_idx: L on and below the diagonal, and every stored upper position (j, i) holds the same double as
+ * l_ij (L^T written as a mirror), so exblas_exsptrsv_csr_dev('L', 'N', ..., d_ll, x) followed by
+ * exblas_exsptrsv_csr_dev('U', 'N', ..., d_ll, x) (or the ExSpTRSM pair) applies (L L^T)^-1 as it is.  On a sound call
+ * every stored position of d_ll is written.  d_ll may be d_val (same bits).  On a dense pattern with no breakdown the lower
+ * triangle is bit for bit exblas_expotrf_dev(G, 'L'); on a block-diagonal pattern of dense blocks, each block is what
+ * ExPOTRF gives on that block.
+ * Breakdown: ExSpILU0's rule, NOT ExPOTRF's (which stops at the first radicand that is not > 0 and leaves the rest).  A
+ * radicand c_ii that is not > 0 (zero, negative or NaN) gives l_ii = sqrt(c_ii) by IEEE arithmetic, and every later entry
+ * follows IEEE arithmetic (c / 0, Inf - Inf, 0 * Inf); the factorisation never stops.
+ * d_info is int64[2] on the device, written in stream order.  info[0]: 0, or r + 1 for the smallest row r with a
+ * structural defect, in two phases.  Phase 1: ExSpILU0's defects -- row_ptr decreasing (or a row outside [0, row_ptr[m]]),
+ * a column outside [0, m), columns not strictly ascending, no stored diagonal, more than EXBLAS_SPIC0_MAX_ROW entries.
+ * Phase 2, only when phase 1 found nothing: the smallest row r that stores some (r, j) with no stored (j, r).  On any
+ * structural defect d_ll is not written at all.  info[1]: 0, or r + 1 for the smallest row whose radicand c_rr is not > 0
+ * ("not positive definite on the pattern").  Both are order-independent minima.
+ * The bits depend on the data and the rounding mode only: not on the grid, the index width, the path
+ * (exblas_set_spic0_path), fpe (0 or >= 2), early_exit, the context or the stream.  fpe == 0 rounds every entry from the
+ * integer accumulator; fpe == 1 is the plain fp64 form s = a_ij, then s -= l_ik * l_jk for k ascending, then the division
+ * or the square root (deterministic, not exact).
+ * One stream-ordered chain of four kernels (preset, the two phases of the structure check, one persistent factor kernel),
+ * no analysis phase.  Context workspace: 256 + 8 m (rounded up to 256) + 8 nnz bytes, and the rules of a captured call,
+ * as for ExSpILU0: a call outside a stream capture reads row_ptr[m] back; a call that is being captured is capturable
+ * after exblas_reserve_workspace of that many bytes or one call of the same m and pattern, and on replay a row that does
+ * not fit the captured nnz is reported in info[0].  m == 0: info is zeroed, nothing else is launched.  m < 0, index_bits
+ * other than 32 / 64, fpe < 0 or d_info null: hipErrorInvalidValue.  Returns 0 or a hipError_t.
+ * Not provided: fill (IC(k), ICT), modified IC, shifts on breakdown, a stored upper triangle alone, unsorted rows. */
+#define EXBLAS_SPIC0_MAX_ROW EXBLAS_SPILU0_MAX_ROW
+int exblas_exspic0_csr_dev(int m, int index_bits, const void *d_row_ptr, const void *d_col_idx, const double *d_val,
+                           double *d_ll, int64_t *d_info, int fpe, int early_exit, void *stream);
+/* Test hook for ExSpIC0 (same bits on every path): 0 automatic, 1 every rounding through the wave's integer accumulator,
+ * 2 every row in the several-entries-per-lane form (8 lanes share an owned part of at most 64 entries). */
+void exblas_set_spic0_path(int mode);
+/* The most recent ExSpIC0 on this device: out[0] entries rounded in registers, out[1] entries rounded from the integer
+ * accumulator (out[0] + out[1] == the stored entries on and below the diagonal on a sound, completed call with fpe != 1;
+ * both 0 for fpe == 1), out[2] product terms summed (the triples (i, k, j) with j <= i of the definition), out[3] rows whose
+ * owned part (the entries on and below the diagonal) is in the several-entries-per-lane form; all 0 after a call that
+ * launched nothing or met a structural defect.  Synchronises the device; valid until the next call that uses the
+ * workspace.  Returns 0, a hipError_t, or EXBLAS_SPTRSV_STALLED as exblas_last_sptrsv_info does. */
+int exblas_last_spic0_info(int64_t *out4);
 /* ExTRSM: ExTRSV with k right-hand sides.  A is the n x n column-major triangle of exblas_extrsv_dev (lda >= max(1, n),
  * uplo 'L'/'U', transa 'N'/'T', diag 'N'/'U'); d_x is an n x k ROW-MAJOR block with leading dimension ldx >= k, as in
  * ExSpTRSM and ExBDOT, that holds B on entry and the solution on return.  For every column j, X[:, j] afterwards holds
@@ -803,6 +852,8 @@ int exblas_exspmv_csr_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const
                           double *d_y, int fpe, int early_exit, void *stream);
 int exblas_exspilu0_csr_ctx(exblas_ctx_t *ctx, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                             const double *d_val, double *d_lu, int64_t *d_info, int fpe, int early_exit, void *stream);
+int exblas_exspic0_csr_ctx(exblas_ctx_t *ctx, int m, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                           const double *d_val, double *d_ll, int64_t *d_info, int fpe, int early_exit, void *stream);
 int exblas_exsptrsv_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int index_bits, const void *d_row_ptr,
                             const void *d_col_idx, const double *d_val, double *d_x, int fpe, int early_exit, void *stream);
 int exblas_exsptrsm_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int k, int index_bits, const void *d_row_ptr,
@@ -978,6 +1029,11 @@ int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, 
  * EXBLAS_SPTRSV_STALLED (see exblas_last_spilu0_info). */
 int exblas_exspilu0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *lu,
                         int64_t *info, int fpe, int early_exit);
+/* exblas_exspic0_csr_dev on host arrays (ll: nnz values out, left as they are on a structural defect; info: two words):
+ * staged through the device, synchronous.  Returns 0, hipErrorInvalidValue (also for a negative row_ptr entry) or
+ * EXBLAS_SPTRSV_STALLED (see exblas_last_spic0_info). */
+int exblas_exspic0_csr(int m, int index_bits, const void *row_ptr, const void *col_idx, const double *val, double *ll,
+                       int64_t *info, int fpe, int early_exit);
 /* exblas_exsptrsv_csr_dev on host arrays (x: b on entry, the solution on return): staged through the device, synchronous.
  * Returns 0, hipErrorInvalidValue (also for a negative row_ptr entry) or EXBLAS_SPTRSV_STALLED (see
  * exblas_last_sptrsv_info). */
