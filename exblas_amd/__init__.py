@@ -69,7 +69,16 @@ C_ABI_SYMBOLS = [
     "exblas_last_getrf_batched_info",
     "exblas_exgetrs_batched_dev", "exblas_exgetrs_batched_ctx", "exblas_exgetrs_batched", "exblas_set_getrs_batched_path",
     "exblas_last_getrs_batched_info",
+    "exblas_exsum_lp_dev", "exblas_exdot_lp_dev", "exblas_exsum_lp_accumulate_dev", "exblas_exdot_lp_accumulate_dev",
+    "exblas_exsum_lp_ctx", "exblas_exdot_lp_ctx", "exblas_exsum_lp_accumulate_ctx", "exblas_exdot_lp_accumulate_ctx",
+    "exblas_round_records_dev", "exblas_round_records_ctx", "exblas_round_digits_host", "exblas_exsum_lp",
+    "exblas_exdot_lp",
 ]
+
+# element / target formats of the narrow entries (EXBLAS_DT_* of include/exblas_hip.h), keyed by the dtype's name so
+# that torch and numpy dtypes resolve alike: (code, bytes per element)
+DT_F64, DT_F32, DT_F16, DT_BF16 = 0, 1, 2, 3
+_DT_BY_NAME = {"float64": (DT_F64, 8), "float32": (DT_F32, 4), "float16": (DT_F16, 2), "bfloat16": (DT_BF16, 2)}
 
 # host-transport callback types of include/exblas_hip.h
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.c_int64)
@@ -283,6 +292,19 @@ def load_library():
     L.exblas_set_getrs_batched_path.argtypes = [i32]
     L.exblas_set_getrs_batched_path.restype = None
     L.exblas_last_getrs_batched_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exsum_lp_dev.argtypes = [i32, vp, i64, i64, i32, i32, vp, vp]
+    L.exblas_exdot_lp_dev.argtypes = [i32, vp, i64, vp, i64, i64, i32, i32, vp, vp]
+    L.exblas_exsum_lp_accumulate_dev.argtypes = [i32, vp, i64, i64, i32, i32, vp]
+    L.exblas_exdot_lp_accumulate_dev.argtypes = [i32, vp, i64, vp, i64, i64, i32, i32, vp]
+    L.exblas_exsum_lp_ctx.argtypes = [vp, i32, vp, i64, i64, i32, i32, vp, vp]
+    L.exblas_exdot_lp_ctx.argtypes = [vp, i32, vp, i64, vp, i64, i64, i32, i32, vp, vp]
+    L.exblas_exsum_lp_accumulate_ctx.argtypes = [vp, i32, vp, i64, i64, i32, i32, vp]
+    L.exblas_exdot_lp_accumulate_ctx.argtypes = [vp, i32, vp, i64, vp, i64, i64, i32, i32, vp]
+    L.exblas_round_records_dev.argtypes = [vp, i64, i64, i32, vp, vp]
+    L.exblas_round_records_ctx.argtypes = [vp, vp, i64, i64, i32, vp, vp]
+    L.exblas_round_digits_host.argtypes = [vp, i32, C.POINTER(C.c_uint64)]
+    L.exblas_exsum_lp.argtypes = [i32, vp, i64, i64, i32, i32, vp]
+    L.exblas_exdot_lp.argtypes = [i32, vp, i64, vp, i64, i64, i32, i32, vp]
     L.exblas_exsum_record.argtypes = [i32, vp, i32, i32, i32, i32, vp]
     L.exblas_exdot_record.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, i32, vp]
     _lib = L
@@ -350,7 +372,8 @@ def set_accumulator_slot(slot):
 
 def last_blas1_info():
     """(kernel, grid, group accumulators, compute units) of the last streaming ExSUM / ExDOT launch of the device's
-    default context: kernel 1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 0 before the first launch.
+    default context: kernel 1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 5 narrow ExSUM, 6 narrow strided
+    ExSUM, 7 narrow vector ExDOT, 8 narrow strided ExDOT, 0 before the first launch.
     Host state recorded at launch; does not synchronise."""
     v = (C.c_int * 8)()
     _check(load_library().exblas_last_blas1_info(v), "last_blas1_info")
@@ -1251,6 +1274,31 @@ def csr_diag_blocks_dev(A, p):
     return D
 
 
+def _dt(dtype, who):
+    """(EXBLAS_DT_* code, bytes per element) of a torch / numpy dtype or its name; TypeError for any other"""
+    name = str(dtype).rsplit(".", 1)[-1]
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:
+        pass
+    if name not in _DT_BY_NAME:
+        raise TypeError(f"exblas_amd.{who}: dtype must be float64, float32, float16 or bfloat16, not {dtype}")
+    return _DT_BY_NAME[name]
+
+
+def _lp_operands(who, *tensors):
+    """The checks of the narrow device forms, before any device call: one of the four dtypes (TypeError), the same for
+    every operand (TypeError), CUDA tensors (ValueError).  Returns the EXBLAS_DT_* code."""
+    code = _dt(tensors[0].dtype, who)[0]
+    for t in tensors[1:]:
+        if t.dtype != tensors[0].dtype:
+            raise TypeError(f"exblas_amd.{who}: the operands have different dtypes ({tensors[0].dtype}, {t.dtype})")
+    for t in tensors:
+        if not getattr(t, "is_cuda", False):
+            raise ValueError(f"exblas_amd.{who}: the device forms take CUDA tensors")
+    return code
+
+
 class Context:
     """Owner of an ``exblas_ctx_t *``: private accumulators, flags and workspace on the current device, so that work
     enqueued through different contexts (on different streams) needs no ordering.  Tensors are CUDA float64 / int64 on
@@ -1322,6 +1370,62 @@ class Context:
             out = new_record_buffer()
         _check(load_library().exblas_finish_ctx(self.handle, _stream_ptr(torch), C.c_void_p(out.data_ptr())), "finish")
         return out
+
+    def exsum_lp_accumulate(self, x, fpe=8, early_exit=True, inca=1, n=None):
+        """Phase 1 of exsum_lp: stream a float32 / float16 / bfloat16 (or float64) CUDA tensor into the context
+        accumulators, read at its own width.  Folds with every other accumulate call, the fp64 ones included."""
+        code = _lp_operands("exsum_lp_accumulate", x)
+        torch = _require_gpu()
+        if n is None:
+            n = (x.numel() + inca - 1) // inca
+        _check(load_library().exblas_exsum_lp_accumulate_ctx(self.handle, code, C.c_void_p(x.data_ptr()), n, inca, fpe,
+                                                             int(early_exit), _stream_ptr(torch)), "exsum_lp_accumulate")
+
+    def exdot_lp_accumulate(self, x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None):
+        code = _lp_operands("exdot_lp_accumulate", x, y)
+        torch = _require_gpu()
+        if n is None:
+            n = (x.numel() + incx - 1) // incx
+        _check(load_library().exblas_exdot_lp_accumulate_ctx(self.handle, code, C.c_void_p(x.data_ptr()), incx,
+                                                             C.c_void_p(y.data_ptr()), incy, n, fpe, int(early_exit),
+                                                             _stream_ptr(torch)), "exdot_lp_accumulate")
+
+    def exsum_lp(self, x, fpe=8, early_exit=True, inca=1, n=None, out=None):
+        """ExSUM of a float32 / float16 / bfloat16 (or float64) CUDA tensor, stream-ordered: the record of the exact sum
+        of the widened values -- what exsum(x.double()) returns, without the temporary."""
+        self.exsum_lp_accumulate(x, fpe, early_exit, inca, n)
+        return self.finish(out)
+
+    def exdot_lp(self, x, y, fpe=8, early_exit=True, incx=1, incy=1, n=None, out=None):
+        self.exdot_lp_accumulate(x, y, fpe, early_exit, incx, incy, n)
+        return self.finish(out)
+
+    def round_records(self, records, dtype, out=None):
+        """The exact totals of int64 records ([count, 128], or one record [128]) rounded ONCE into `dtype`: a tensor of
+        that dtype, one element per record (0-d for one record).  Stream-ordered, capturable."""
+        code = _dt(dtype, "round_records")[0]
+        if not getattr(records, "is_cuda", False):
+            raise ValueError("exblas_amd.round_records: the device forms take CUDA tensors")
+        torch = _require_gpu()
+        if records.dtype != torch.int64 or records.dim() not in (1, 2) or records.shape[-1] != OUT_WORDS \
+                or records.stride(-1) != 1:
+            raise ValueError("exblas_amd.round_records: records must be int64 [count, 128] or [128], rows contiguous")
+        count = records.shape[0] if records.dim() == 2 else 1
+        stride = records.stride(0) if records.dim() == 2 else OUT_WORDS
+        tdt = getattr(torch, next(k for k, v in _DT_BY_NAME.items() if v[0] == code))
+        if out is None:
+            out = torch.empty((count,) if records.dim() == 2 else (), dtype=tdt, device=records.device)
+        _check(load_library().exblas_round_records_ctx(self.handle, C.c_void_p(records.data_ptr()), count, stride, code,
+                                                       C.c_void_p(out.data_ptr()), _stream_ptr(torch)), "round_records")
+        return out
+
+    def exsum_to(self, x, dtype=None, fpe=8, early_exit=True):
+        """The exact sum of x rounded once into `dtype` (default: x's own): a 0-d tensor."""
+        return self.round_records(self.exsum_lp(x, fpe, early_exit), x.dtype if dtype is None else dtype)
+
+    def exdot_to(self, x, y, dtype=None, fpe=8, early_exit=True):
+        """The exact dot product of x and y rounded once into `dtype` (default: the operands' own): a 0-d tensor."""
+        return self.round_records(self.exdot_lp(x, y, fpe, early_exit), x.dtype if dtype is None else dtype)
 
     def exgemv(self, trans, m, n, alpha, a, lda, x, beta, y, fpe=0, early_exit=False, incx=1, incy=1):
         torch = _require_gpu()
@@ -1591,6 +1695,9 @@ _default = object.__new__(Context)
 _default.handle = None
 exsum_dev, exdot_dev, finish_dev = _default.exsum, _default.exdot, _default.finish
 exsum_accumulate_dev, exdot_accumulate_dev = _default.exsum_accumulate, _default.exdot_accumulate
+exsum_lp_dev, exdot_lp_dev, round_records_dev = _default.exsum_lp, _default.exdot_lp, _default.round_records
+exsum_lp_accumulate_dev, exdot_lp_accumulate_dev = _default.exsum_lp_accumulate, _default.exdot_lp_accumulate
+exsum_to_dev, exdot_to_dev = _default.exsum_to, _default.exdot_to
 exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.exgemm
 extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
@@ -1686,6 +1793,54 @@ def exdot_record(Ng, ag, inca, offseta, bg, incb, offsetb, fpe, early_exit=False
                                        C.c_void_p(b.ctypes.data), int(incb), int(offsetb), int(fpe),
                                        int(bool(early_exit)), C.c_void_p(out.ctypes.data))
     return Record(out)
+
+
+def _host_lp(a, who):
+    """(EXBLAS_DT_* code, address, keep-alive) of a contiguous numpy array or torch CPU tensor (bfloat16: torch only)"""
+    if hasattr(a, "data_ptr"):
+        if a.is_cuda:
+            raise ValueError(f"exblas_amd.{who}: the host forms take numpy arrays or torch CPU tensors")
+        a = a.contiguous()
+        return _dt(a.dtype, who)[0], a.data_ptr(), a
+    a = np.ascontiguousarray(a)
+    return _dt(a.dtype, who)[0], a.ctypes.data, a
+
+
+def exsum_lp(a, fpe=8, early_exit=True):
+    """ExSUM of a host array of float64 / float32 / float16 (numpy, torch CPU) or bfloat16 (torch CPU): the Record."""
+    code, ptr, keep = _host_lp(a, "exsum_lp")
+    _require_gpu()
+    out = np.zeros(OUT_WORDS, dtype=np.int64)
+    _check(load_library().exblas_exsum_lp(code, C.c_void_p(ptr), keep.size if hasattr(keep, "ctypes") else keep.numel(),
+                                          1, fpe, int(bool(early_exit)), C.c_void_p(out.ctypes.data)), "exsum_lp")
+    return Record(out)
+
+
+def exdot_lp(a, b, fpe=8, early_exit=True):
+    """ExDOT of two host arrays of one of the four dtypes (see exsum_lp): the Record."""
+    code, pa, ka = _host_lp(a, "exdot_lp")
+    codeb, pb, kb = _host_lp(b, "exdot_lp")
+    if code != codeb:
+        raise TypeError("exblas_amd.exdot_lp: the operands have different dtypes")
+    na, nb = (k.size if hasattr(k, "ctypes") else k.numel() for k in (ka, kb))
+    if na != nb:
+        raise ValueError("exblas_amd.exdot_lp: the operands have different lengths")
+    _require_gpu()
+    out = np.zeros(OUT_WORDS, dtype=np.int64)
+    _check(load_library().exblas_exdot_lp(code, C.c_void_p(pa), 1, C.c_void_p(pb), 1, na, fpe, int(bool(early_exit)),
+                                          C.c_void_p(out.ctypes.data)), "exdot_lp")
+    return Record(out)
+
+
+def round_digits_host(digits, dtype):
+    """The 68 normalised digits of a record rounded once into `dtype`, on the CPU (no device): the bit pattern, an int."""
+    code = _dt(dtype, "round_digits_host")[0]
+    d = np.ascontiguousarray(digits, dtype=np.int64)
+    if d.shape != (NDIGITS,):
+        raise ValueError("exblas_amd.round_digits_host: 68 digits expected")
+    bits = C.c_uint64()
+    _check(load_library().exblas_round_digits_host(C.c_void_p(d.ctypes.data), code, C.byref(bits)), "round_digits_host")
+    return int(bits.value)
 
 
 def exgemv(transa, m, n, alpha, a, lda, offseta, x, incx, offsetx, beta, y, incy, offsety, fpe, early_exit=False):

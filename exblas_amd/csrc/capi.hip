@@ -18,6 +18,7 @@
 #include "../../include/blas3.hpp"
 #include "exblas_internal.h"
 #include "superacc.hip.h"
+#include "round_lowp.hip.h"
 
 #include <cmath>
 #include <cstdio>
@@ -97,6 +98,8 @@ static void init_ctx(Ctx &c, int device, int layer)
     c.bpc_dot = env_int("EXBLAS_BPC_DOT", 48);
     c.bpc_sa = env_int("EXBLAS_BPC_SA", 3);
     c.bpc_heavy = env_int("EXBLAS_BPC_HEAVY", 4);
+    c.bpc_lp_sum = env_int("EXBLAS_BPC_LP_SUM", c.bpc_lp_sum);
+    c.bpc_lp_dot = env_int("EXBLAS_BPC_LP_DOT", c.bpc_lp_dot);
     c.ngroups = env_int("EXBLAS_NGROUPS", 32);
     c.grid_adj = env_int("EXBLAS_GRID_ADJ", 0);
     if (c.ngroups < 1) c.ngroups = 1;
@@ -235,7 +238,7 @@ int exblas_set_tuning(int blocks_per_cu, int ngroups, int variant)
     // fails instead of timing the one production kernel under a variant's name.
     if (variant != -1 && variant != 0) return (int)hipErrorInvalidValue;
     for_each_layer([&](Ctx &c) {
-        if (blocks_per_cu > 0) c.blocks_per_cu = c.bpc_sum = c.bpc_dot = c.bpc_sa = c.bpc_heavy = blocks_per_cu;
+        if (blocks_per_cu > 0) c.blocks_per_cu = c.bpc_sum = c.bpc_dot = c.bpc_sa = c.bpc_heavy = c.bpc_lp_sum = c.bpc_lp_dot = blocks_per_cu;
         if (ngroups > 0 && ngroups != c.ngroups) {
             EXB_CHECK(hipDeviceSynchronize());
             c.ngroups = ngroups;
@@ -307,7 +310,7 @@ int exblas_last_gemm_slices(void)
 }
 
 // The last streaming ExSUM / ExDOT launch of the current device's default context (the *_dev entry points): out[0] the
-// kernel (1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided; 0: none yet), out[1] its grid, out[2] the group
+// kernel (1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 5 .. 8 the same of blas1_lowp.hip; 0: none yet), out[1] its grid, out[2] the group
 // accumulators, out[3] the compute units the geometry was sized for, out[4..7] reserved.  Host state only: nothing is
 // read from the device and nothing synchronises.
 int exblas_last_blas1_info(int *out)
@@ -472,6 +475,42 @@ static int finish_on(Ctx &c, hipStream_t st, int64_t *d_out)
 {
     std::lock_guard<std::mutex> lk(c.mu);
     return (int)finalize_groups(c, st, (long long *)d_out);
+}
+
+// The narrow-input forms (blas1_lowp.hip).  What they refuse is decided from the arguments alone, before any context is
+// looked up: 0, or hipErrorInvalidValue.  b == nullptr with incb == 1: ExSUM.
+static int lp_refused(int dtype, const void *a, int64_t inca, const void *b, int64_t incb, int64_t n, int fpe)
+{
+    if (!dtype_known(dtype) || fpe < 0 || fpe > 8 || inca < 1 || incb < 1 || n < 0 || n > 0x7fffffffll)
+        return (int)hipErrorInvalidValue;
+    const uintptr_t mask = (uintptr_t)dtype_bytes(dtype) - 1;
+    return (((uintptr_t)a | (uintptr_t)b) & mask) ? (int)hipErrorInvalidValue : 0;
+}
+
+static int exsum_lp_accumulate_on(Ctx &c, int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
+                                  hipStream_t st)
+{
+    if (int rc = lp_refused(dtype, d_a, inca, nullptr, 1, n, fpe)) return rc;
+    if (dtype == DT_F64) return exsum_accumulate_on(c, (const double *)d_a, n, inca, fpe, early_exit, st);
+    std::lock_guard<std::mutex> lk(c.mu);
+    return n > 0 ? (int)exsum_lp_dispatch(c, dtype, d_a, n, inca, fpe, st) : 0;
+}
+
+static int exdot_lp_accumulate_on(Ctx &c, int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb,
+                                  int64_t n, int fpe, int early_exit, hipStream_t st)
+{
+    if (int rc = lp_refused(dtype, d_a, inca, d_b, incb, n, fpe)) return rc;
+    if (dtype == DT_F64)
+        return exdot_accumulate_on(c, (const double *)d_a, inca, (const double *)d_b, incb, n, fpe, early_exit, st);
+    std::lock_guard<std::mutex> lk(c.mu);
+    return n > 0 ? (int)exdot_lp_dispatch(c, dtype, d_a, inca, d_b, incb, n, fpe, st) : 0;
+}
+
+static int round_records_refused(const int64_t *d_records, int64_t count, int64_t stride_words, int dtype, const void *d_out)
+{
+    const bool bad = !dtype_known(dtype) || count < 0 || (count > 1 && stride_words < OUT_WORDS) ||
+                     (count > 0 && (!d_records || !d_out));
+    return bad ? (int)hipErrorInvalidValue : 0;
 }
 
 static int exgemv_on(Ctx &c, char transa, int m, int n, double alpha, const double *d_a, int lda, const double *d_x,
@@ -990,6 +1029,56 @@ int exblas_exdot_ctx(exblas_ctx_t *h, const double *d_a, int64_t inca, const dou
     return rc ? rc : finish_on(*cp, (hipStream_t)stream, d_out);
 }
 
+// (the refusals come first: a refused call must not create the default context)
+int exblas_exsum_lp_accumulate_ctx(exblas_ctx_t *h, int dtype, const void *d_a, int64_t n, int64_t inca, int fpe,
+                                   int early_exit, void *stream)
+{
+    if (int rc = lp_refused(dtype, d_a, inca, nullptr, 1, n, fpe)) return rc;
+    EXB_HANDLE(h);
+    return exsum_lp_accumulate_on(*cp, dtype, d_a, n, inca, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_exdot_lp_accumulate_ctx(exblas_ctx_t *h, int dtype, const void *d_a, int64_t inca, const void *d_b,
+                                   int64_t incb, int64_t n, int fpe, int early_exit, void *stream)
+{
+    if (int rc = lp_refused(dtype, d_a, inca, d_b, incb, n, fpe)) return rc;
+    EXB_HANDLE(h);
+    return exdot_lp_accumulate_on(*cp, dtype, d_a, inca, d_b, incb, n, fpe, early_exit, (hipStream_t)stream);
+}
+
+int exblas_exsum_lp_ctx(exblas_ctx_t *h, int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
+                        void *stream, int64_t *d_out)
+{
+    int rc = exblas_exsum_lp_accumulate_ctx(h, dtype, d_a, n, inca, fpe, early_exit, stream);
+    return rc ? rc : exblas_finish_ctx(h, stream, d_out);
+}
+
+int exblas_exdot_lp_ctx(exblas_ctx_t *h, int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb,
+                        int64_t n, int fpe, int early_exit, void *stream, int64_t *d_out)
+{
+    int rc = exblas_exdot_lp_accumulate_ctx(h, dtype, d_a, inca, d_b, incb, n, fpe, early_exit, stream);
+    return rc ? rc : exblas_finish_ctx(h, stream, d_out);
+}
+
+// (no state of the context is used: the handle only says which device the pointers belong to)
+int exblas_round_records_ctx(exblas_ctx_t *h, const int64_t *d_records, int64_t count, int64_t stride_words, int dtype,
+                             void *d_out, void *stream)
+{
+    if (int rc = round_records_refused(d_records, count, stride_words, dtype, d_out)) return rc;
+    if (count == 0) return 0;
+    EXB_HANDLE(h);
+    return (int)round_records_dispatch((const long long *)d_records, count, stride_words, dtype, d_out, (hipStream_t)stream);
+}
+
+int exblas_round_digits_host(const int64_t *digits68, int dtype, uint64_t *bits)
+{
+    if (!digits68 || !bits || !dtype_known(dtype)) return (int)hipErrorInvalidValue;
+    long long v[NL];
+    for (int i = 0; i < NL; ++i) v[i] = digits68[i];
+    *bits = round_digits_to(v, dtype);
+    return 0;
+}
+
 int exblas_exgemv_ctx(exblas_ctx_t *h, char transa, int m, int n, double alpha, const double *d_a, int lda,
                       const double *d_x, int incx, double beta, double *d_y, int incy, int fpe, int early_exit,
                       void *stream)
@@ -1215,6 +1304,30 @@ int exblas_exdot_dev(const double *d_a, int64_t inca, const double *d_b, int64_t
                      int early_exit, void *stream, int64_t *d_out)
 {
     return exblas_exdot_ctx(nullptr, d_a, inca, d_b, incb, n, fpe, early_exit, stream, d_out);
+}
+int exblas_exsum_lp_accumulate_dev(int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream)
+{
+    return exblas_exsum_lp_accumulate_ctx(nullptr, dtype, d_a, n, inca, fpe, early_exit, stream);
+}
+int exblas_exdot_lp_accumulate_dev(int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb, int64_t n,
+                                   int fpe, int early_exit, void *stream)
+{
+    return exblas_exdot_lp_accumulate_ctx(nullptr, dtype, d_a, inca, d_b, incb, n, fpe, early_exit, stream);
+}
+int exblas_exsum_lp_dev(int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream,
+                        int64_t *d_out)
+{
+    return exblas_exsum_lp_ctx(nullptr, dtype, d_a, n, inca, fpe, early_exit, stream, d_out);
+}
+int exblas_exdot_lp_dev(int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb, int64_t n, int fpe,
+                        int early_exit, void *stream, int64_t *d_out)
+{
+    return exblas_exdot_lp_ctx(nullptr, dtype, d_a, inca, d_b, incb, n, fpe, early_exit, stream, d_out);
+}
+int exblas_round_records_dev(const int64_t *d_records, int64_t count, int64_t stride_words, int dtype, void *d_out,
+                             void *stream)
+{
+    return exblas_round_records_ctx(nullptr, d_records, count, stride_words, dtype, d_out, stream);
 }
 int exblas_exgemv_dev(char transa, int m, int n, double alpha, const double *d_a, int lda, const double *d_x,
                       int incx, double beta, double *d_y, int incy, int fpe, int early_exit, void *stream)
@@ -1622,6 +1735,36 @@ int exblas_exdot_record(int Ng, const double *ag, int inca, int offseta, const d
     host_reduce(Ng > 0 ? Ng : 0, ag + offseta, inca > 0 ? inca : 1, bg + offsetb, incb > 0 ? incb : 1, fpe, early_exit,
                 out_words);
     return 0;
+}
+
+// Narrow ExSUM / ExDOT on host arrays: staged to the current device, the same *_on body, one device (b == nullptr: ExSUM)
+static int host_lp(const char *who, int dtype, const void *a, int64_t inca, const void *b, int64_t incb, int64_t n, int fpe,
+                   int early_exit, int64_t *out_words)
+{
+    if (int rc = lp_refused(dtype, a, inca, b, incb, n, fpe)) return rc;
+    if (!out_words) return (int)hipErrorInvalidValue;
+    HostCall hc(who);
+    Ctx &c = hc.c;
+    const size_t es = (size_t)dtype_bytes(dtype);
+    const size_t abytes = n > 0 ? ((size_t)(n - 1) * (size_t)inca + 1) * es : 0;
+    const size_t bbytes = (b && n > 0) ? ((size_t)(n - 1) * (size_t)incb + 1) * es : 0;
+    const void *da = hc.in(0, abytes, a, abytes), *db = b ? hc.in(1, bbytes, b, bbytes) : nullptr;
+    int rc = b ? exdot_lp_accumulate_on(c, dtype, da, inca, db, incb, n, fpe, early_exit, c.stream)
+               : exsum_lp_accumulate_on(c, dtype, da, n, inca, fpe, early_exit, c.stream);
+    if (!rc) rc = finish_on(c, c.stream, (int64_t *)c.d_record);
+    return hc.out(rc, out_words, c.d_record, sizeof(long long) * OUT_WORDS);
+}
+
+int exblas_exsum_lp(int dtype, const void *a, int64_t n, int64_t inca, int fpe, int early_exit, int64_t *out_words)
+{
+    return host_lp("exblas_exsum_lp", dtype, a, inca, nullptr, 1, n, fpe, early_exit, out_words);
+}
+
+int exblas_exdot_lp(int dtype, const void *a, int64_t inca, const void *b, int64_t incb, int64_t n, int fpe, int early_exit,
+                    int64_t *out_words)
+{
+    if (!b) return (int)hipErrorInvalidValue;
+    return host_lp("exblas_exdot_lp", dtype, a, inca, b, incb, n, fpe, early_exit, out_words);
 }
 
 static double record_value(const int64_t *rec)

@@ -17,6 +17,12 @@ struct CtxKnobs {
     // blocks (2 per CU: 7.15 TB/s vs 6.46 at 8), the two-stream ExDOT kernel with many (16-32 per CU).
     int bpc_sum = 2, bpc_dot = 48;   // ExDOT: 48 (an odd grid of 12289 workgroups) edges out 32 by ~1 %, 16 and 96 lose 2-3 %
     int bpc_sa = 3;          // superaccumulator-only ExSUM (LDS-atomic bound; 3/CU: 6.65 TB/s, 2/CU: 6.0)
+    // The narrow-input kernels (blas1_lowp.hip; EXBLAS_BPC_LP_SUM / EXBLAS_BPC_LP_DOT; exblas_set_tuning sets them too).
+    // Measured at n = 2^28 (tools/bench_lowp.py --sweep, profiles/lowp_sweep.jsonl): they convert and run the cascade on
+    // 2 to 4 times the elements per byte, so they want more waves than the fp64 kernels -- ExSUM float32 0.193 ms at 2 per
+    // CU, 0.176 at 8 to 16, 0.179 from 24 on; bfloat16 0.181 / 0.154 / 0.156; ExDOT float32 0.354 at 4, 0.321 at 16 to 32,
+    // float16 0.217 / 0.193 to 0.196 at 8 to 16 / 0.200 at 48
+    int bpc_lp_sum = 16, bpc_lp_dot = 16;
     int bpc_heavy = 4;       // ExSUM variants without early exit, N >= 5, in -DEXBLAS_FULL_CASCADE=1 builds only (VALU-latency-bound)
     int ngroups = 32;        // EXBLAS_NGROUPS: global group accumulators the blocks add into
     int grid_adj = 0;        // EXBLAS_GRID_ADJ: workgroups added to the grid of the streaming ExSUM / ExDOT kernels
@@ -186,7 +192,11 @@ struct GemmChunks;
 
 // blas1.hip
 // Ctx::last_blas1_kernel: which streaming kernel the last ExSUM / ExDOT launch of the context was
-enum { BLAS1_K_EXSUM = 1, BLAS1_K_EXSUM_STRIDED = 2, BLAS1_K_EXDOT = 3, BLAS1_K_EXDOT_STRIDED = 4 };
+enum {
+    BLAS1_K_EXSUM = 1, BLAS1_K_EXSUM_STRIDED = 2, BLAS1_K_EXDOT = 3, BLAS1_K_EXDOT_STRIDED = 4,
+    // blas1_lowp.hip: float32 / float16 / bfloat16 inputs
+    BLAS1_K_EXSUM_LP = 5, BLAS1_K_EXSUM_LP_STRIDED = 6, BLAS1_K_EXDOT_LP = 7, BLAS1_K_EXDOT_LP_STRIDED = 8
+};
 hipError_t exsum_dispatch(Ctx &c, const double *a, long long n, long long inca, int fpe, int early_exit,
                           hipStream_t st);
 hipError_t exdot_dispatch(Ctx &c, const double *a, long long inca, const double *b, long long incb, long long n,
@@ -196,6 +206,13 @@ hipError_t exsum_segmented_dispatch(const double *values, const long long *offse
 hipError_t finalize_groups(Ctx &c, hipStream_t st, long long *d_out, long long *d_ext_out = nullptr);
 hipError_t finalize_sets(const long long *d_sets, int nsets, unsigned flags_or, hipStream_t st, long long *d_out,
                          const long long *d_ext_sets = nullptr);
+// blas1_lowp.hip: dtype is DT_F32 / DT_F16 / DT_BF16 (round_lowp.hip.h) and fpe 0..8, both checked by the caller; the
+// kernels add into the same accumulators as the fp64 ones.  round_records_dispatch: any of the four formats.
+hipError_t exsum_lp_dispatch(Ctx &c, int dtype, const void *a, long long n, long long inca, int fpe, hipStream_t st);
+hipError_t exdot_lp_dispatch(Ctx &c, int dtype, const void *a, long long inca, const void *b, long long incb, long long n,
+                             int fpe, hipStream_t st);
+hipError_t round_records_dispatch(const long long *d_records, long long count, long long stride_words, int dtype,
+                                  void *d_out, hipStream_t st);
 // the *_dev layer's context of the current device (comm.hip finishes its accumulators with exported low / high sets)
 Ctx &default_ctx();
 

@@ -124,7 +124,9 @@ void exblas_set_gemm_max_moduli(int l);
 int exblas_last_gemm_info(int *out8);
 /* The most recent streaming ExSUM / ExDOT launch of this device's default context (the *_dev entry points and
  * exblas_*_ctx with a NULL handle): out[0] = kernel (1 contiguous ExSUM, 2 strided ExSUM, 3 contiguous 16-byte-aligned
- * ExDOT, 4 strided or misaligned ExDOT, 0 nothing launched yet), out[1] = workgroups launched, out[2] = group
+ * ExDOT, 4 strided or misaligned ExDOT; the narrow-input kernels: 5 contiguous ExSUM, 6 strided ExSUM, 7 vector ExDOT
+ * (both operands equally misaligned modulo 16 bytes), 8 strided or unequally misaligned ExDOT; 0 nothing launched
+ * yet), out[1] = workgroups launched, out[2] = group
  * accumulators (EXBLAS_NGROUPS / exblas_set_tuning), out[3] = compute units the geometry is sized for, out[4..7] = 0.
  * Recorded on the host at launch: no synchronisation, nothing read from the device.  For tests and tuning tools that
  * must know which launch geometry a size took.  Returns 0 or hipErrorInvalidValue (out8 NULL). */
@@ -187,6 +189,51 @@ int exblas_exsum_accumulate_dev(const double *d_a, int64_t n, int64_t inca, int 
 int exblas_exdot_accumulate_dev(const double *d_a, int64_t inca, const double *d_b, int64_t incb,
                                 int64_t n, int fpe, int early_exit, void *stream);
 int exblas_finish_dev(void *stream, int64_t *d_out);
+/* ---- narrow inputs: ExSUM / ExDOT on float32, float16 and bfloat16 arrays, and one rounding into a narrow format ----
+ * dtype names the element type of d_a (and d_b: both operands of ExDOT have the same type); bfloat16 is the raw 16-bit
+ * word (the upper half of a float32).  Every such value widens to a double exactly and the product of two of them is
+ * an exact double, so these entries compute the same exact total as the fp64 entries on the widened data -- the same
+ * 128-word record, every field with the same meaning, EXBLAS_OUT_EXACT still the correctly rounded DOUBLE -- while
+ * reading the data at its own width, with no temporary.  Flag bits 3 to 6 are never set: a product of two narrow
+ * values lies in [2^-298, 2^256) or is zero.  The kernels add into the same context accumulators as the fp64 ones: narrow
+ * and fp64 *_accumulate calls between two exblas_finish_dev calls fold into ONE exact reduction, and the multi-rank
+ * finish (exblas_allreduce_finish_dev) serves them unchanged.
+ * fpe: 0 to 8.  0 and 1 run the superaccumulators alone, 2 to 4 an expansion of 4 and 5 to 8 an expansion of 8, both
+ * with the per-tile early exit; early_exit is accepted for symmetry and changes nothing (the bits cannot depend on
+ * either).  EXBLAS_DT_F64 forwards to the fp64 entry: the same record.  Refused with hipErrorInvalidValue (1) before the
+ * device is touched: an unknown dtype, fpe outside 0..8, an increment < 1, n < 0, n >= 2^31, a pointer that is not a
+ * multiple of the element size.  n == 0 launches nothing and yields the zero record.  The pointers need only be
+ * element-aligned; ExDOT streams 16-byte vectors when d_a and d_b are equally misaligned modulo 16 bytes and takes
+ * the (slower) strided kernel otherwise. */
+#define EXBLAS_DT_F64 0
+#define EXBLAS_DT_F32 1
+#define EXBLAS_DT_F16 2
+#define EXBLAS_DT_BF16 3
+int exblas_exsum_lp_dev(int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit, void *stream,
+                        int64_t *d_out);
+int exblas_exdot_lp_dev(int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb, int64_t n, int fpe,
+                        int early_exit, void *stream, int64_t *d_out);
+int exblas_exsum_lp_accumulate_dev(int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
+                                   void *stream);
+int exblas_exdot_lp_accumulate_dev(int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb, int64_t n,
+                                   int fpe, int early_exit, void *stream);
+/* d_out[i] = the exact total of record i, rounded ONCE (to nearest, ties to even) into `dtype`: one element of that
+ * format per record (8, 4 or 2 bytes), i < count; record i is the EXBLAS_OUT_WORDS words at d_records +
+ * i * stride_words (stride_words >= EXBLAS_OUT_WORDS when count > 1).  A record whose flags word has one of bits 0 to 2
+ * set yields its EXBLAS_OUT_EXACT double converted to the format (+-Inf and NaN convert exactly); every other record
+ * yields the rounding of its 68 digits (words [48, 116)): subnormal results, the carry into the next binade and the
+ * overflow to +-Inf (float16 from 65520 on, float32 / bfloat16 from 2^128 - 2^103 / 2^128 - 2^119 on) included; an
+ * exact zero gives +0.  Rounding the record's double instead would round twice and go wrong on near-ties.  With
+ * EXBLAS_DT_F64 the output equals word EXBLAS_OUT_EXACT.  Limit: a record that carries
+ * EXBLAS_FLAG_PRODUCT_UNDERFLOW (an fp64 ExDOT) has a fraction below 2^-1074 that the digits do not hold; this routine
+ * rounds the value of the digits.  Narrow-input reductions never set that bit.  Refused with hipErrorInvalidValue: an
+ * unknown dtype, count < 0, a stride below EXBLAS_OUT_WORDS with count > 1, a NULL pointer with count > 0. */
+int exblas_round_records_dev(const int64_t *d_records, int64_t count, int64_t stride_words, int dtype, void *d_out,
+                             void *stream);
+/* The same rounding of ONE digit set (68 normalised digits: digits 0..66 in [0, 2^32), the top one signed) on the CPU;
+ * no device is touched.  *bits receives the pattern in its low 64 / 32 / 16 bits.  hipErrorInvalidValue for an unknown
+ * dtype or a NULL pointer. */
+int exblas_round_digits_host(const int64_t *digits68, int dtype, uint64_t *bits);
 /* The context owns TWO accumulator sets.  *_accumulate_dev and exblas_finish_dev act on the selected one
  * (0 by default).  A caller that pipelines independent reductions alternates the slot per reduction and runs
  * exblas_finish_dev on a second stream (ordered by events), so that the finalize of reduction i overlaps the
@@ -837,6 +884,17 @@ int exblas_exsum_accumulate_ctx(exblas_ctx_t *ctx, const double *d_a, int64_t n,
 int exblas_exdot_accumulate_ctx(exblas_ctx_t *ctx, const double *d_a, int64_t inca, const double *d_b, int64_t incb,
                                 int64_t n, int fpe, int early_exit, void *stream);
 int exblas_finish_ctx(exblas_ctx_t *ctx, void *stream, int64_t *d_out);
+/* the narrow-input entries (see exblas_exsum_lp_dev) on a handle */
+int exblas_exsum_lp_ctx(exblas_ctx_t *ctx, int dtype, const void *d_a, int64_t n, int64_t inca, int fpe, int early_exit,
+                        void *stream, int64_t *d_out);
+int exblas_exdot_lp_ctx(exblas_ctx_t *ctx, int dtype, const void *d_a, int64_t inca, const void *d_b, int64_t incb,
+                        int64_t n, int fpe, int early_exit, void *stream, int64_t *d_out);
+int exblas_exsum_lp_accumulate_ctx(exblas_ctx_t *ctx, int dtype, const void *d_a, int64_t n, int64_t inca, int fpe,
+                                   int early_exit, void *stream);
+int exblas_exdot_lp_accumulate_ctx(exblas_ctx_t *ctx, int dtype, const void *d_a, int64_t inca, const void *d_b,
+                                   int64_t incb, int64_t n, int fpe, int early_exit, void *stream);
+int exblas_round_records_ctx(exblas_ctx_t *ctx, const int64_t *d_records, int64_t count, int64_t stride_words, int dtype,
+                             void *d_out, void *stream);
 int exblas_exgemv_ctx(exblas_ctx_t *ctx, char transa, int m, int n, double alpha, const double *d_a, int lda,
                       const double *d_x, int incx, double beta, double *d_y, int incy, int fpe, int early_exit,
                       void *stream);
@@ -1093,6 +1151,12 @@ int exblas_exsum_record(int Ng, const double *ag, int inca, int offset, int fpe,
 int exblas_exdot_record(int Ng, const double *ag, int inca, int offseta, const double *bg, int incb,
                         int offsetb, int fpe, int early_exit, int64_t *out_words);
 
+/* Narrow ExSUM / ExDOT on HOST arrays (see exblas_exsum_lp_dev): the arrays are staged to the current device and the
+ * same routine runs there; out_words receives the record.  One device (the fp64 host entries spread over several).
+ * The argument refusals of the device entries apply, before the device is touched. */
+int exblas_exsum_lp(int dtype, const void *a, int64_t n, int64_t inca, int fpe, int early_exit, int64_t *out_words);
+int exblas_exdot_lp(int dtype, const void *a, int64_t inca, const void *b, int64_t incb, int64_t n, int fpe,
+                    int early_exit, int64_t *out_words);
 #ifdef __cplusplus
 }
 #endif
