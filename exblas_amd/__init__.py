@@ -372,8 +372,9 @@ def set_accumulator_slot(slot):
 
 def last_blas1_info():
     """(kernel, grid, group accumulators, compute units) of the last streaming ExSUM / ExDOT launch of the device's
-    default context: kernel 1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 5 narrow ExSUM, 6 narrow strided
-    ExSUM, 7 narrow vector ExDOT, 8 narrow strided ExDOT, 0 before the first launch.
+    default context: kernel 1 fp64 ExSUM on k_blas1_stream, 2 on k_blas1_strided, 3 fp64 vector ExDOT (k_blas1_stream),
+    4 fp64 strided ExDOT (k_blas1_strided), 5 narrow ExSUM, 6 narrow strided ExSUM, 7 narrow vector ExDOT, 8 narrow strided
+    ExDOT, 0 before the first launch.
     Host state recorded at launch; does not synchronise."""
     v = (C.c_int * 8)()
     _check(load_library().exblas_last_blas1_info(v), "last_blas1_info")

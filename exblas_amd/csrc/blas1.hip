@@ -2,7 +2,9 @@
 //
 // Replaces the reference's OpenCL kernels ExSUM/ExSUMComplete (src/gpu/blas/blas1/ExSUM.Superacc.cl:211-356,
 // ExSUM.FPE.cl:230-388, ExSUM.FPE.EX.{4,6,8}.cl) and ExDOT/ExDOTComplete (ExDOT.Superacc.cl:217-359,
-// ExDOT.FPE.cl:201-345) -- behaviour only; the structure is ours:
+// ExDOT.FPE.cl:201-345) -- behaviour only; the structure is ours.  This file holds the fp64 front ends (SumF64, DotF64),
+// the finalize and the segmented ExSUM.  The loop itself is k_blas1_stream / k_blas1_strided of blas1_common.hip.h,
+// and with these front ends it works like this:
 //   * every lane streams 16-byte (double2) coalesced, non-temporal loads, U of them in flight per tile, and the
 //     next tile is already on its way into a second register set while the current one is absorbed;
 //   * a register-resident floating-point expansion of NFPE doubles absorbs the elements with Knuth
@@ -19,247 +21,70 @@
 
 namespace exb {
 
-constexpr int U = 4;   // double2 loads per lane and stream in one tile of k_exsum / k_exdot
+#ifndef EXBLAS_SUM_COPIES
+#define EXBLAS_SUM_COPIES 8
+#endif
+#ifndef EXBLAS_DOT_COPIES
+#define EXBLAS_DOT_COPIES 8
+#endif
 
 // ---------------------------------------------------------------------------------------------
-// ExSUM, contiguous input
+// the fp64 front ends of k_blas1_stream / k_blas1_strided (blas1_common.hip.h)
 // ---------------------------------------------------------------------------------------------
-template <int N, bool EE, int COPIES>
-__global__ void __launch_bounds__(BLOCK) k_exsum(const double *__restrict__ a, long long n,
-                                                 long long *__restrict__ gacc,
-                                                 unsigned *__restrict__ gflags, int ngroups)
-{
-    __shared__ long long s_acc[WAVES * NL * COPIES];
-    auto zero_lds = [&]() {   // (after the first tile's loads are in flight, see k_exdot)
-        for (int i = threadIdx.x; i < WAVES * NL * COPIES; i += BLOCK) s_acc[i] = 0;
-        __syncthreads();
-    };
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    long long *col = s_acc + wave * NL * COPIES + (lane & (COPIES - 1));
-    unsigned flags = 0;
-    double fpe[N > 0 ? N : 1];
-#pragma unroll
-    for (int i = 0; i < (N > 0 ? N : 1); ++i) fpe[i] = 0.0;
+// a lane's 16-byte load is a double2 (loaded through a generic 4 x 32-bit vector and rebuilt from halves, the doubles
+// cost 9 more VGPRs)
+struct F64 {
+    typedef double elem;
+    typedef d2_t vec;
+    static constexpr int VEC = 2;
+    static __device__ __forceinline__ double widen(elem v) { return v; }
+    static __device__ __forceinline__ double at(const vec &r, int j) { return j ? r.y : r.x; }
+};
 
-    // 16-byte alignment: at most one scalar head element
-    const long long head = (((uintptr_t)a & 8u) && n > 0) ? 1 : 0;
-    const d2_t *v = (const d2_t *)(a + head);
-    const long long nv = (n - head) >> 1;
-    constexpr long long TILE = (long long)BLOCK * U;
-    const long long ntiles = nv / TILE;
-    LdsSink<COPIES> sinkm{col, flags};
-    Bypass bypass;
+struct SumF64 : ExactOp<F64, 1> {
+    static constexpr int COPIES = EXBLAS_SUM_COPIES, K_STREAM = BLAS1_K_EXSUM, K_STRIDED = BLAS1_K_EXSUM_STRIDED;
+    // resident blocks per CU: the HBM-bound kernels want few fat blocks; the variants that run the full N-level cascade
+    // on every element (no early exit, N >= 5: 30-48 dependent fp64 adds per element) are VALU-latency-bound and want
+    // more waves per SIMD to hide it
+    template <int N, bool EE>
+    static int bpc(const Ctx &c)
+    {
+        return N == 0 ? c.bpc_sa : ((!SKIP_ZERO_LEVELS<EE> && N >= 5) ? c.bpc_heavy : c.bpc_sum);
+    }
+};
 
-    // register double-buffering: the next tile's loads are in flight while this one is absorbed.  Tile t goes to
-    // workgroup t mod grid: the grid sweeps one compact window of addresses.
-    long long t = blockIdx.x;
-    if (t < ntiles) {
-        // two explicit register sets, filled alternately with unconditional loads (past the end: the last tile
-        // again) -- see k_exdot: no per-trip copies between the sets, both in flight
-        d2_t r0[U], r1[U];
-        auto fill = [&](long long tile, d2_t (&r)[U]) {
-            const d2_t *p = v + (tile < ntiles ? tile : ntiles - 1) * TILE + threadIdx.x;
+// ExDOT: TwoProductFMA front-end (ExDOT.Superacc.cl:25-29, :244-253); the rounding error of the product enters the
+// expansion at slot max(N-3,0) like ExDOT.FPE.cl:254.  Products below 2^-968 / beyond the double range have their exact
+// homes in the context's low / high accumulators (prod_range_divert, which replaces the range guard: GUARD = false).
+struct DotF64 : F64 {
+    static constexpr int STREAMS = 2;
+    static constexpr int COPIES = EXBLAS_DOT_COPIES, K_STREAM = BLAS1_K_EXDOT, K_STRIDED = BLAS1_K_EXDOT_STRIDED;
+    template <int N, bool EE>
+    static int bpc(const Ctx &c) { return c.bpc_dot; }
+    // vectors only when BOTH streams are 16-byte aligned
+    static bool can_stream(const double *a, const double *b) { return (((uintptr_t)a | (uintptr_t)b) & 15u) == 0; }
+    // x becomes the products, e their TwoProd errors; true: the group was diverted as a whole (prod_range_divert)
+    template <int N, int COPIES, int CNT>
+    static __device__ __forceinline__ bool divert(double (&fpe)[N > 0 ? N : 1], Lane<COPIES> &L, double (&x)[CNT],
+                                                  const double (&y)[CNT], double (&e)[CNT])
+    {
+        LdsSink<COPIES> sink = L.sink();
+        double a[CNT];
 #pragma unroll
-            for (int u = 0; u < U; ++u) r[u] = ld2(p + u * BLOCK);
-        };
-        auto absorb = [&](d2_t (&r)[U]) {
-            double x[2 * U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                x[2 * u] = r[u].x;
-                x[2 * u + 1] = r[u].y;
-            }
-            fpe_absorb_adaptive<N, EE, 2 * U, LdsSink<COPIES>>(fpe, x, sinkm, bypass);
-        };
-        fill(t, r0);
-        zero_lds();
-        for (;;) {
-            fill(t + gridDim.x, r1);
-            absorb(r0);
-            t += gridDim.x;
-            if (t >= ntiles) break;
-            fill(t + gridDim.x, r0);
-            absorb(r1);
-            t += gridDim.x;
-            if (t >= ntiles) break;
-        }
-    } else {
-        zero_lds();
+        for (int j = 0; j < CNT; ++j) a[j] = x[j], x[j] = two_prod(a[j], y[j], e[j]);
+        return prod_range_divert<CNT>(fpe[0], x, e, sink, low_acc_of(L.gflags), high_acc_of(L.gflags),
+                                      [&](int j) { return a[j]; }, [&](int j) { return y[j]; });
     }
-    // remainder vectors, grid-strided one double2 at a time
-    for (long long i = ntiles * TILE + (long long)blockIdx.x * BLOCK + threadIdx.x; i < nv;
-         i += (long long)gridDim.x * BLOCK) {
-        d2_t r = v[i];
-        double x[2] = {r.x, r.y};
-        fpe_absorb<N, false, COPIES, 2>(fpe, x, 0, col, flags);
+    template <Feed M, int N, bool EE, int COPIES, int ZM, int CNT>
+    static __device__ __forceinline__ void absorb(double (&fpe)[N > 0 ? N : 1], Lane<COPIES> &L, double (&p)[CNT],
+                                                  double (&e)[CNT])
+    {
+        LdsSink<COPIES> sink = L.sink();
+        if constexpr (M == ONE) sink_product(sink, p[0], e[0]);
+        else if constexpr (M == HOT) fpe_absorb_prod_adaptive<N, EE, CNT, LdsSink<COPIES>, ZM, false>(fpe, p, e, sink, L.bypass);
+        else fpe_absorb_prod<N, false, CNT, LdsSink<COPIES>, 0, false>(fpe, p, e, sink);
     }
-    // scalar head / tail straight into the superaccumulator
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (head) lds_add<COPIES>(col, a[0], flags);
-        if ((n - head) & 1) lds_add<COPIES>(col, a[n - 1], flags);
-    }
-    fpe_flush<N, COPIES>(fpe, col, flags);
-    block_epilogue<COPIES>(s_acc, flags, gacc, gflags, ngroups);
-}
-
-// ExSUM, strided input a[i*inca] (ExSUM.Superacc.cl:248-264 takes the same slow path)
-template <int N, bool EE, int COPIES>
-__global__ void __launch_bounds__(BLOCK) k_exsum_strided(const double *__restrict__ a, long long n,
-                                                         long long inca, long long *__restrict__ gacc,
-                                                         unsigned *__restrict__ gflags, int ngroups)
-{
-    __shared__ long long s_acc[WAVES * NL * COPIES];
-    for (int i = threadIdx.x; i < WAVES * NL * COPIES; i += BLOCK) s_acc[i] = 0;
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    long long *col = s_acc + wave * NL * COPIES + (lane & (COPIES - 1));
-    unsigned flags = 0;
-    double fpe[N > 0 ? N : 1];
-#pragma unroll
-    for (int i = 0; i < (N > 0 ? N : 1); ++i) fpe[i] = 0.0;
-    // four independent loads in flight per lane (a strided element is its own cache line: latency, not bandwidth)
-    const long long T = (long long)gridDim.x * BLOCK;
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += 4 * T) {
-        double x[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = i + u * T < n ? a[(i + u * T) * inca] : 0.0;
-        fpe_absorb<N, false, COPIES, 4>(fpe, x, 0, col, flags);
-    }
-    fpe_flush<N, COPIES>(fpe, col, flags);
-    block_epilogue<COPIES>(s_acc, flags, gacc, gflags, ngroups);
-}
-
-// ---------------------------------------------------------------------------------------------
-// ExDOT: TwoProductFMA front-end (ExDOT.Superacc.cl:25-29, :244-253); the rounding error of the
-// product enters the expansion at slot max(N-3,0) like ExDOT.FPE.cl:254
-// ---------------------------------------------------------------------------------------------
-template <int N, bool EE, int COPIES, int ZM>
-__global__ void __launch_bounds__(BLOCK) k_exdot(const double *__restrict__ a, const double *__restrict__ b,
-                                                 long long n, long long *__restrict__ gacc,
-                                                 unsigned *__restrict__ gflags, int ngroups)
-{
-    __shared__ long long s_acc[WAVES * NL * COPIES];
-    // (zeroed below, AFTER the first tile's loads are in flight: a microsecond of every workgroup's life, which counts
-    // for the short shards of a multi-GPU job -- 2^25 elements are 16 us of HBM time per stream)
-    auto zero_lds = [&]() {
-        for (int i = threadIdx.x; i < WAVES * NL * COPIES; i += BLOCK) s_acc[i] = 0;
-        __syncthreads();
-    };
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    long long *col = s_acc + wave * NL * COPIES + (lane & (COPIES - 1));
-    unsigned flags = 0;
-    LdsSink<COPIES> sink{col, flags};
-    long long *const lo_acc = low_acc_of(gflags), *const hi_acc = high_acc_of(gflags);   // exact homes of the products below 2^-968 / beyond the double range (prod_range_divert)
-    double fpe[N > 0 ? N : 1];
-#pragma unroll
-    for (int i = 0; i < (N > 0 ? N : 1); ++i) fpe[i] = 0.0;
-
-    // vector path only when both streams are 16-byte aligned (host guarantees or falls to strided)
-    const d2_t *va = (const d2_t *)a, *vb = (const d2_t *)b;
-    const long long nv = n >> 1;
-    Bypass bypass;
-    constexpr long long TILE = (long long)BLOCK * U;
-    const long long ntiles = nv / TILE;
-    long long t = blockIdx.x;
-    d2_t ra[U], rb[U];
-    if (t < ntiles) {
-        const long long base = t * TILE + threadIdx.x;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            ra[u] = ld2(va + base + u * BLOCK);
-            rb[u] = ld2(vb + base + u * BLOCK);
-        }
-    }
-    zero_lds();
-    if (t < ntiles) {
-        // Two explicit register sets, filled alternately; the loads are unconditional (past the end they
-        // fetch the last tile again), so the compiler has no reason to copy one set into the other each
-        // trip (16 v_mov_b64 per tile with a conditional reload) and both sets stay in flight.
-        d2_t rc[U], rd[U];
-        auto fill = [&](long long tile, d2_t (&pa)[U], d2_t (&pb)[U]) {
-            const long long base = (tile < ntiles ? tile : ntiles - 1) * TILE + threadIdx.x;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                pa[u] = ld2(va + base + u * BLOCK);
-                pb[u] = ld2(vb + base + u * BLOCK);
-            }
-        };
-        auto absorb = [&](d2_t (&pa)[U], d2_t (&pb)[U]) {
-            double x[2 * U], e[2 * U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                x[2 * u] = two_prod(pa[u].x, pb[u].x, e[2 * u]);
-                x[2 * u + 1] = two_prod(pa[u].y, pb[u].y, e[2 * u + 1]);
-            }
-            if (!prod_range_divert<2 * U>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j & 1 ? pa[j >> 1].y : pa[j >> 1].x; },
-                                              [&](int j) { return j & 1 ? pb[j >> 1].y : pb[j >> 1].x; }))
-                fpe_absorb_prod_adaptive<N, EE, 2 * U, LdsSink<COPIES>, ZM, false>(fpe, x, e, sink, bypass);
-        };
-        for (;;) {
-            fill(t + gridDim.x, rc, rd);
-            absorb(ra, rb);
-            t += gridDim.x;
-            if (t >= ntiles) break;
-            fill(t + gridDim.x, ra, rb);
-            absorb(rc, rd);
-            t += gridDim.x;
-            if (t >= ntiles) break;
-        }
-    }
-    for (long long i = ntiles * TILE + (long long)blockIdx.x * BLOCK + threadIdx.x; i < nv;
-         i += (long long)gridDim.x * BLOCK) {
-        d2_t ra = va[i], rb = vb[i];
-        double x[2], e[2];
-        x[0] = two_prod(ra.x, rb.x, e[0]);
-        x[1] = two_prod(ra.y, rb.y, e[1]);
-        if (!prod_range_divert<2>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return j ? ra.y : ra.x; }, [&](int j) { return j ? rb.y : rb.x; }))
-            fpe_absorb_prod<N, false, 2, LdsSink<COPIES>, 0, false>(fpe, x, e, sink);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && (n & 1)) {
-        double x1[1], e1[1];
-        x1[0] = two_prod(a[n - 1], b[n - 1], e1[0]);
-        // (only this lane is active: the helper's votes are votes of one)
-        if (!prod_range_divert<1>(fpe[0], x1, e1, sink, lo_acc, hi_acc, [&](int) { return a[n - 1]; }, [&](int) { return b[n - 1]; }))
-            sink_product(sink, x1[0], e1[0]);
-    }
-    fpe_flush<N, COPIES>(fpe, col, flags);
-    block_epilogue<COPIES>(s_acc, flags, gacc, gflags, ngroups);
-}
-
-template <int N, bool EE, int COPIES>
-__global__ void __launch_bounds__(BLOCK) k_exdot_strided(const double *__restrict__ a, long long inca,
-                                                         const double *__restrict__ b, long long incb,
-                                                         long long n, long long *__restrict__ gacc,
-                                                         unsigned *__restrict__ gflags, int ngroups)
-{
-    __shared__ long long s_acc[WAVES * NL * COPIES];
-    for (int i = threadIdx.x; i < WAVES * NL * COPIES; i += BLOCK) s_acc[i] = 0;
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    long long *col = s_acc + wave * NL * COPIES + (lane & (COPIES - 1));
-    unsigned flags = 0;
-    LdsSink<COPIES> sink{col, flags};
-    long long *const lo_acc = low_acc_of(gflags), *const hi_acc = high_acc_of(gflags);
-    double fpe[N > 0 ? N : 1];
-#pragma unroll
-    for (int i = 0; i < (N > 0 ? N : 1); ++i) fpe[i] = 0.0;
-    const long long T = (long long)gridDim.x * BLOCK;
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < n; i += 4 * T) {
-        double va[4], vb[4], x[4], e[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool in = i + u * T < n;
-            va[u] = in ? a[(i + u * T) * inca] : 0.0;
-            vb[u] = in ? b[(i + u * T) * incb] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) x[u] = two_prod(va[u], vb[u], e[u]);
-        if (!prod_range_divert<4>(fpe[0], x, e, sink, lo_acc, hi_acc, [&](int j) { return va[j]; }, [&](int j) { return vb[j]; }))
-            fpe_absorb_prod<N, false, 4, LdsSink<COPIES>, 0, false>(fpe, x, e, sink);
-    }
-    fpe_flush<N, COPIES>(fpe, col, flags);
-    block_epilogue<COPIES>(s_acc, flags, gacc, gflags, ngroups);
-}
+};
 
 // ---------------------------------------------------------------------------------------------
 // finalize: sum `nsets` limb vectors, ONE carry propagation, canonical limbs, rounding.
@@ -459,84 +284,8 @@ __global__ void __launch_bounds__(BLOCK) k_exsum_segmented_zero(long long nseg, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// launchers
+// launchers (launch_blas1, EXB_LAUNCH_STREAMING and grid_for: blas1_common.hip.h)
 // ---------------------------------------------------------------------------------------------
-
-// (EXB_LAUNCH_STREAMING and grid_for: blas1_common.hip.h)
-template <int N, bool EE, int COPIES>
-static void run_exsum(Ctx &c, const double *a, long long n, hipStream_t st)
-{
-    // resident blocks per CU: the HBM-bound kernels want few fat blocks; the variants that run the full N-level cascade
-    // on every element (no early exit, N >= 5: 30-48 dependent fp64 adds per element) are VALU-latency-bound and want
-    // more waves per SIMD to hide it
-    const int bpc = N == 0 ? c.bpc_sa : ((!SKIP_ZERO_LEVELS<EE> && N >= 5) ? c.bpc_heavy : c.bpc_sum);
-    int grid = grid_for(c, n, (long long)BLOCK * 2 * U, bpc);
-    // an odd number of workgroups (one resident slot left idle): the tiles a workgroup has in flight are grid x 16 KiB
-    // apart, and with an even grid they compete for the same HBM channels -- 865 against 855 Gelem/s at n = 2^28
-    if (grid == c.num_cu * bpc && grid > 1 && !(grid & 1)) grid -= 1;
-    c.last_blas1_kernel = BLAS1_K_EXSUM, c.last_blas1_grid = grid;   // (exblas_last_blas1_info)
-    EXB_LAUNCH_STREAMING(c, (k_exsum<N, EE, COPIES>), grid, st, a, n, c.gacc, c.gflags, c.ngroups);
-}
-
-#ifndef EXBLAS_SUM_COPIES
-#define EXBLAS_SUM_COPIES 8
-#endif
-#ifndef EXBLAS_DOT_COPIES
-#define EXBLAS_DOT_COPIES 8
-#endif
-template <int N, bool EE>
-static hipError_t launch_exsum(Ctx &c, const double *a, long long n, long long inca, hipStream_t st)
-{
-    constexpr int COPIES = (N == 0) ? 16 : EXBLAS_SUM_COPIES;
-    if (inca == 1) {
-        run_exsum<N, EE, COPIES>(c, a, n, st);
-    } else {
-        int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
-        c.last_blas1_kernel = BLAS1_K_EXSUM_STRIDED, c.last_blas1_grid = grid;
-        EXB_LAUNCH_STREAMING(c, (k_exsum_strided<N, EE, COPIES>), grid, st, a, n, inca, c.gacc, c.gflags, c.ngroups);
-    }
-    return hipGetLastError();
-}
-
-template <int N, bool EE, int COPIES>
-static void run_exdot(Ctx &c, const double *a, const double *b, long long n, hipStream_t st)
-{
-    // Workgroups per CU: 48 at n = 2^28 (placement probe, round 2), but a workgroup should stream about five tiles or
-    // more: at n = 2^25 -- a rank's shard of ONE 2^28 vector over 8 GPUs -- 48 per CU leave 1.3 tiles per workgroup
-    // (some stream two, most one: 108 us with the finalize), 12 per CU 5.3 (93 us); 2^26: 179 -> 174 us with 24
-    // (tools/tune_shard.py).  An explicit smaller setting (exblas_set_tuning / EXBLAS_BPC_DOT) is kept.
-    const long long tiles = n / ((long long)BLOCK * 2 * U);
-    const int bpc = (int)min((long long)c.bpc_dot, max(4ll, tiles / (5ll * c.num_cu)));
-    int grid = grid_for(c, n, (long long)BLOCK * 2 * U, bpc);
-    // An ODD number of workgroups: a workgroup's successive tiles (grid tiles = grid x 16 KiB apart) then walk through
-    // the 32 KiB period with which the two streams' addresses compete for HBM channels, whatever b - a is.  With the
-    // even grid (32 x 256) the step time at n = 2^28 depended on the relative placement of the two vectors, 0.625 ms
-    // (b - a = 16 KiB mod 32 KiB) to 0.667 ms (0 mod 32 KiB); odd: 0.625-0.635 ms for every placement
-    // (tools/dot_align.py, profiles/r02_exdot_placement.log).
-    if (grid > c.num_cu && !(grid & 1)) grid += 1;
-    // early-exit votes by one fp64 compare per residue (ZM = 1): median 0.658 ms against 0.699 by integer ORs at
-    // n = 2^28 (tools/tune.py, same box)
-    c.last_blas1_kernel = BLAS1_K_EXDOT, c.last_blas1_grid = grid;
-    EXB_LAUNCH_STREAMING(c, (k_exdot<N, EE, COPIES, SKIP_ZERO_LEVELS<EE> ? 1 : 0>), grid, st, a, b, n, c.gacc, c.gflags,
-                         c.ngroups);
-}
-
-template <int N, bool EE>
-static hipError_t launch_exdot(Ctx &c, const double *a, long long inca, const double *b, long long incb,
-                               long long n, hipStream_t st)
-{
-    constexpr int COPIES = (N == 0) ? 16 : EXBLAS_DOT_COPIES;
-    const bool vec = inca == 1 && incb == 1 && (((uintptr_t)a | (uintptr_t)b) & 15u) == 0;
-    if (vec) {
-        run_exdot<N, EE, COPIES>(c, a, b, n, st);
-    } else {
-        int grid = grid_for(c, n, BLOCK, c.blocks_per_cu);
-        c.last_blas1_kernel = BLAS1_K_EXDOT_STRIDED, c.last_blas1_grid = grid;
-        EXB_LAUNCH_STREAMING(c, (k_exdot_strided<N, EE, COPIES>), grid, st, a, inca, b, incb, n, c.gacc, c.gflags,
-                             c.ngroups);
-    }
-    return hipGetLastError();
-}
 
 // d_ext_out == nullptr: the context's low / high accumulators (ExDOT products below 2^-968 / beyond the double range) are
 // folded into the record; otherwise they are exported as two digit sets (EXT_WORDS int64: [low | high]) and the record
@@ -562,9 +311,9 @@ hipError_t finalize_sets(const long long *d_sets, int nsets, unsigned flags_or, 
 hipError_t exsum_dispatch(Ctx &c, const double *a, long long n, long long inca, int fpe, int early_exit,
                           hipStream_t st)
 {
-    if (fpe < 2) return launch_exsum<0, false>(c, a, n, inca, st);
+    if (fpe < 2) return launch_blas1<SumF64, 0, false>(c, a, inca, a, inca, n, st);
     hipError_t e = hipSuccess;
-    select_variant<2>(fpe, early_exit, [&](auto N, auto EE) { e = launch_exsum<N(), EE()>(c, a, n, inca, st); });
+    select_variant<2>(fpe, early_exit, [&](auto N, auto EE) { e = launch_blas1<SumF64, N(), EE()>(c, a, inca, a, inca, n, st); });
     return e;
 }
 
@@ -588,10 +337,10 @@ hipError_t exsum_segmented_dispatch(const double *values, const long long *offse
 hipError_t exdot_dispatch(Ctx &c, const double *a, long long inca, const double *b, long long incb, long long n,
                           int fpe, int early_exit, hipStream_t st)
 {
-    if (fpe < 3) return launch_exdot<0, false>(c, a, inca, b, incb, n, st);
+    if (fpe < 3) return launch_blas1<DotF64, 0, false>(c, a, inca, b, incb, n, st);
     hipError_t e = hipSuccess;
     select_variant<3>(fpe, early_exit,
-                      [&](auto N, auto EE) { e = launch_exdot<N(), EE()>(c, a, inca, b, incb, n, st); });
+                      [&](auto N, auto EE) { e = launch_blas1<DotF64, N(), EE()>(c, a, inca, b, incb, n, st); });
     return e;
 }
 

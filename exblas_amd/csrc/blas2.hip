@@ -374,7 +374,7 @@ __global__ void __launch_bounds__(GV_BLOCK) k_gemvT(int m, const double *__restr
         // add per load)
         const int lane_off = (tid >> 6) * (64 * U) + (tid & 63);
         if (ntiles > 0) {
-            // two register sets filled alternately with unconditional loads (see k_exdot in blas1.hip)
+            // two register sets filled alternately with unconditional loads (see k_blas1_stream in blas1_common.hip.h)
             d2_t ra[U], rx[U], rb[U], ry[U];
             auto fill = [&](long long tt, d2_t (&qa)[U], d2_t (&qx)[U]) {
                 long long t = (tt < ntiles ? tt : ntiles - 1) + t0;

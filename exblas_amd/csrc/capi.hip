@@ -310,7 +310,7 @@ int exblas_last_gemm_slices(void)
 }
 
 // The last streaming ExSUM / ExDOT launch of the current device's default context (the *_dev entry points): out[0] the
-// kernel (1 k_exsum, 2 k_exsum_strided, 3 k_exdot, 4 k_exdot_strided, 5 .. 8 the same of blas1_lowp.hip; 0: none yet), out[1] its grid, out[2] the group
+// kernel (1 fp64 ExSUM on k_blas1_stream, 2 on k_blas1_strided, 3 and 4 fp64 ExDOT likewise, 5 .. 8 the same of blas1_lowp.hip; 0: none yet), out[1] its grid, out[2] the group
 // accumulators, out[3] the compute units the geometry was sized for, out[4..7] reserved.  Host state only: nothing is
 // read from the device and nothing synchronises.
 int exblas_last_blas1_info(int *out)

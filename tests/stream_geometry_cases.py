@@ -1,5 +1,6 @@
 """Sizes, data and expected totals that put every positional seam of the streaming ExSUM / ExDOT kernels
-(exblas_amd/csrc/blas1.hip: k_exsum, k_exsum_strided, k_exdot, k_exdot_strided) under test in every launch geometry.
+(exblas_amd/csrc/blas1_common.hip.h: k_blas1_stream and k_blas1_strided, here with the fp64 front ends SumF64 and DotF64
+of blas1.hip) under test in every launch geometry.
 Pure numpy / Python: no GPU, no oracle.  tests/test_stream_geometry_cases.py holds this module to its coverage claims,
 tests/test_gpu_stream_geometry.py runs the plans (tests/stream_geometry_worker.py, one child process per geometry).
 
@@ -31,7 +32,7 @@ VARIANTS = {SUM: list(FPE_VARIANTS_SUM), DOT: list(FPE_VARIANTS_DOT) + [(1, Fals
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# launch geometry (restatement of blas1.hip: grid_for, run_exsum, launch_exsum, run_exdot, launch_exdot)
+# launch geometry (restatement of blas1_common.hip.h: grid_for, run_stream, run_strided, launch_blas1)
 # ---------------------------------------------------------------------------------------------------------------------
 def geometries(num_cu):
     """name -> environment of the child process"""
@@ -84,7 +85,7 @@ def launch_model(num_cu, env, routine, n, aligned=True, strided=False, fpe=8):
 # which seams a call exercises
 # ---------------------------------------------------------------------------------------------------------------------
 def seams(n, head, grid):
-    """The positional facts of one k_exsum / k_exdot launch (head: 1 when ExSUM's pointer is 8 mod 16, else 0)."""
+    """The positional facts of one fp64 k_blas1_stream launch (head: 1 when ExSUM's pointer is 8 mod 16, else 0)."""
     head = 1 if (head and n > 0) else 0
     nv = (n - head) >> 1
     ntiles = nv // TILE_V
@@ -105,7 +106,7 @@ def seams(n, head, grid):
 
 
 def seams_strided(n, grid):
-    """k_exsum_strided / k_exdot_strided: how many of the four u slots the last trip uses, how many slots any trip uses,
+    """fp64 k_blas1_strided: how many of the four u slots the last trip uses, how many slots any trip uses,
     the loop trips of the busiest lane, and where n sits relative to a multiple of T = grid x 256"""
     T = grid * BLOCK
     trips = -(-n // (4 * T))
@@ -323,7 +324,7 @@ def lone_decode(total, names):
 
 
 def lone_head(e):
-    """the scalar head element of a lone entry's launch (k_exsum with a pointer 8 mod 16)"""
+    """the scalar head element of a lone entry's launch (k_blas1_stream<SumF64> with a pointer 8 mod 16)"""
     return e["offa"] & 1 if (e["routine"] == SUM and e["inca"] == 1) else 0
 
 
@@ -541,7 +542,7 @@ def plan_json(entries):
 # a plain TwoSum cascade of one wavefront (what the spill / bypass claims of the families rest on)
 # ---------------------------------------------------------------------------------------------------------------------
 def wave_stream(x, head, grid, wg, ntiles, wave=0):
-    """[tiles of this workgroup, 64 lanes, 8 elements]: what one wavefront of k_exsum absorbs, tile by tile"""
+    """[tiles of this workgroup, 64 lanes, 8 elements]: what one wavefront of k_blas1_stream<SumF64> absorbs, tile by tile"""
     lanes = wave * 64 + np.arange(64)
     out = []
     for t in range(wg, ntiles, grid):

@@ -1,6 +1,6 @@
 """Every positional seam of the streaming ExSUM / ExDOT kernels in every launch geometry, bit for bit.
 
-k_exsum, k_exdot and their strided forms are positional bookkeeping: a scalar head, tiles dealt round-robin to the
+k_blas1_stream and k_blas1_strided (fp64 front ends SumF64 and DotF64) are positional bookkeeping: a scalar head, tiles dealt round-robin to the
 workgroups, two register sets with two exits, re-fetched last tiles, a grid-strided remainder, a scalar tail, a bypass
 counter, group accumulators chosen by blockIdx.x % ngroups.  Which of these a size exercises is decided by the launch
 geometry, and the geometry knobs (EXBLAS_BPC_*, EXBLAS_BLOCKS_PER_CU, EXBLAS_GRID_ADJ, EXBLAS_NGROUPS) are read once, when

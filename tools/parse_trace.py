@@ -6,7 +6,7 @@ f=sorted(glob.glob(sys.argv[1]))[-1]
 rows=[r for r in csv.DictReader(open(f))]
 rows.sort(key=lambda r:int(r["Start_Timestamp"]))
 # find last 40 kernels around exsum steps
-idx=[i for i,r in enumerate(rows) if "k_exsum<" in r["Kernel_Name"]]
+idx=[i for i,r in enumerate(rows) if "k_blas1_stream<exb::SumF64" in r["Kernel_Name"]]
 sel=idx[-6:]
 t0=int(rows[sel[0]]["Start_Timestamp"])
 for i in range(sel[0], sel[-1]+1):

@@ -34,6 +34,11 @@ if ks:
 
 
 def short(name):
+    # ExSUM / ExDOT share k_blas1_stream; the front end in the template arguments says which fp64 routine a launch was
+    if "k_blas1_stream<exb::SumF64" in name:
+        return "k_exsum"
+    if "k_blas1_stream<exb::DotF64" in name:
+        return "k_exdot"
     # longest names first: k_stream_read2 must not be averaged into k_stream_read (it reads twice the bytes)
     for k in ("k_stream_read2", "k_stream_read", "k_exsum_segmented", "k_exsum", "k_exdot", "k_finalize", "k_gen",
               "k_gemv_finish", "k_gemvN_fpe_sx", "k_gemvN_fpe", "k_gemvN_sa", "k_gemvT", "k_scale_x", "k_gemm_mfma", "k_gemm_crt", "k_crt_finish", "k_crt_residues", "k_crt_decide", "k_gemm_i8g",
