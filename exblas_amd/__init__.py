@@ -47,6 +47,9 @@ C_ABI_SYMBOLS = [
     "exblas_last_spmv_info",
     "exblas_exspmm_csr_dev", "exblas_exspmm_csr_ctx", "exblas_exspmm_csr", "exblas_set_spmm_path",
     "exblas_last_spmm_info",
+    "exblas_exspmv_csr_lp_dev", "exblas_exspmv_csr_lp_ctx", "exblas_exspmv_csr_lp",
+    "exblas_exspmm_csr_lp_dev", "exblas_exspmm_csr_lp_ctx", "exblas_exspmm_csr_lp", "exblas_round_interval_host",
+    "exblas_round_window_host",
     "exblas_exsptrsv_csr_dev", "exblas_exsptrsv_csr_ctx", "exblas_exsptrsv_csr", "exblas_set_sptrsv_path",
     "exblas_last_sptrsv_info",
     "exblas_exspilu0_csr_dev", "exblas_exspilu0_csr_ctx", "exblas_exspilu0_csr", "exblas_set_spilu0_path",
@@ -210,6 +213,14 @@ def load_library():
     L.exblas_set_spmm_path.argtypes = [i32]
     L.exblas_set_spmm_path.restype = None
     L.exblas_last_spmm_info.argtypes = [C.POINTER(i64)]
+    L.exblas_exspmv_csr_lp_dev.argtypes = [i32, i32, i32, vp, vp, i32, vp, dbl, i32, vp, dbl, vp, i32, i32, vp]
+    L.exblas_exspmv_csr_lp_ctx.argtypes = [vp] + L.exblas_exspmv_csr_lp_dev.argtypes
+    L.exblas_exspmv_csr_lp.argtypes = L.exblas_exspmv_csr_lp_dev.argtypes[:-1]
+    L.exblas_exspmm_csr_lp_dev.argtypes = [i32, i32, i32, i32, vp, vp, i32, vp, dbl, i32, vp, i64, dbl, vp, i64, i32, i32, vp]
+    L.exblas_exspmm_csr_lp_ctx.argtypes = [vp] + L.exblas_exspmm_csr_lp_dev.argtypes
+    L.exblas_exspmm_csr_lp.argtypes = L.exblas_exspmm_csr_lp_dev.argtypes[:-1]
+    L.exblas_round_interval_host.argtypes = [dbl, dbl, i32, C.POINTER(C.c_uint64)]
+    L.exblas_round_window_host.argtypes = [vp, i32, C.POINTER(C.c_uint64)]
     L.exblas_exsptrsv_csr_dev.argtypes = [C.c_char, C.c_char, i32, i32, vp, vp, vp, vp, i32, i32, vp]
     L.exblas_exsptrsv_csr_ctx.argtypes = [vp] + L.exblas_exsptrsv_csr_dev.argtypes
     L.exblas_exsptrsv_csr.argtypes = [C.c_char, C.c_char, i32, i32, vp, vp, vp, vp, i32, i32]
@@ -406,7 +417,15 @@ def finalize_dev(digit_sets, flags_or=0, out=None):
     return out
 
 
-def _csr_rules(who, xp, crow, col, val, shape, square):
+def _csr_value_rule(who, xp, val, narrow):
+    """The dtype rule of the CSR values: float64, or with `narrow` (the *_lp routines) any of the four dtypes."""
+    if narrow:
+        _dt(val.dtype, who)
+    elif val.dtype != xp.float64:
+        raise TypeError(f"{who}: values must be float64")
+
+
+def _csr_rules(who, xp, crow, col, val, shape, square, narrow=False):
     """The rules the CSR arrays of routine `who` obey, whatever holds them (xp: torch or numpy); returns (m, n, index_bits)."""
     if len(shape) != 2:
         raise ValueError(f"{who}: A must be 2-D, got shape {tuple(shape)}")
@@ -415,8 +434,7 @@ def _csr_rules(who, xp, crow, col, val, shape, square):
         raise ValueError(f"{who}: unsupported shape {tuple(shape)}")
     if square and m != n:
         raise ValueError(f"{who}: A must be square, got shape ({m}, {n})")
-    if val.dtype != xp.float64:
-        raise TypeError(f"{who}: values must be float64")
+    _csr_value_rule(who, xp, val, narrow)
     if crow.dtype not in (xp.int32, xp.int64) or col.dtype != crow.dtype:
         raise TypeError(f"{who}: row pointers and column indices must both be int32 or both int64")
     if crow.ndim != 1 or col.ndim != 1 or val.ndim != 1:
@@ -428,7 +446,7 @@ def _csr_rules(who, xp, crow, col, val, shape, square):
     return m, n, (32 if crow.dtype == xp.int32 else 64)
 
 
-def _csr_dev(who, A, square=False):
+def _csr_dev(who, A, square=False, narrow=False):
     """The CSR operand of the device routine `who`: a torch.sparse_csr_tensor or a (crow, col, val, shape) tuple of torch
     tensors.  Refuses what is wrong with it without needing a GPU; returns (crow, col, val, m, n, index_bits)."""
     torch = _torch()
@@ -443,7 +461,7 @@ def _csr_dev(who, A, square=False):
     for name, t in (("crow", crow), ("col", col), ("val", val)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{who}: {name} must be a torch tensor")
-    m, n, bits = _csr_rules(who, torch, crow, col, val, shape, square)
+    m, n, bits = _csr_rules(who, torch, crow, col, val, shape, square, narrow)
     return crow.contiguous(), col.contiguous(), val.contiguous(), m, n, bits
 
 
@@ -509,6 +527,62 @@ def _spmv_args(A, x, y, alpha, beta, fpe, early_exit):
         y = _torch().zeros(m, dtype=x.dtype, device=x.device)
     return y, (m, n, bits, _ptr(crow), _ptr(col), _ptr(val), float(alpha), _ptr(x), float(beta), _ptr(y), int(fpe),
                int(bool(early_exit)))
+
+
+EXBLAS_UNSUPPORTED = -1
+
+
+def _lp_pair(who, val_dtype, vec_dtype, fpe):
+    """The accepted type pairs of the narrow sparse products: values float32 / float16 / bfloat16 (or float64 with float64
+    vectors), vectors float64 or of the values' type; fpe 0 or 2..8 (1: no plain narrow kernel).  Returns the two codes."""
+    vcode, xcode = _dt(val_dtype, who)[0], _dt(vec_dtype, who)[0]
+    if xcode != DT_F64 and xcode != vcode:
+        raise TypeError(f"exblas_amd.{who}: the vectors must be float64 or of the values' type, not {vec_dtype} with "
+                        f"{val_dtype} values")
+    if vcode != DT_F64:
+        if int(fpe) == 1:
+            raise NotImplementedError(f"exblas_amd.{who}: fpe = 1 (the plain sums) has no narrow kernel "
+                                      f"(EXBLAS_UNSUPPORTED)")
+        if not 0 <= int(fpe) <= 8:
+            raise ValueError(f"exblas_amd.{who}: fpe must be 0 or 2..8")
+    return vcode, xcode
+
+
+def _check_lp(rc, what):
+    if rc == EXBLAS_UNSUPPORTED:
+        raise NotImplementedError(f"exblas_amd: {what}: fpe = 1 has no narrow kernel (EXBLAS_UNSUPPORTED)")
+    _check(rc, what)
+
+
+def _dense_lp(who, name, t, ndim, dtype=None):
+    """The type rules of a dense operand of a narrow device routine: a torch tensor of ndim dimensions (of `dtype`)."""
+    torch = _torch()
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{who}: {name} must be a torch tensor")
+    if dtype is not None and t.dtype != dtype:
+        raise TypeError(f"{who}: {name} must be {dtype}, the type of the other dense operand")
+    if t.dim() != ndim:
+        raise ValueError(f"{who}: {name} must be {ndim}-D")
+
+
+def _spmv_lp_args(A, x, y, alpha, beta, fpe, early_exit):
+    """Validates a narrow device ExSpMV call before anything is launched; returns (y, the C arguments up to the stream)."""
+    who = "exspmv_lp"
+    crow, col, val, m, n, bits = _csr_dev(who, A, narrow=True)
+    _dense_lp(who, "x", x, 1)
+    vcode, xcode = _lp_pair(who, val.dtype, x.dtype, fpe)
+    if x.numel() < n:
+        raise ValueError(f"{who}: x has {x.numel()} entries, fewer than n = {n}")
+    if y is not None:
+        _dense_lp(who, "y", y, 1, x.dtype)
+        if y.numel() != m or not y.is_contiguous():
+            raise ValueError(f"{who}: y must be a contiguous vector of m = {m} entries")
+    _on_gpu(who, crow=crow, col=col, val=val, x=x, **({} if y is None else {"y": y}))
+    x = x.contiguous()
+    if y is None:
+        y = _torch().zeros(m, dtype=x.dtype, device=x.device)
+    return y, (m, n, bits, _ptr(crow), _ptr(col), vcode, _ptr(val), float(alpha), xcode, _ptr(x), float(beta), _ptr(y),
+               int(fpe), int(bool(early_exit)))
 
 
 def set_spmv_path(mode):
@@ -729,6 +803,32 @@ def _spmm_args(A, X, Y, alpha, beta, fpe, early_exit):
         Y = _torch().zeros((m, k), dtype=X.dtype, device=X.device)
     return Y, (m, n, k, bits, _ptr(crow), _ptr(col), _ptr(val), float(alpha), _ptr(X), _ld(X, k), float(beta), _ptr(Y),
                _ld(Y, k), int(fpe), int(bool(early_exit)))
+
+
+def _spmm_lp_args(A, X, Y, alpha, beta, fpe, early_exit):
+    """Validates a narrow device ExSpMM call before anything is launched; returns (Y, the C arguments up to the stream)."""
+    who = "exspmm_lp"
+    crow, col, val, m, n, bits = _csr_dev(who, A, narrow=True)
+    if getattr(X, "ndim", 2) == 1:
+        raise ValueError(f"{who}: X must be 2-D (n x k); for one vector use exspmv_lp_dev")
+    _dense_lp(who, "X", X, 2)
+    vcode, xcode = _lp_pair(who, val.dtype, X.dtype, fpe)
+    if X.shape[0] < n:
+        raise ValueError(f"{who}: X has {X.shape[0]} rows, fewer than n = {n}")
+    k = int(X.shape[1])
+    if Y is not None:
+        _dense_lp(who, "Y", Y, 2, X.dtype)
+        if tuple(Y.shape) != (m, k):
+            raise ValueError(f"{who}: Y must have shape ({m}, {k})")
+        if m > 0 and k > 0 and (Y.stride(1) != 1 or (m > 1 and Y.stride(0) < k)):
+            raise ValueError(f"{who}: Y is updated in place: it needs stride(1) == 1 and stride(0) >= k")
+    _on_gpu(who, crow=crow, col=col, val=val, X=X, **({} if Y is None else {"Y": Y}))
+    if k > 0 and X.shape[0] > 0 and (X.stride(1) != 1 or (X.shape[0] > 1 and X.stride(0) < k)):
+        X = X.contiguous()
+    if Y is None:
+        Y = _torch().zeros((m, k), dtype=X.dtype, device=X.device)
+    return Y, (m, n, k, bits, _ptr(crow), _ptr(col), vcode, _ptr(val), float(alpha), xcode, _ptr(X), _ld(X, k),
+               float(beta), _ptr(Y), _ld(Y, k), int(fpe), int(bool(early_exit)))
 
 
 def set_spmm_path(mode):
@@ -1473,6 +1573,22 @@ class Context:
         _check(load_library().exblas_exspmv_csr_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmv")
         return y
 
+    def exspmv_lp(self, A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+        """Narrow ExSpMV: A with float32 / float16 / bfloat16 values read at their own width, x and y float64 or of the
+        values' type.  The exact sum of exspmv on the widened operands, rounded ONCE into the type of x: float64 results
+        are bit for bit exspmv(A.double(), ...), narrow ones are rounded to nearest even straight from the exact sum
+        (never the double cast afterwards).  y=None allocates zeros of x's type.  fpe 0 or 2..8."""
+        y, args = _spmv_lp_args(A, x, y, alpha, beta, fpe, early_exit)
+        _check_lp(load_library().exblas_exspmv_csr_lp_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmv_lp")
+        return y
+
+    def exspmm_lp(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+        """Narrow ExSpMM: column j of Y is bit for bit exspmv_lp(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_lp; X
+        and Y row-major blocks (stride(1) == 1) of float64 or of the values' type; the padding of Y is not written."""
+        Y, args = _spmm_lp_args(A, X, Y, alpha, beta, fpe, early_exit)
+        _check_lp(load_library().exblas_exspmm_csr_lp_ctx(self.handle, *args, _stream_ptr(_torch())), "exspmm_lp")
+        return Y
+
     def exspmm(self, A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
         """ExSpMM: Y = Round(alpha A X + beta Y) output by output, exact and reproducible, stream-ordered on the current
         stream; column j is bit for bit exspmv_dev(A, X[:, j], alpha, beta, Y[:, j]).  A as for exspmv_dev; X a 2-D float64
@@ -1702,6 +1818,7 @@ exsum_to_dev, exdot_to_dev = _default.exsum_to, _default.exdot_to
 exgemv_dev, extrsv_dev, exgemm_dev = _default.exgemv, _default.extrsv, _default.exgemm
 extrsm_dev = _default.extrsm
 exspmv_dev, exspmm_dev, exsptrsv_dev, exsptrsm_dev = _default.exspmv, _default.exspmm, _default.exsptrsv, _default.exsptrsm
+exspmv_lp_dev, exspmm_lp_dev = _default.exspmv_lp, _default.exspmm_lp
 exspilu0_dev, exspilu0_apply_dev = _default.exspilu0, _default.exspilu0_apply
 exspic0_dev, exspic0_apply_dev = _default.exspic0, _default.exspic0_apply
 exbdot_dev, exbdot_export_dev, exbdot_round_dev = _default.exbdot, _default.exbdot_export, _default.exbdot_round
@@ -1844,6 +1961,30 @@ def round_digits_host(digits, dtype):
     return int(bits.value)
 
 
+def round_window_host(digits, dtype):
+    """round_digits_host computed the way the narrow sparse products round an accumulator (the leading 64 bits and a sticky):
+    the bit pattern, an int; no device"""
+    code = _dt(dtype, "round_window_host")[0]
+    d = np.ascontiguousarray(digits, dtype=np.int64)
+    if d.shape != (NDIGITS,):
+        raise ValueError("exblas_amd.round_window_host: 68 digits expected")
+    bits = C.c_uint64()
+    _check(load_library().exblas_round_window_host(C.c_void_p(d.ctypes.data), code, C.byref(bits)), "round_window_host")
+    return int(bits.value)
+
+
+def round_interval_host(res, bound, dtype):
+    """The certificate of the narrow sparse products' in-register rounding, on the CPU (no device): the bit pattern (an int)
+    of the one `dtype` value that every real number of [res - bound, res + bound] rounds to, or None when the interval
+    reaches a rounding boundary of the format.  bound = 0 declares res exact (ties are then decided, to even)."""
+    code = _dt(dtype, "round_interval_host")[0]
+    bits = C.c_uint64()
+    rc = load_library().exblas_round_interval_host(float(res), float(bound), code, C.byref(bits))
+    if rc < 0:
+        raise RuntimeError("exblas_amd: round_interval_host refused its arguments")
+    return int(bits.value) if rc == 1 else None
+
+
 def exgemv(transa, m, n, alpha, a, lda, offseta, x, incx, offsetx, beta, y, incy, offsety, fpe, early_exit=False):
     """int exgemv(...) -- include/blas2.hpp:95; y (numpy float64) is updated in place."""
     _require_gpu()
@@ -1914,6 +2055,88 @@ def exspmv(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
     _check(load_library().exblas_exspmv_csr(m, n, bits, _hptr(crow), _hptr(col), _hptr(val), float(alpha), _hptr(x),
                                             float(beta), _hptr(y), int(fpe), int(bool(early_exit))), "exspmv")
     return y
+
+
+def _host_lp_csr(who, A):
+    """The CSR operand of a narrow host routine: (row_ptr, col_idx, val, shape) with numpy index arrays and the values a
+    numpy array or torch CPU tensor (bfloat16: torch only).  Returns (crow, col, (code, address, keep-alive), m, n, bits)."""
+    if not isinstance(A, (tuple, list)) or len(A) != 4:
+        raise ValueError(f"{who}: A must be a (row_ptr, col_idx, val, shape) tuple")
+    crow, col = np.asarray(A[0]), np.asarray(A[1])
+    val = A[2] if hasattr(A[2], "data_ptr") else np.asarray(A[2])
+    m, n, bits = _csr_rules(who, np, crow, col, val, A[3], False, narrow=True)
+    if m > 0 and (crow.min() < 0 or crow.max() > col.size):
+        raise ValueError(f"{who}: row_ptr entries must lie in [0, nnz]")
+    return np.ascontiguousarray(crow), np.ascontiguousarray(col), _host_lp(val, who), m, n, bits
+
+
+def _host_like(x, shape):
+    """zeros of the kind and dtype of the host operand x (numpy array or torch CPU tensor)"""
+    return _torch().zeros(shape, dtype=x.dtype) if hasattr(x, "data_ptr") else np.zeros(shape, dtype=x.dtype)
+
+
+def _host_copy(y, x, who):
+    """a contiguous copy of y in the kind and dtype of x"""
+    if hasattr(x, "data_ptr"):
+        torch = _torch()
+        if not isinstance(y, torch.Tensor) or y.dtype != x.dtype:
+            raise TypeError(f"{who}: y must be a torch CPU tensor of x's dtype")
+        return y.detach().clone().contiguous()
+    y = np.asarray(y)
+    if y.dtype != x.dtype:
+        raise TypeError(f"{who}: y must have x's dtype")
+    return np.array(y, copy=True, order="C")
+
+
+def _hp(ptr_keep):
+    code, ptr, keep = ptr_keep
+    return C.c_void_p(ptr) if (keep.size if hasattr(keep, "ctypes") else keep.numel()) else None
+
+
+def exspmv_lp(A, x, alpha=1.0, beta=0.0, y=None, fpe=8, early_exit=True):
+    """Narrow ExSpMV on host arrays: A = (row_ptr, col_idx, val, (m, n)) with float32 / float16 / bfloat16 values, x float64
+    or of the values' type; numpy arrays or torch CPU tensors (bfloat16: torch CPU tensors).  Returns a new y of x's kind
+    and dtype (the y passed in is not changed)."""
+    who = "exspmv_lp"
+    crow, col, hv, m, n, bits = _host_lp_csr(who, A)
+    hx = _host_lp(x, who)
+    if hx[2].ndim != 1:
+        raise ValueError(f"{who}: x must be 1-D")
+    vcode, xcode = hv[0], hx[0]
+    _lp_pair(who, hv[2].dtype, hx[2].dtype, fpe)
+    if (hx[2].size if hasattr(hx[2], "ctypes") else hx[2].numel()) < n:
+        raise ValueError(f"{who}: x has fewer than n = {n} entries")
+    y = _host_like(hx[2], m) if y is None else _host_copy(y, hx[2], who)
+    if y.ndim != 1 or y.shape[0] != m:
+        raise ValueError(f"{who}: y must have m = {m} entries")
+    hy = _host_lp(y, who)
+    _require_gpu()
+    _check_lp(load_library().exblas_exspmv_csr_lp(m, n, bits, _hptr(crow), _hptr(col), vcode, _hp(hv), float(alpha), xcode,
+                                                  _hp(hx), float(beta), _hp(hy), int(fpe), int(bool(early_exit))), who)
+    return y
+
+
+def exspmm_lp(A, X, alpha=1.0, beta=0.0, Y=None, fpe=8, early_exit=True):
+    """Narrow ExSpMM on host arrays (see exspmv_lp): X of shape (n', k) with n' >= n; returns a new Y (m x k)."""
+    who = "exspmm_lp"
+    crow, col, hv, m, n, bits = _host_lp_csr(who, A)
+    hx = _host_lp(X, who)
+    if hx[2].ndim != 2:
+        raise ValueError(f"{who}: X must be 2-D (n x k; for one vector use exspmv_lp)")
+    vcode, xcode = hv[0], hx[0]
+    _lp_pair(who, hv[2].dtype, hx[2].dtype, fpe)
+    if hx[2].shape[0] < n:
+        raise ValueError(f"{who}: X has {hx[2].shape[0]} rows, fewer than n = {n}")
+    k = int(hx[2].shape[1])
+    Y = _host_like(hx[2], (m, k)) if Y is None else _host_copy(Y, hx[2], who)
+    if tuple(Y.shape) != (m, k):
+        raise ValueError(f"{who}: Y must have shape ({m}, {k})")
+    hy = _host_lp(Y, who)
+    _require_gpu()
+    _check_lp(load_library().exblas_exspmm_csr_lp(m, n, k, bits, _hptr(crow), _hptr(col), vcode, _hp(hv), float(alpha),
+                                                  xcode, _hp(hx), k, float(beta), _hp(hy), k, int(fpe),
+                                                  int(bool(early_exit))), who)
+    return Y
 
 
 def exsptrsv(A, b, uplo="L", diag="N", fpe=8, early_exit=True):

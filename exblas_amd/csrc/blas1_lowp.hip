@@ -21,42 +21,11 @@
 // as a float32.  Inf and NaN widen to Inf and NaN and take the range guard's flag path (fpe_guard, lds_add).
 #include "blas1_common.hip.h"
 #include "round_lowp.hip.h"
+#include "lowp_types.hip.h"
 
 namespace exb {
 
-typedef unsigned u4_t __attribute__((ext_vector_type(4)));
-
-// element types: `elem` as it lies in memory, `vec` the 16 loaded bytes, VEC elements in them, element j of a loaded
-// vector as a double
-struct LpF32 {
-    typedef float elem;
-    typedef u4_t vec;
-    static constexpr int VEC = 4;
-    static __device__ __forceinline__ double widen(elem v) { return (double)v; }
-    static __device__ __forceinline__ double at(const u4_t &r, int j) { return (double)__uint_as_float(r[j]); }
-};
-struct LpF16 {
-    typedef _Float16 elem;
-    typedef u4_t vec;
-    static constexpr int VEC = 8;
-    static __device__ __forceinline__ double widen(elem v) { return (double)(float)v; }
-    static __device__ __forceinline__ double at(const u4_t &r, int j)
-    {
-        const unsigned w = r[j >> 1];
-        return widen(__builtin_bit_cast(_Float16, (unsigned short)((j & 1) ? (w >> 16) : (w & 0xffffu))));
-    }
-};
-struct LpBF16 {
-    typedef unsigned short elem;   // raw words
-    typedef u4_t vec;
-    static constexpr int VEC = 8;
-    static __device__ __forceinline__ double widen(elem v) { return (double)__uint_as_float((unsigned)v << 16); }
-    static __device__ __forceinline__ double at(const u4_t &r, int j)
-    {
-        const unsigned w = r[j >> 1];
-        return (double)__uint_as_float((j & 1) ? (w & 0xffff0000u) : (w << 16));
-    }
-};
+// the element types LpF32 / LpF16 / LpBF16: lowp_types.hip.h
 
 // the narrow front ends of k_blas1_stream / k_blas1_strided (blas1_common.hip.h): exact doubles in, exact products
 template <class T>

@@ -561,6 +561,66 @@ static int exspmm_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_
                                 fpe, early_exit, round_mode(), st);
 }
 
+// The narrow CSR entries: what they refuse beyond csr_check_args, before a device is needed.  The pair (float64, float64)
+// is the fp64 entry's business (*forward); fpe = 1 has no narrow kernel.
+static int csr_lp_refused(int val_dtype, const void *val, int vec_dtype, const void *x, const void *y, int fpe, bool *forward)
+{
+    *forward = false;
+    if (!dtype_known(val_dtype) || !dtype_known(vec_dtype)) return (int)hipErrorInvalidValue;
+    if (vec_dtype != DT_F64 && vec_dtype != val_dtype) return (int)hipErrorInvalidValue;
+    const uintptr_t vmask = (uintptr_t)dtype_bytes(val_dtype) - 1, xmask = (uintptr_t)dtype_bytes(vec_dtype) - 1;
+    if (((uintptr_t)val & vmask) || ((uintptr_t)x & xmask) || ((uintptr_t)y & xmask)) return (int)hipErrorInvalidValue;
+    *forward = val_dtype == DT_F64;
+    if (*forward) return 0;
+    if (fpe < 0 || fpe > 8) return (int)hipErrorInvalidValue;
+    return fpe == 1 ? EXBLAS_UNSUPPORTED : 0;
+}
+
+static int exspmv_lp_on(Ctx &c, int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx, int val_dtype,
+                        const void *d_val, double alpha, int vec_dtype, const void *d_x, double beta, void *d_y, int fpe,
+                        int early_exit, hipStream_t st)
+{
+    bool forward, empty;
+    if (int rc = csr_lp_refused(val_dtype, d_val, vec_dtype, d_x, d_y, fpe, &forward)) return rc;
+    if (forward)
+        return exspmv_on(c, m, n, index_bits, d_row_ptr, d_col_idx, (const double *)d_val, alpha, (const double *)d_x, beta,
+                         (double *)d_y, fpe, early_exit, st);
+    if (int rc = csr_check_args(m, n, 1, index_bits, d_row_ptr, (const double *)d_x, 1, (const double *)d_y, 1, fpe, &empty))
+        return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exspmv_lp_dispatch(c, m, n, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype, d_x, beta,
+                                   d_y, fpe, round_mode(), st);
+}
+
+static int exspmm_lp_on(Ctx &c, int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                        int val_dtype, const void *d_val, double alpha, int vec_dtype, const void *d_x, int64_t ldx,
+                        double beta, void *d_y, int64_t ldy, int fpe, int early_exit, hipStream_t st)
+{
+    bool forward, empty;
+    if (int rc = csr_lp_refused(val_dtype, d_val, vec_dtype, d_x, d_y, fpe, &forward)) return rc;
+    if (forward)
+        return exspmm_on(c, m, n, k, index_bits, d_row_ptr, d_col_idx, (const double *)d_val, alpha, (const double *)d_x,
+                         ldx, beta, (double *)d_y, ldy, fpe, early_exit, st);
+    const int rc = csr_check_args(m, n, k, index_bits, d_row_ptr, (const double *)d_x, ldx, (const double *)d_y, ldy, fpe,
+                                  &empty);
+    if (rc || empty) return rc;
+    std::lock_guard<std::mutex> lk(c.mu);
+    if (c.layer < MAX_LAYERS) g_last_layer[c.device] = c.layer;
+    return (int)exspmm_lp_dispatch(c, m, n, k, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype, d_x,
+                                   ldx, beta, d_y, ldy, fpe, round_mode(), st);
+}
+
+// what the narrow CSR entries refuse without a context: csr_lp_refused, then (unless the fp64 entry takes over) the shape
+// rules of csr_check_args
+static int csr_lp_precheck(int m, int n, int k, int index_bits, const void *row_ptr, int val_dtype, const void *val,
+                           int vec_dtype, const void *x, int64_t ldx, const void *y, int64_t ldy, int fpe)
+{
+    bool forward, empty;
+    if (int rc = csr_lp_refused(val_dtype, val, vec_dtype, x, y, fpe, &forward)) return rc;
+    return csr_check_args(m, n, k, index_bits, row_ptr, (const double *)x, ldx, (const double *)y, ldy, fpe, &empty);
+}
+
 static bool one_of(char ch, const char *set) { return ch != 0 && strchr(set, ch) != nullptr; }
 
 // The argument checks of ExBDOT, on host or device pointers alike.  *empty: nothing to compute (p == 0 or q == 0), which
@@ -1105,6 +1165,75 @@ int exblas_exspmm_csr_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, 
                      early_exit, (hipStream_t)stream);
 }
 
+// The narrow CSR entries refuse bad arguments before they need a device (as the narrow reductions above)
+int exblas_exspmv_csr_lp_ctx(exblas_ctx_t *h, int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                             int val_dtype, const void *d_val, double alpha, int vec_dtype, const void *d_x, double beta,
+                             void *d_y, int fpe, int early_exit, void *stream)
+{
+    if (int rc = csr_lp_precheck(m, n, 1, index_bits, d_row_ptr, val_dtype, d_val, vec_dtype, d_x, 1, d_y, 1, fpe)) return rc;
+    EXB_HANDLE(h);
+    return exspmv_lp_on(*cp, m, n, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype, d_x, beta, d_y, fpe,
+                        early_exit, (hipStream_t)stream);
+}
+
+int exblas_exspmm_csr_lp_ctx(exblas_ctx_t *h, int m, int n, int k, int index_bits, const void *d_row_ptr,
+                             const void *d_col_idx, int val_dtype, const void *d_val, double alpha, int vec_dtype,
+                             const void *d_x, int64_t ldx, double beta, void *d_y, int64_t ldy, int fpe, int early_exit,
+                             void *stream)
+{
+    if (int rc = csr_lp_precheck(m, n, k, index_bits, d_row_ptr, val_dtype, d_val, vec_dtype, d_x, ldx, d_y, ldy, fpe))
+        return rc;
+    EXB_HANDLE(h);
+    return exspmm_lp_on(*cp, m, n, k, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype, d_x, ldx, beta,
+                        d_y, ldy, fpe, early_exit, (hipStream_t)stream);
+}
+
+// The accumulator rounding of the narrow sparse products on the CPU: the leading bit, the 64 bits from it down and "anything
+// below" are taken from the digits one after the other (sp_pick_to, spmv_common.hip.h, takes them with the wave), then
+// round_window_to rounds them -- so the CPU suite can hold that function to round_digits_to and the integer model.
+int exblas_round_window_host(const int64_t *digits68, int dtype, uint64_t *bits)
+{
+    if (!digits68 || !bits || !dtype_known(dtype)) return (int)hipErrorInvalidValue;
+    const bool neg = digits68[NL - 1] < 0;
+    unsigned mag[NL];
+    unsigned long long carry = 1;
+    for (int i = 0; i < NL; ++i) {
+        const unsigned d = (unsigned)digits68[i];
+        if (!neg) {
+            mag[i] = d;
+        } else {
+            const unsigned long long t = (unsigned long long)(~d) + carry;
+            mag[i] = (unsigned)t;
+            carry = t >> 32;
+        }
+    }
+    int tp = NL - 1;
+    while (tp >= 0 && mag[tp] == 0) --tp;
+    *bits = 0;
+    if (tp < 0) return 0;
+    int z = 0;
+    while (mag[z] == 0) ++z;
+    const unsigned mt = mag[tp], ma = tp >= 1 ? mag[tp - 1] : 0u, mb = tp >= 2 ? mag[tp - 2] : 0u;
+    const int lz = __builtin_clz(mt);
+    unsigned long long w = ((unsigned long long)mt << 32) | ma;
+    unsigned rest = mb;
+    if (lz) {
+        w = (w << lz) | (unsigned long long)(mb >> (32 - lz));
+        rest = mb << lz;
+    }
+    *bits = round_window_to(neg, 32 * tp + 31 - lz, w, rest != 0 || z < tp - 2, dtype);
+    return 0;
+}
+
+int exblas_round_interval_host(double res, double bound, int dtype, uint64_t *bits)
+{
+    if (!bits || !dtype_known(dtype)) return -(int)hipErrorInvalidValue;   // (1 and 0 are answers)
+    unsigned long long b = 0;
+    const int ok = round_interval_to(res, bound, dtype, &b);
+    *bits = ok ? b : 0;
+    return ok;
+}
+
 // The three ExBDOT entries refuse bad arguments, or return 0 for an empty problem, before they need a device: the check
 // comes before the default context is created (a handle on the wrong device is still refused first).
 int exblas_exbdot_ctx(exblas_ctx_t *h, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
@@ -1397,6 +1526,20 @@ int exblas_exspmv_csr_dev(int m, int n, int index_bits, const void *d_row_ptr, c
 {
     return exblas_exspmv_csr_ctx(nullptr, m, n, index_bits, d_row_ptr, d_col_idx, d_val, alpha, d_x, beta, d_y, fpe,
                                  early_exit, stream);
+}
+int exblas_exspmv_csr_lp_dev(int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx, int val_dtype,
+                             const void *d_val, double alpha, int vec_dtype, const void *d_x, double beta, void *d_y, int fpe,
+                             int early_exit, void *stream)
+{
+    return exblas_exspmv_csr_lp_ctx(nullptr, m, n, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype, d_x,
+                                    beta, d_y, fpe, early_exit, stream);
+}
+int exblas_exspmm_csr_lp_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                             int val_dtype, const void *d_val, double alpha, int vec_dtype, const void *d_x, int64_t ldx,
+                             double beta, void *d_y, int64_t ldy, int fpe, int early_exit, void *stream)
+{
+    return exblas_exspmm_csr_lp_ctx(nullptr, m, n, k, index_bits, d_row_ptr, d_col_idx, val_dtype, d_val, alpha, vec_dtype,
+                                    d_x, ldx, beta, d_y, ldy, fpe, early_exit, stream);
 }
 int exblas_exspmm_csr_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
                           const double *d_val, double alpha, const double *d_x, int64_t ldx, double beta, double *d_y,
@@ -1832,13 +1975,14 @@ int exblas_extrsv(char uplo, char transa, char diag, int n, const double *a, int
 // The host-pointer CSR call: Y (m x k, row stride ldy) from X (n x k, row stride ldx); ExSpMV is k = 1, ldx = ldy = 1.
 // One staging block [row_ptr | col_idx | val | X | Y] goes to the device, launch(c, d_row_ptr, d_col_idx, d_val, d_x, d_y)
 // runs the routine on the context's stream, and Y comes back.  ywords != 0: Y is that many words, not an m x k block.
+// vsz, xsz: bytes of an element of val, and of X and Y (the narrow entries; launch still sees them as double pointers).
 template <class Launch>
 static int csr_host_call(const char *who, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
-                         const double *val, const double *x, int64_t ldx, double *y, int64_t ldy, int fpe,
-                         Launch &&launch, size_t ywords = 0)
+                         const void *val, const void *x, int64_t ldx, void *y, int64_t ldy, int fpe,
+                         Launch &&launch, size_t ywords = 0, size_t vsz = 8, size_t xsz = 8)
 {
     bool empty;
-    const int bad = csr_check_args(m, n, k, index_bits, row_ptr, x, ldx, y, ldy, fpe, &empty);
+    const int bad = csr_check_args(m, n, k, index_bits, row_ptr, (const double *)x, ldx, (const double *)y, ldy, fpe, &empty);
     if (bad || empty) return bad;
     // the entries the call reads: [0, max row_ptr); a negative row_ptr entry is refused
     const size_t isz = index_bits / 8;
@@ -1854,17 +1998,17 @@ static int csr_host_call(const char *who, int m, int n, int k, int index_bits, c
     const size_t xspan = n > 0 ? (size_t)(n - 1) * (size_t)ldx + (size_t)k : 0;
     const size_t yspan = ywords ? ywords : (size_t)(m - 1) * (size_t)ldy + (size_t)k;
     const size_t b_rp = align_up((size_t)(m + 1) * isz), b_ci = align_up((size_t)nnz * isz),
-                 b_val = align_up((size_t)nnz * 8), b_x = align_up(xspan * 8), b_y = align_up(yspan * 8);
+                 b_val = align_up((size_t)nnz * vsz), b_x = align_up(xspan * xsz), b_y = align_up(yspan * xsz);
     char *d = (char *)hc.in(0, b_rp + b_ci + b_val + b_x + b_y, row_ptr, (size_t)(m + 1) * isz);
     char *d_val = d + b_rp + b_ci, *d_x = d_val + b_val, *d_y = d_x + b_x;
     hc.h2d(d + b_rp, col_idx, (size_t)nnz * isz);
-    hc.h2d(d_val, val, (size_t)nnz * 8);
-    hc.h2d(d_x, x, xspan * 8);
-    hc.h2d(d_y, y, yspan * 8);
+    hc.h2d(d_val, val, (size_t)nnz * vsz);
+    hc.h2d(d_x, x, xspan * xsz);
+    hc.h2d(d_y, y, yspan * xsz);
     // the padding of Y comes back as it went
     return hc.out(launch(hc.c, (const void *)d, (const void *)(d + b_rp), (const double *)d_val, (const double *)d_x,
                          (double *)d_y),
-                  y, d_y, yspan * 8);
+                  y, d_y, yspan * xsz);
 }
 
 // what a host solve returns after its csr_host_call: the status of the layer-1 context's last solve
@@ -1925,6 +2069,35 @@ int exblas_exspmm_csr(int m, int n, int k, int index_bits, const void *row_ptr, 
                              return exspmm_on(c, m, n, k, index_bits, d_rp, d_ci, d_val, alpha, d_x, ldx, beta, d_y, ldy, fpe,
                                               early_exit, c.stream);
                          });
+}
+
+// the narrow products on host arrays stage through the current device as the fp64 ones do
+int exblas_exspmv_csr_lp(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, int val_dtype,
+                         const void *val, double alpha, int vec_dtype, const void *x, double beta, void *y, int fpe,
+                         int early_exit)
+{
+    if (int rc = csr_lp_precheck(m, n, 1, index_bits, row_ptr, val_dtype, val, vec_dtype, x, 1, y, 1, fpe)) return rc;
+    return csr_host_call(
+        "exblas_exspmv_csr_lp", m, n, 1, index_bits, row_ptr, col_idx, val, x, 1, y, 1, fpe,
+        [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *d_x, double *d_y) {
+            return exspmv_lp_on(c, m, n, index_bits, d_rp, d_ci, val_dtype, d_val, alpha, vec_dtype, d_x, beta, d_y, fpe,
+                                early_exit, c.stream);
+        },
+        0, (size_t)dtype_bytes(val_dtype), (size_t)dtype_bytes(vec_dtype));
+}
+
+int exblas_exspmm_csr_lp(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, int val_dtype,
+                         const void *val, double alpha, int vec_dtype, const void *x, int64_t ldx, double beta, void *y,
+                         int64_t ldy, int fpe, int early_exit)
+{
+    if (int rc = csr_lp_precheck(m, n, k, index_bits, row_ptr, val_dtype, val, vec_dtype, x, ldx, y, ldy, fpe)) return rc;
+    return csr_host_call(
+        "exblas_exspmm_csr_lp", m, n, k, index_bits, row_ptr, col_idx, val, x, ldx, y, ldy, fpe,
+        [&](Ctx &c, const void *d_rp, const void *d_ci, const double *d_val, const double *d_x, double *d_y) {
+            return exspmm_lp_on(c, m, n, k, index_bits, d_rp, d_ci, val_dtype, d_val, alpha, vec_dtype, d_x, ldx, beta, d_y,
+                                ldy, fpe, early_exit, c.stream);
+        },
+        0, (size_t)dtype_bytes(val_dtype), (size_t)dtype_bytes(vec_dtype));
 }
 
 // the shared CSR host path with no X: x (b on entry, the solution on return) travels as its Y

@@ -228,11 +228,19 @@ hipError_t exgemm_dispatch(Ctx &c, char transa, char transb, int m, int n, int k
 hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
                            const double *val, double alpha, const double *x, double beta, double *y, int fpe,
                            int early_exit, int round_mode, hipStream_t st);
+// values of val_dtype (DT_F32 / DT_F16 / DT_BF16), x and y of vec_dtype (DT_F64 or val_dtype), fpe 0 or 2..8: all checked
+// by the caller
+hipError_t exspmv_lp_dispatch(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
+                              int val_dtype, const void *val, double alpha, int vec_dtype, const void *x, double beta,
+                              void *y, int fpe, int round_mode, hipStream_t st);
 
 // spmm.hip
 hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
                            const double *val, double alpha, const double *x, long long ldx, double beta, double *y,
                            long long ldy, int fpe, int early_exit, int round_mode, hipStream_t st);
+hipError_t exspmm_lp_dispatch(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                              int val_dtype, const void *val, double alpha, int vec_dtype, const void *x, long long ldx,
+                              double beta, void *y, long long ldy, int fpe, int round_mode, hipStream_t st);
 
 // sptrsv.hip
 hipError_t exsptrsv_dispatch(Ctx &c, char uplo, char diag, int m, int index_bits, const void *row_ptr, const void *col_idx,

@@ -25,6 +25,8 @@
 //                     accumulators (order-free)
 //   k_spmm_long_finish one wave per (split row, column): beta term, finish_wave, store
 // fpe == 1 runs the same structure with plain fp64 sums (nothing is deferred).
+// Narrow entries (exspmm_lp_dispatch): as in spmv.hip, the kernels are templates on the element types VT (values) and XT
+// (X and Y); <LpF64, LpF64> is the fp64 routine, ldx and ldy count elements.
 #include "spmv_common.hip.h"
 
 namespace exb {
@@ -52,12 +54,12 @@ struct AccSink {
     __device__ __forceinline__ void note(unsigned) {}
 };
 
-// fl(alpha * X[c, j]) for an in-range column; a column outside [0, n) is never read and makes the row NaN
-template <class I>
-__device__ __forceinline__ double gather_xj(const double *__restrict__ xj, I c, long long ldx, int n, double alpha,
-                                            unsigned &flags)
+// fl(alpha * W(X[c, j])) for an in-range column; a column outside [0, n) is never read and makes the row NaN
+template <class XT, class I>
+__device__ __forceinline__ double gather_xj(const typename XT::elem *__restrict__ xj, I c, long long ldx, int n,
+                                            double alpha, unsigned &flags)
 {
-    if ((unsigned long long)(long long)c < (unsigned long long)n) return alpha * xj[(long long)c * ldx];
+    if ((unsigned long long)(long long)c < (unsigned long long)n) return alpha * XT::widen(xj[(long long)c * ldx]);
     flags |= FLAG_NAN | SP_SPILL;
     return 0.0;
 }
@@ -140,11 +142,11 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_classify(int m, int k, const 
 // ---------------------------------------------------------------------------------------------
 // main kernel: lanes own columns
 // ---------------------------------------------------------------------------------------------
-template <bool WIDE, bool PLAIN, class I>
+template <bool WIDE, bool PLAIN, class VT, class XT, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmm_main(int m, int n, int k, ItemGeom geo, const I *__restrict__ rp,
-                                                       const I *__restrict__ ci, const double *__restrict__ val,
-                                                       double alpha, const double *__restrict__ x, long long ldx,
-                                                       double beta, double *__restrict__ y, long long ldy,
+                                                       const I *__restrict__ ci, const typename VT::elem *__restrict__ val,
+                                                       double alpha, const typename XT::elem *__restrict__ x, long long ldx,
+                                                       double beta, typename XT::elem *__restrict__ y, long long ldy,
                                                        long long long_min, const int *__restrict__ lslot,
                                                        unsigned long long *__restrict__ bm, long long nitems,
                                                        long long *__restrict__ hdr, int force_defer)
@@ -165,13 +167,13 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_main(int m, int n, int k, Ite
             if (p1 - p0 > long_min && lslot[row] >= 0) active = false;   // split row: other kernels
         }
         if (!active || force_defer) p1 = p0;   // forced: k_spmm_deferred does all the work
-        const double *xj = x + j;
-        double *yp = y + row * ldy + j;
+        const typename XT::elem *xj = x + j;
+        typename XT::elem *yp = y + row * ldy + j;
         unsigned flags = 0;
         if constexpr (PLAIN) {
             double s = 0.0;
             for (long long p = p0; __any(p < p1); ++p) {
-                if (p < p1) s += val[p] * gather_xj(xj, ci[p], ldx, n, alpha, flags);
+                if (p < p1) s += val[p] * gather_xj<XT>(xj, ci[p], ldx, n, alpha, flags);
             }
             if (flags & FLAG_NAN) s = __builtin_nan("");
             if (active) *yp = (beta == 0.0) ? s : s + beta * *yp;
@@ -190,25 +192,31 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_main(int m, int n, int k, Ite
                     a[u] = 0.0;
                     if (q < p1) {
                         c[u] = ci[q];
-                        a[u] = val[q];
+                        a[u] = VT::widen(val[q]);
                     }
                 }
 #pragma unroll
                 for (int u = 0; u < SM_U; ++u) {
                     xv[u] = 0.0;
-                    if (q0 + u < p1) xv[u] = gather_xj(xj, c[u], ldx, n, alpha, flags);
+                    if (q0 + u < p1) xv[u] = gather_xj<XT>(xj, c[u], ldx, n, alpha, flags);
                 }
 #pragma unroll
                 for (int u = 0; u < SM_U; ++u) p[u] = two_prod(a[u], xv[u], er[u]);
                 fpe_absorb_prod<SP_N, true, SM_U>(f, p, er, sink);
                 if (!__any(active && flags == 0)) break;   // every output of the item is deferred already
             }
-            sp_absorb_beta(f, active, beta, yp, 0, sink);
+            sp_absorb_beta<XT>(f, active, beta, yp, 0, sink);
             bool defer = false;
             if (active) {
-                double r;
-                if (!force_defer && flags == 0 && spmv_round_fast<SP_N>(f, r)) *yp = r;
-                else defer = true;
+                if constexpr (XT::DT == DT_F64) {   // (the fp64 kernel's own lines: its code stays what it was)
+                    double r;
+                    if (!force_defer && flags == 0 && spmv_round_fast<SP_N>(f, r)) *yp = r;
+                    else defer = true;
+                } else {
+                    unsigned long long r;
+                    if (!force_defer && flags == 0 && sp_round_fast_to<XT, SP_N>(f, r)) XT::store(yp, r);
+                    else defer = true;
+                }
             }
             const unsigned long long dm = __ballot(defer);
             if (lane == 0) bm[item] = dm;
@@ -226,12 +234,13 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_main(int m, int n, int k, Ite
 // deferred outputs: integer accumulator in LDS, finish_wave
 // ---------------------------------------------------------------------------------------------
 // up to 64 / G2 of the outputs listed in `bits` (an item's bitmap word), one per group of G2 lanes; returns the rest
-template <int G2, class I>
+template <int G2, class VT, class XT, class I>
 __device__ __forceinline__ unsigned long long spmm_finish_some(unsigned long long bits, long long item, ItemGeom geo,
                                                                int n, const I *__restrict__ rp, const I *__restrict__ ci,
-                                                               const double *__restrict__ val, double alpha,
-                                                               const double *__restrict__ x, long long ldx, double beta,
-                                                               double *__restrict__ y, long long ldy,
+                                                               const typename VT::elem *__restrict__ val, double alpha,
+                                                               const typename XT::elem *__restrict__ x, long long ldx,
+                                                               double beta, typename XT::elem *__restrict__ y,
+                                                               long long ldy,
                                                                long long (*acc)[NL], int round_mode)
 {
     constexpr int NOUT = 64 / G2;
@@ -253,15 +262,15 @@ __device__ __forceinline__ unsigned long long spmm_finish_some(unsigned long lon
         j = geo.col(item, bit);
         const long long p0 = (long long)rp[row], p1 = max(p0, (long long)rp[row + 1]);
         AccSink sink{acc[grp], flags};
-        const double *xj = x + j;
+        const typename XT::elem *xj = x + j;
         for (long long p = p0 + sub; p < p1; p += G2) {
             double e;
-            const double a = ld_nt(val + p);
-            const double pr = two_prod(a, gather_xj(xj, ld_nt(ci + p), ldx, n, alpha, flags), e);
+            const double a = VT::widen(ld_nt(val + p));
+            const double pr = two_prod(a, gather_xj<XT>(xj, ld_nt(ci + p), ldx, n, alpha, flags), e);
             sink_product(sink, pr, e);
         }
         if (sub == 0 && beta != 0.0) {
-            const double yv = y[row * ldy + j];
+            const double yv = XT::widen(y[row * ldy + j]);
             if (beta == 1.0) {
                 sink.add(yv);
             } else {
@@ -275,19 +284,26 @@ __device__ __forceinline__ unsigned long long spmm_finish_some(unsigned long lon
     const NonFiniteLanes nf(flags);
     for (int s = 0; s < count; ++s) {   // wave-uniform: every lane runs the finish of each output
         const unsigned long long gm = G2 == 64 ? ~0ull : (((1ull << (G2 & 63)) - 1ull) << (s * (G2 & 63)));
-        const double v = sp_acc_round(acc[s], nf.of(gm), round_mode);
-        const long long o_row = __shfl(row, s * G2, 64), o_j = __shfl(j, s * G2, 64);
-        if (lane == 0) y[o_row * ldy + o_j] = v;
+        if constexpr (XT::DT == DT_F64) {   // (the fp64 kernel's own lines: its code stays what it was)
+            const double v = sp_acc_round(acc[s], nf.of(gm), round_mode);
+            const long long o_row = __shfl(row, s * G2, 64), o_j = __shfl(j, s * G2, 64);
+            if (lane == 0) y[o_row * ldy + o_j] = v;
+        } else {
+            const unsigned long long v = sp_acc_round_to<XT>(acc[s], nf.of(gm), round_mode);
+            const long long o_row = __shfl(row, s * G2, 64), o_j = __shfl(j, s * G2, 64);
+            if (lane == 0) XT::store(y + (o_row * ldy + o_j), v);
+        }
     }
     sp_wave_sync();
     return bits;
 }
 
-template <class I>
+template <class VT, class XT, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmm_deferred(int m, int n, ItemGeom geo, const I *__restrict__ rp,
-                                                           const I *__restrict__ ci, const double *__restrict__ val,
-                                                           double alpha, const double *__restrict__ x, long long ldx,
-                                                           double beta, double *__restrict__ y, long long ldy,
+                                                           const I *__restrict__ ci,
+                                                           const typename VT::elem *__restrict__ val, double alpha,
+                                                           const typename XT::elem *__restrict__ x, long long ldx,
+                                                           double beta, typename XT::elem *__restrict__ y, long long ldy,
                                                            const unsigned long long *__restrict__ bm, long long nitems,
                                                            int span, int round_mode)
 {
@@ -316,12 +332,12 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_deferred(int m, int n, ItemGe
             }
             if (__any(is_long)) {
                 while (bits)
-                    bits = spmm_finish_some<64>(bits, item, geo, n, rp, ci, val, alpha, x, ldx, beta, y, ldy, acc[w],
+                    bits = spmm_finish_some<64, VT, XT>(bits, item, geo, n, rp, ci, val, alpha, x, ldx, beta, y, ldy, acc[w],
                                                 round_mode);
             } else {
                 while (bits)
-                    bits = spmm_finish_some<SM_DEF_G>(bits, item, geo, n, rp, ci, val, alpha, x, ldx, beta, y, ldy,
-                                                      acc[w], round_mode);
+                    bits = spmm_finish_some<SM_DEF_G, VT, XT>(bits, item, geo, n, rp, ci, val, alpha, x, ldx, beta, y,
+                                                              ldy, acc[w], round_mode);
             }
         }
     }
@@ -330,10 +346,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_deferred(int m, int n, ItemGe
 // ---------------------------------------------------------------------------------------------
 // split rows: chunks into the row's k global accumulators, finish
 // ---------------------------------------------------------------------------------------------
-template <bool PLAIN, class I>
+template <bool PLAIN, class VT, class XT, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long(int n, int k, ItemGeom geo, const I *__restrict__ rp,
-                                                       const I *__restrict__ ci, const double *__restrict__ val,
-                                                       double alpha, const double *__restrict__ x, long long ldx,
+                                                       const I *__restrict__ ci, const typename VT::elem *__restrict__ val,
+                                                       double alpha, const typename XT::elem *__restrict__ x, long long ldx,
                                                        const int *__restrict__ lrows, const long long *__restrict__ lbase,
                                                        int lcap, long long chunk, long long *__restrict__ hdr,
                                                        long long *__restrict__ lacc)
@@ -352,14 +368,14 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long(int n, int k, ItemGeom g
         const long long p0 = r0 + (t - lbase[lo]) * chunk, p1 = min(r1, p0 + chunk);
         const bool active = j < k;
         long long *g = lacc + (lo * (long long)k + (active ? j : 0)) * SET_WORDS;
-        const double *xj = x + j;
+        const typename XT::elem *xj = x + j;
         unsigned flags = 0;
         if (u % geo.tiles == 0) ++n_chunks;
         if constexpr (PLAIN) {
             double s = 0.0;
             if (active)
                 for (long long p = p0 + part; p < p1; p += nparts)
-                    s += ld_nt(val + p) * gather_xj(xj, ld_nt(ci + p), ldx, n, alpha, flags);
+                    s += ld_nt(val + p) * gather_xj<XT>(xj, ld_nt(ci + p), ldx, n, alpha, flags);
             if (flags & FLAG_NAN) s = __builtin_nan("");
             if (active) atomicAdd((double *)g, s);
         } else {
@@ -374,8 +390,8 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long(int n, int k, ItemGeom g
                     const long long q = q0 + (long long)v * nparts;
                     double a = 0.0, xv = 0.0;
                     if (active && q < p1) {
-                        a = ld_nt(val + q);
-                        xv = gather_xj(xj, ld_nt(ci + q), ldx, n, alpha, flags);
+                        a = VT::widen(ld_nt(val + q));
+                        xv = gather_xj<XT>(xj, ld_nt(ci + q), ldx, n, alpha, flags);
                     }
                     p[v] = two_prod(a, xv, er[v]);
                 }
@@ -388,9 +404,9 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long(int n, int k, ItemGeom g
     if (lane == 0 && n_chunks) atomicAdd((unsigned long long *)&hdr[7], n_chunks);
 }
 
-template <bool PLAIN>
+template <bool PLAIN, class XT>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int *__restrict__ lrows, int lcap,
-                                                              double beta, double *__restrict__ y, long long ldy,
+                                                              double beta, typename XT::elem *__restrict__ y, long long ldy,
                                                               long long *__restrict__ hdr,
                                                               const long long *__restrict__ lacc, int round_mode)
 {
@@ -399,7 +415,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int 
     const long long wave0 = (long long)blockIdx.x * SP_WAVES + w, nwaves = (long long)gridDim.x * SP_WAVES;
     for (long long o = wave0; o < nl * k; o += nwaves) {
         const long long i = o / k, j = o % k;
-        double *yp = y + (long long)lrows[i] * ldy + j;
+        typename XT::elem *yp = y + (long long)lrows[i] * ldy + j;
         const long long *g = lacc + o * SET_WORDS;
         if constexpr (PLAIN) {
             const double s = __longlong_as_double(g[0]);
@@ -407,9 +423,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int 
         } else {
             long long v0 = g[lane], v1 = lane < NL - 64 ? g[64 + lane] : 0;
             unsigned flags = (g[NL] ? FLAG_PINF : 0u) | (g[NL + 1] ? FLAG_NINF : 0u) | (g[NL + 2] ? FLAG_NAN : 0u);
-            sp_wave_add_beta(v0, v1, beta, yp, 0, flags);
+            sp_wave_add_beta<XT>(v0, v1, beta, yp, 0, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
-            if (lane == 0) *yp = sp_pick(r, round_mode);
+            const unsigned long long v = sp_pick_to<XT>(r, flags, round_mode);
+            if (lane == 0) XT::store(yp, v);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) hdr[6] = nl;
@@ -418,10 +435,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmm_long_finish(int k, const int 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-template <bool PLAIN, class I>
-static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I *ci, const double *val, double alpha,
-                              const double *x, long long ldx, double beta, double *y, long long ldy, int force_defer,
-                              int round_mode, hipStream_t st)
+template <bool PLAIN, class VT, class XT, class I>
+static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I *ci, const typename VT::elem *val,
+                              double alpha, const typename XT::elem *x, long long ldx, double beta, typename XT::elem *y,
+                              long long ldy, int force_defer, int round_mode, hipStream_t st)
 {
     const SplitRule split = sp_split_rule(c.spmm_path, SM_LONG_MIN, SM_CHUNK);
     const long long long_min = split.long_min;
@@ -454,23 +471,23 @@ static hipError_t spmm_launch(Ctx &c, int m, int n, int k, const I *rp, const I 
                        lcap, hdr, lslot, lrows, lacc);
     const int grid = (int)min((long long)cap, (nitems + SP_WAVES - 1) / SP_WAVES);
     if (geo.lg == 6)
-        hipLaunchKernelGGL((k_spmm_main<true, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, k, geo, rp, ci, val,
+        hipLaunchKernelGGL((k_spmm_main<true, PLAIN, VT, XT, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, k, geo, rp, ci, val,
                            alpha, x, ldx, beta, y, ldy, long_min, (const int *)lslot, bm, nitems, hdr, force_defer);
     else
-        hipLaunchKernelGGL((k_spmm_main<false, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, k, geo, rp, ci, val,
+        hipLaunchKernelGGL((k_spmm_main<false, PLAIN, VT, XT, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, k, geo, rp, ci, val,
                            alpha, x, ldx, beta, y, ldy, long_min, (const int *)lslot, bm, nitems, hdr, force_defer);
     if constexpr (!PLAIN) {
         const long long span = max(1ll, min(64ll, nitems / ((long long)cap * SP_WAVES)));
         const int gd = (int)min((long long)cap, (nitems + span * SP_WAVES - 1) / (span * SP_WAVES));
-        hipLaunchKernelGGL((k_spmm_deferred<I>), dim3(gd), dim3(SP_BLOCK), 0, st, m, n, geo, rp, ci, val, alpha, x, ldx,
+        hipLaunchKernelGGL((k_spmm_deferred<VT, XT, I>), dim3(gd), dim3(SP_BLOCK), 0, st, m, n, geo, rp, ci, val, alpha, x, ldx,
                            beta, y, ldy, (const unsigned long long *)bm, nitems, (int)span, round_mode);
     }
     hipLaunchKernelGGL((k_spmv_long_prep<I>), dim3(1), dim3(1024), 0, st, rp, (const int *)lrows, lcap, chunk, hdr, lbase);
-    hipLaunchKernelGGL((k_spmm_long<PLAIN, I>), dim3(cap), dim3(SP_BLOCK), 0, st, n, k, geo, rp, ci, val, alpha, x, ldx,
+    hipLaunchKernelGGL((k_spmm_long<PLAIN, VT, XT, I>), dim3(cap), dim3(SP_BLOCK), 0, st, n, k, geo, rp, ci, val, alpha, x, ldx,
                        (const int *)lrows, (const long long *)lbase, lcap, chunk, hdr, lacc);
     {
         const int gl = (int)min((long long)c.num_cu * 2, ((long long)lcap * k + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((k_spmm_long_finish<PLAIN>), dim3(max(gl, 1)), dim3(SP_BLOCK), 0, st, k, (const int *)lrows,
+        hipLaunchKernelGGL((k_spmm_long_finish<PLAIN, XT>), dim3(max(gl, 1)), dim3(SP_BLOCK), 0, st, k, (const int *)lrows,
                            lcap, beta, y, ldy, hdr, (const long long *)lacc, round_mode);
     }
     return hipGetLastError();
@@ -486,9 +503,46 @@ hipError_t exspmm_dispatch(Ctx &c, int m, int n, int k, int index_bits, const vo
     const int force_defer = (fpe == 0 || c.spmm_path == 1 || round_mode) ? 1 : 0;
     return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
         constexpr bool PLAIN = decltype(plain)::value;   // the plain kernels neither defer nor round
-        return spmm_launch<PLAIN>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy, PLAIN ? 0 : force_defer,
-                                  PLAIN ? 0 : round_mode, st);
+        return spmm_launch<PLAIN, LpF64, LpF64>(c, m, n, k, rp, ci, val, alpha, x, ldx, beta, y, ldy,
+                                                PLAIN ? 0 : force_defer, PLAIN ? 0 : round_mode, st);
     });
+}
+
+// The narrow entry, as exspmv_lp_dispatch (spmv.hip): values of val_dtype, X and Y of vec_dtype (float64 or val_dtype; the
+// caller has checked the pair and that fpe != 1); ldx and ldy in elements
+template <class VT, class XT>
+static hipError_t spmm_lp_typed(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                                const void *val, double alpha, const void *x, long long ldx, double beta, void *y,
+                                long long ldy, int force_defer, int round_mode, hipStream_t st)
+{
+    return sp_dispatch(index_bits, 0, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
+        if constexpr (decltype(plain)::value) return hipErrorInvalidValue;   // (fpe = 0 was passed: never taken)
+        else
+            return spmm_launch<false, VT, XT>(c, m, n, k, rp, ci, (const typename VT::elem *)val, alpha,
+                                              (const typename XT::elem *)x, ldx, beta, (typename XT::elem *)y, ldy,
+                                              force_defer, round_mode, st);
+    });
+}
+
+hipError_t exspmm_lp_dispatch(Ctx &c, int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx,
+                              int val_dtype, const void *val, double alpha, int vec_dtype, const void *x, long long ldx,
+                              double beta, void *y, long long ldy, int fpe, int round_mode, hipStream_t st)
+{
+    if (m == 0 || k == 0) return hipSuccess;
+    const int force_defer = (fpe == 0 || c.spmm_path == 1 || round_mode) ? 1 : 0;
+    hipError_t e = hipErrorInvalidValue;
+    auto run = [&](auto vt, auto xt) {
+        e = spmm_lp_typed<decltype(vt), decltype(xt)>(c, m, n, k, index_bits, row_ptr, col_idx, val, alpha, x, ldx, beta,
+                                                      y, ldy, force_defer, round_mode, st);
+    };
+    auto by_value = [&](auto vt) {
+        if (vec_dtype == DT_F64) run(vt, LpF64());
+        else run(vt, vt);
+    };
+    if (val_dtype == DT_F32) by_value(LpF32());
+    else if (val_dtype == DT_F16) by_value(LpF16());
+    else if (val_dtype == DT_BF16) by_value(LpBF16());
+    return e;
 }
 
 }  // namespace exb

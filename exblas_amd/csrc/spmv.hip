@@ -19,6 +19,12 @@
 //                     row's global accumulator (order-free)
 //   k_spmv_long_finish one wave per long row: beta terms, finish_wave, store
 // fpe == 1 runs the same structure with plain fp64 sums (the non-reproducible baseline).
+//
+// Narrow entries (exspmv_lp_dispatch): the kernels are templates on VT, the element type of the values, and XT, that of
+// x and y (lowp_types.hip.h); <LpF64, LpF64> is the fp64 routine.  A narrow element is loaded at its own width and
+// widened exactly, so the multiset {p, e} is the one of the fp64 entry on the widened operands (e = 0 when both factors
+// are narrow).  A narrow y is rounded ONCE from that exact sum: in registers behind the interval certificate
+// (sp_round_fast_to), or from the accumulator's digits (sp_pick_to) -- never from the rounded double.
 #include "spmv_common.hip.h"
 
 namespace exb {
@@ -60,11 +66,11 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_classify(int m, const I *__re
 // ---------------------------------------------------------------------------------------------
 // one row per group of G lanes (8 short, 64 medium); persistent waves over batches of 64 / G rows
 // ---------------------------------------------------------------------------------------------
-template <int G, bool LIST, bool PLAIN, class I>
+template <int G, bool LIST, bool PLAIN, class VT, class XT, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *__restrict__ rp, const I *__restrict__ ci,
-                                                       const double *__restrict__ val, double alpha,
-                                                       const double *__restrict__ x, double beta, double *__restrict__ y,
-                                                       long long short_max, const int *__restrict__ list,
+                                                       const typename VT::elem *__restrict__ val, double alpha,
+                                                       const typename XT::elem *__restrict__ x, double beta,
+                                                       typename XT::elem *__restrict__ y, long long short_max, const int *__restrict__ list,
                                                        long long *__restrict__ hdr, int force_fb, int round_mode)
 {
     constexpr int RPW = 64 / G;   // rows per wave and batch
@@ -96,7 +102,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
             for (long long k = p0 + sub; k < p1; k += G) {
                 const I c = ld_nt(ci + k);
                 const double v = ld_nt(val + k);
-                s += v * gather_x(x, c, n, alpha, flags);
+                s += v * gather_x<XT>(x, c, n, alpha, flags);
             }
             if (flags & FLAG_NAN) s = __builtin_nan("");
 #pragma unroll
@@ -115,23 +121,29 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
                     double a = 0.0, xv = 0.0;
                     if (k < p1) {
                         const I c = ld_nt(ci + k);
-                        a = ld_nt(val + k);
-                        xv = gather_x(x, c, n, alpha, flags);
+                        a = VT::widen(ld_nt(val + k));
+                        xv = gather_x<XT>(x, c, n, alpha, flags);
                     }
                     p[j] = two_prod(a, xv, er[j]);
                 }
                 fpe_absorb_prod<SP_N, true, U>(f, p, er, sink);
             }
-            sp_absorb_beta(f, valid && sub == 0, beta, y, row, sink);
+            sp_absorb_beta<XT>(f, valid && sub == 0, beta, y, row, sink);
             // exact tree merge of the group's expansions into its first lane
 #pragma unroll
             for (int s = 1; s < G; s <<= 1) sp_cascade_step(f, flags, s, (sub & (2 * s - 1)) == 0, sink);
             const bool leader = valid && sub == 0;
             bool fb = false;
             if (leader) {
-                double r;
-                fb = !sp_certify_or_spill(f, flags, force_fb, acc[w][slot], r);
-                if (!fb) y[row] = r;
+                if constexpr (XT::DT == DT_F64) {   // (the fp64 kernel's own lines, here and below: its code stays what it was)
+                    double r;
+                    fb = !sp_certify_or_spill(f, flags, force_fb, acc[w][slot], r);
+                    if (!fb) y[row] = r;
+                } else {
+                    unsigned long long r;
+                    fb = !sp_certify_or_spill_to<XT>(f, flags, force_fb, acc[w][slot], r);
+                    if (!fb) XT::store(y + row, r);
+                }
             }
             n_reg += __popcll(__ballot(leader && !fb));
             unsigned long long fbm = __ballot(fb);
@@ -143,8 +155,13 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
                     fbm &= fbm - 1ull;
                     const unsigned fl = (unsigned)__shfl((int)flags, l, 64) & FLAG_NONFINITE;
                     const long long r_row = __shfl(row, l, 64);
-                    const double v = sp_acc_round(acc[w][sl], fl, round_mode);
-                    if (lane == 0) y[r_row] = v;
+                    if constexpr (XT::DT == DT_F64) {
+                        const double v = sp_acc_round(acc[w][sl], fl, round_mode);
+                        if (lane == 0) y[r_row] = v;
+                    } else {
+                        const unsigned long long v = sp_acc_round_to<XT>(acc[w][sl], fl, round_mode);
+                        if (lane == 0) XT::store(y + r_row, v);
+                    }
                     sp_wave_sync();
                 }
             }
@@ -159,10 +176,11 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_rows(int m, int n, const I *_
 // ---------------------------------------------------------------------------------------------
 // long rows: chunks, finish (the chunk bases come from k_spmv_long_prep, spmv_common.hip.h)
 // ---------------------------------------------------------------------------------------------
-template <bool PLAIN, class I>
+template <bool PLAIN, class VT, class XT, class I>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restrict__ rp, const I *__restrict__ ci,
-                                                       const double *__restrict__ val, double alpha,
-                                                       const double *__restrict__ x, const int *__restrict__ lrows,
+                                                       const typename VT::elem *__restrict__ val, double alpha,
+                                                       const typename XT::elem *__restrict__ x,
+                                                       const int *__restrict__ lrows,
                                                        const long long *__restrict__ lbase, int lcap, long long chunk,
                                                        long long *__restrict__ hdr, long long *__restrict__ lacc)
 {
@@ -185,7 +203,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restri
         ++n_chunks;
         if constexpr (PLAIN) {
             double s = 0.0;
-            for (long long k = p0 + lane; k < p1; k += 64) s += ld_nt(val + k) * gather_x(x, ld_nt(ci + k), n, alpha, flags);
+            for (long long k = p0 + lane; k < p1; k += 64) s += ld_nt(val + k) * gather_x<XT>(x, ld_nt(ci + k), n, alpha, flags);
             if (flags & FLAG_NAN) s = __builtin_nan("");
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
@@ -202,8 +220,8 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restri
                     const long long k = k0 + lane + 64 * j;
                     double a = 0.0, xv = 0.0;
                     if (k < p1) {
-                        a = ld_nt(val + k);
-                        xv = gather_x(x, ld_nt(ci + k), n, alpha, flags);
+                        a = VT::widen(ld_nt(val + k));
+                        xv = gather_x<XT>(x, ld_nt(ci + k), n, alpha, flags);
                     }
                     p[j] = two_prod(a, xv, er[j]);
                 }
@@ -226,9 +244,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long(int n, const I *__restri
     if (lane == 0 && n_chunks) atomicAdd((unsigned long long *)&hdr[7], n_chunks);
 }
 
-template <bool PLAIN>
+template <bool PLAIN, class XT>
 __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__restrict__ lrows, int lcap, double beta,
-                                                              double *__restrict__ y, long long *__restrict__ hdr,
+                                                              typename XT::elem *__restrict__ y,
+                                                              long long *__restrict__ hdr,
                                                               const long long *__restrict__ lacc, int round_mode)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -245,9 +264,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__rest
         } else {
             long long v0 = g[lane], v1 = lane < NL - 64 ? g[64 + lane] : 0;
             unsigned flags = (unsigned)g[SP_ACC_FLAGS] & FLAG_NONFINITE;
-            sp_wave_add_beta(v0, v1, beta, y, row, flags);
+            sp_wave_add_beta<XT>(v0, v1, beta, y, row, flags);
             const WaveFinish r = finish_wave(v0, v1, flags);
-            if (lane == 0) y[row] = sp_pick(r, round_mode);
+            const unsigned long long v = sp_pick_to<XT>(r, flags, round_mode);
+            if (lane == 0) XT::store(y + row, v);
         }
     }
     if (lane == 0 && n_rows) atomicAdd((unsigned long long *)&hdr[6], n_rows);
@@ -257,9 +277,10 @@ __global__ void __launch_bounds__(SP_BLOCK) k_spmv_long_finish(const int *__rest
 // host side
 // ---------------------------------------------------------------------------------------------
 
-template <bool PLAIN, class I>
-static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, const double *val, double alpha,
-                              const double *x, double beta, double *y, int force_fb, int round_mode, hipStream_t st)
+template <bool PLAIN, class VT, class XT, class I>
+static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, const typename VT::elem *val, double alpha,
+                              const typename XT::elem *x, double beta, typename XT::elem *y, int force_fb, int round_mode,
+                              hipStream_t st)
 {
     const int path = c.spmv_path;
     const long long short_max = path == 3 ? -1 : SP_SHORT_MAX;
@@ -283,20 +304,20 @@ static hipError_t spmv_launch(Ctx &c, int m, int n, const I *rp, const I *ci, co
     {
         const long long waves = ((long long)m + 64 / SP_G_SHORT - 1) / (64 / SP_G_SHORT);
         const int grid = (int)min((long long)cap, (waves + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((k_spmv_rows<SP_G_SHORT, false, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, rp, ci, val,
+        hipLaunchKernelGGL((k_spmv_rows<SP_G_SHORT, false, PLAIN, VT, XT, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, rp, ci, val,
                            alpha, x, beta, y, short_max, (const int *)nullptr, hdr, force_fb, round_mode);
     }
     {
         const int grid = (int)min((long long)cap, ((long long)m + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((k_spmv_rows<64, true, PLAIN, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, rp, ci, val, alpha,
+        hipLaunchKernelGGL((k_spmv_rows<64, true, PLAIN, VT, XT, I>), dim3(grid), dim3(SP_BLOCK), 0, st, m, n, rp, ci, val, alpha,
                            x, beta, y, short_max, (const int *)med, hdr, force_fb, round_mode);
     }
     hipLaunchKernelGGL((k_spmv_long_prep<I>), dim3(1), dim3(1024), 0, st, rp, (const int *)lrows, lcap, chunk, hdr, lbase);
-    hipLaunchKernelGGL((k_spmv_long<PLAIN, I>), dim3(cap), dim3(SP_BLOCK), 0, st, n, rp, ci, val, alpha, x,
+    hipLaunchKernelGGL((k_spmv_long<PLAIN, VT, XT, I>), dim3(cap), dim3(SP_BLOCK), 0, st, n, rp, ci, val, alpha, x,
                        (const int *)lrows, (const long long *)lbase, lcap, chunk, hdr, lacc);
     {
         const int grid = (int)min((long long)c.num_cu * 2, ((long long)lcap + SP_WAVES - 1) / SP_WAVES);
-        hipLaunchKernelGGL((k_spmv_long_finish<PLAIN>), dim3(grid), dim3(SP_BLOCK), 0, st, (const int *)lrows, lcap, beta,
+        hipLaunchKernelGGL((k_spmv_long_finish<PLAIN, XT>), dim3(grid), dim3(SP_BLOCK), 0, st, (const int *)lrows, lcap, beta,
                            y, hdr, (const long long *)lacc, round_mode);
     }
     return hipGetLastError();
@@ -313,8 +334,48 @@ hipError_t exspmv_dispatch(Ctx &c, int m, int n, int index_bits, const void *row
     const int force_fb = (fpe == 0 || c.spmv_path == 1 || round_mode) ? 1 : 0;
     return sp_dispatch(index_bits, fpe, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
         constexpr bool PLAIN = decltype(plain)::value;   // the plain kernels neither force the accumulator nor round
-        return spmv_launch<PLAIN>(c, m, n, rp, ci, val, alpha, x, beta, y, PLAIN ? 0 : force_fb, PLAIN ? 0 : round_mode, st);
+        return spmv_launch<PLAIN, LpF64, LpF64>(c, m, n, rp, ci, val, alpha, x, beta, y, PLAIN ? 0 : force_fb,
+                                                PLAIN ? 0 : round_mode, st);
     });
+}
+
+// The narrow entry: values of the type val_dtype, x and y of vec_dtype (float64 or val_dtype; the caller has checked the
+// pair and that fpe != 1).  The same kernels with another front end: the exact sum is the one of the fp64 entry on the
+// widened operands.  A float64 y is rounded as there; a narrow y once, to nearest even whatever the mode (the reference
+// mode still sends every row through its accumulator, which changes no bit).
+template <class VT, class XT>
+static hipError_t spmv_lp_typed(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
+                                const void *val, double alpha, const void *x, double beta, void *y, int force_fb,
+                                int round_mode, hipStream_t st)
+{
+    return sp_dispatch(index_bits, 0, row_ptr, col_idx, [&](auto plain, auto *rp, auto *ci) {
+        if constexpr (decltype(plain)::value) return hipErrorInvalidValue;   // (fpe = 0 was passed: never taken)
+        else
+            return spmv_launch<false, VT, XT>(c, m, n, rp, ci, (const typename VT::elem *)val, alpha,
+                                              (const typename XT::elem *)x, beta, (typename XT::elem *)y, force_fb,
+                                              round_mode, st);
+    });
+}
+
+hipError_t exspmv_lp_dispatch(Ctx &c, int m, int n, int index_bits, const void *row_ptr, const void *col_idx,
+                              int val_dtype, const void *val, double alpha, int vec_dtype, const void *x, double beta,
+                              void *y, int fpe, int round_mode, hipStream_t st)
+{
+    if (m == 0) return hipSuccess;
+    const int force_fb = (fpe == 0 || c.spmv_path == 1 || round_mode) ? 1 : 0;
+    hipError_t e = hipErrorInvalidValue;
+    auto run = [&](auto vt, auto xt) {
+        e = spmv_lp_typed<decltype(vt), decltype(xt)>(c, m, n, index_bits, row_ptr, col_idx, val, alpha, x, beta, y,
+                                                      force_fb, round_mode, st);
+    };
+    auto by_value = [&](auto vt) {
+        if (vec_dtype == DT_F64) run(vt, LpF64());
+        else run(vt, vt);
+    };
+    if (val_dtype == DT_F32) by_value(LpF32());
+    else if (val_dtype == DT_F16) by_value(LpF16());
+    else if (val_dtype == DT_BF16) by_value(LpBF16());
+    return e;
 }
 
 }  // namespace exb

@@ -7,10 +7,15 @@
 // constants, the choice of index type and plain / exact kernels, the split thresholds.  For the routines built on these
 // pieces (sptrs_common.hip.h, block_common.hip.h) also the sink of a lane's expansion without an accumulator (SpLaneSink)
 // and the rule for fpe, path and rounding mode (st_rule).
+// The narrow products (exspmv_lp / exspmm_lp) run the same row step with typed front ends (lowp_types.hip.h): gather_x,
+// sp_absorb_beta and sp_wave_add_beta widen an element of the vector's type, sp_round_fast_to certifies a rounding into that
+// type against ITS rounding boundaries, and sp_pick_to / sp_acc_round_to round an accumulator's digits once into it.  With
+// LpF64 (the default) every one of them is the fp64 code above it.
 #pragma once
 #include "superacc.hip.h"
 #include "fpe.hip.h"
 #include "exblas_internal.h"
+#include "lowp_types.hip.h"
 
 namespace exb {
 
@@ -30,11 +35,13 @@ constexpr int SP_ACC_FLAGS = NL + 3;       // word of a long row's accumulator t
 template <class I>
 __device__ __forceinline__ I ld_nt(const I *p) { return __builtin_nontemporal_load(p); }
 
-// fl(alpha * x[c]) for an in-range column; a column outside [0, n) is never read and makes the row NaN
-template <class I>
-__device__ __forceinline__ double gather_x(const double *__restrict__ x, I c, int n, double alpha, unsigned &flags)
+// fl(alpha * W(x[c])) for an in-range column; a column outside [0, n) is never read and makes the row NaN.  XT: the
+// element type of x (lowp_types.hip.h), W its exact widening
+template <class XT = LpF64, class I>
+__device__ __forceinline__ double gather_x(const typename XT::elem *__restrict__ x, I c, int n, double alpha,
+                                           unsigned &flags)
 {
-    if ((unsigned long long)(long long)c < (unsigned long long)n) return alpha * x[c];
+    if ((unsigned long long)(long long)c < (unsigned long long)n) return alpha * XT::widen(x[c]);
     flags |= FLAG_NAN | SP_SPILL;
     return 0.0;
 }
@@ -103,6 +110,52 @@ __device__ __forceinline__ bool spmv_round_fast(double (&f)[N], double &out)
     return true;
 }
 
+// (The typed forms below -- sp_round_fast_to, sp_certify_or_spill_to, sp_pick_to, sp_acc_round_to -- stand BESIDE
+// spmv_round_fast, sp_certify_or_spill, sp_pick and sp_acc_round and repeat some of their lines on purpose: the fp64
+// functions, and finish_wave under them, are shared with the solves, the factors and the block routines, and are left
+// exactly as they were so that the code generated for every fp64 kernel stays what it was.  With LpF64 the typed forms
+// only call them.)
+// The same certificate for an output of the type XT, as the bit pattern to store.  float64: spmv_round_fast.  A narrow XT:
+// the same two VecSum passes, res and the bound |q| + tail on |S - res| -- the tail taken twice over and the whole with a
+// margin of 2^-30, the safety factors of spmv_round_fast -- and round_interval_to (round_lowp.hip.h), which certifies
+// against the rounding boundaries of XT: the value is returned only if every real number within the bound of res rounds
+// to it.  A bound of zero says that res is the exact sum, and then a tie of XT is decided here.
+template <class XT, int N>
+__device__ __forceinline__ bool sp_round_fast_to(double (&f)[N], unsigned long long &bits)
+{
+    if constexpr (XT::DT == DT_F64) {
+        double out = 0.0;
+        const bool ok = spmv_round_fast<N>(f, out);
+        bits = (unsigned long long)__double_as_longlong(out);
+        return ok;
+    } else {
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll
+            for (int i = N - 1; i >= 1; --i) {
+                double s;
+                f[i - 1] = two_sum(f[i - 1], f[i], s);
+                f[i] = s;
+            }
+        }
+        double q;
+        const double res = two_sum(f[0], f[1], q);
+        double tail = 0.0;
+        bool any = f[0] != 0.0 || f[1] != 0.0;
+#pragma unroll
+        for (int i = 2; i < N; ++i) {
+            tail += __builtin_fabs(f[i]);
+            any |= f[i] != 0.0;
+        }
+        bits = 0ull;   // the exact sum is zero: +0, as the accumulator rounds it
+        if (!any) return true;
+        const unsigned ef = expo_field(res);
+        if (ef < 1023u - 960u || ef >= 1023u + 1020u) return false;
+        const double b = __builtin_fabs(q) + 2.0 * tail;
+        return round_interval_to(res, b + b * 0x1p-30, XT::DT, &bits) != 0;
+    }
+}
+
 // between a wave's lanes writing LDS and other lanes of it reading (or overwriting) the same words
 __device__ __forceinline__ void sp_wave_sync()
 {
@@ -138,10 +191,61 @@ __device__ __forceinline__ bool sp_certify_or_spill(double (&f)[SP_N], unsigned 
     return false;
 }
 
+// the same with the output of the type XT, as the bit pattern to store (sp_round_fast_to)
+template <class XT>
+__device__ __forceinline__ bool sp_certify_or_spill_to(double (&f)[SP_N], unsigned &flags, int force_fb, long long *acc,
+                                                       unsigned long long &bits)
+{
+    if (!force_fb && flags == 0 && sp_round_fast_to<XT, SP_N>(f, bits)) return true;
+#pragma unroll
+    for (int i = 0; i < SP_N; ++i)
+        if (f[i] != 0.0) lds_add<1>(acc, f[i], flags);
+    return false;
+}
+
 // the value of a finished accumulator under the rounding mode (0: nearest even, else the reference's)
 __device__ __forceinline__ double sp_pick(const WaveFinish &r, int round_mode)
 {
     return round_mode ? r.rf : __longlong_as_double((long long)r.ex);
+}
+
+// The pattern to store for an output of the type XT from a finished accumulator.  float64: sp_pick.  A narrow XT is rounded
+// ONCE, to nearest even whatever the mode, from the normalised digits the wave holds in r.d0 / r.d1 -- never from r.ex,
+// which is rounded already.  The wave forms the magnitude and its leading 64 bits as finish_wave does for the double;
+// round_window_to (round_lowp.hip.h) is round_digits_to on them.  Every lane gets the pattern.
+template <class XT>
+__device__ __forceinline__ unsigned long long sp_pick_to(const WaveFinish &r, unsigned nonfinite, int round_mode)
+{
+    if constexpr (XT::DT == DT_F64) {
+        return (unsigned long long)__double_as_longlong(sp_pick(r, round_mode));
+    } else {
+        if (nonfinite & FLAG_NONFINITE) return nonfinite_to(r.ex, XT::DT);
+        const int lane = (int)(threadIdx.x & 63u);
+        constexpr int HI = NL - 64;
+        const bool neg = lane_bcast(r.d1, HI - 1) < 0;
+        const unsigned d0 = (unsigned)r.d0, d1 = (unsigned)r.d1;
+        const unsigned long long nz0 = __ballot(d0 != 0), nz1 = __ballot(lane < HI && d1 != 0);
+        const int z = nz0 ? __builtin_ctzll(nz0) : (nz1 ? 64 + __builtin_ctzll(nz1) : NL);
+        const int i1 = 64 + lane;
+        const unsigned m0 = !neg ? d0 : (lane < z ? 0u : (lane == z ? (0u - d0) : ~d0));
+        const unsigned m1 = (lane >= HI) ? 0u : (!neg ? d1 : (i1 < z ? 0u : (i1 == z ? (0u - d1) : ~d1)));
+        const unsigned long long mz0 = __ballot(m0 != 0), mz1 = __ballot(m1 != 0);
+        const int tp = mz1 ? 64 + (63 - __builtin_clzll(mz1)) : (mz0 ? 63 - __builtin_clzll(mz0) : -1);
+        if (tp < 0) return 0ull;
+        auto mag = [&](int i) -> unsigned {   // i uniform
+            const unsigned a = lane_bcast(m0, i & 63), b = lane_bcast(m1, (i - 64) & 63);
+            return i < 0 ? 0u : (i < 64 ? a : b);
+        };
+        const unsigned mt = mag(tp), ma = mag(tp - 1), mb = mag(tp - 2);
+        const int lz = __builtin_clz(mt | 1u);
+        unsigned long long w = ((unsigned long long)mt << 32) | ma;
+        unsigned rest = mb;
+        if (lz) {
+            w = (w << lz) | (unsigned long long)(mb >> (32 - lz));
+            rest = mb << lz;
+        }
+        return round_window_to(neg, 32 * tp + 31 - lz, w, rest != 0 || z < tp - 2, XT::DT);
+    }
 }
 
 __device__ __forceinline__ void sp_acc_clear(long long *a)
@@ -162,6 +266,17 @@ __device__ __forceinline__ double sp_acc_round(long long *a, unsigned nonfinite,
     return sp_pick(r, round_mode);
 }
 
+// the same for an output of the type XT, as the bit pattern to store (sp_pick_to)
+template <class XT>
+__device__ __forceinline__ unsigned long long sp_acc_round_to(long long *a, unsigned nonfinite, int round_mode)
+{
+    const int lane = threadIdx.x & 63;
+    const long long v0 = a[lane], v1 = lane < NL - 64 ? a[64 + lane] : 0;
+    const WaveFinish r = finish_wave(v0, v1, nonfinite);
+    sp_acc_clear(a);
+    return sp_pick_to<XT>(r, nonfinite, round_mode);
+}
+
 // which lanes of the wave hold which non-finite flag; of(group): the union over the lanes of a mask
 struct NonFiniteLanes {
     unsigned long long pinf, ninf, nan;
@@ -177,14 +292,14 @@ struct NonFiniteLanes {
 };
 
 // beta * y under ExGEMV's rules (beta = 0 ignores y, 1 adds it exactly, else the error-free product), absorbed into a
-// lane's expansion; `take` says whether this lane carries the term (y[at] is read by no other)
-template <class Sink>
-__device__ __forceinline__ void sp_absorb_beta(double (&f)[SP_N], bool take, double beta, const double *y, long long at,
-                                               Sink &sink)
+// lane's expansion; `take` says whether this lane carries the term (y[at] is read by no other).  XT: the element type of y
+template <class XT = LpF64, class Sink>
+__device__ __forceinline__ void sp_absorb_beta(double (&f)[SP_N], bool take, double beta, const typename XT::elem *y,
+                                               long long at, Sink &sink)
 {
     double p[1] = {0.0}, er[1] = {0.0};
     if (take && beta != 0.0) {
-        const double yv = y[at];
+        const double yv = XT::widen(y[at]);
         if (beta == 1.0) p[0] = yv;
         else p[0] = two_prod(beta, yv, er[0]);
     }
@@ -192,11 +307,12 @@ __device__ __forceinline__ void sp_absorb_beta(double (&f)[SP_N], bool take, dou
 }
 
 // the same term added into the accumulator a wave holds in (v0, v1)
-__device__ __forceinline__ void sp_wave_add_beta(long long &v0, long long &v1, double beta, const double *y,
+template <class XT = LpF64>
+__device__ __forceinline__ void sp_wave_add_beta(long long &v0, long long &v1, double beta, const typename XT::elem *y,
                                                  long long at, unsigned &flags)
 {
     if (beta == 0.0) return;
-    const double yv = y[at];
+    const double yv = XT::widen(y[at]);
     if (beta == 1.0) {
         wave_add_double(v0, v1, yv, flags);
     } else {

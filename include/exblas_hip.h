@@ -323,6 +323,45 @@ void exblas_set_spmm_path(int mode);
  * integer accumulator after the main kernel deferred them, out[2] rows split across workgroups, out[3] chunks of those
  * rows.  Synchronises the device; valid until the next call that uses the workspace; -1 when unknown. */
 int exblas_last_spmm_info(int64_t *out4);
+/* Narrow ExSpMV / ExSpMM: the matrix values in float32, float16 or bfloat16 (val_dtype, an EXBLAS_DT_* code) read at
+ * their own width, the vectors x and y (the blocks X and Y) in float64 or in the type of the values (vec_dtype).  With W
+ * the exact widening to double,
+ *     y_i = RoundTo_vec_dtype( sum_p W(val[p]) * fl64(alpha * W(x[col_idx[p]]))  (+)  beta * W(y_i) )
+ * where the sum is the one exblas_exspmv_csr_dev forms on the widened operands, with every rule stated there (alpha folded
+ * into x by one rounded fp64 multiply, the three cases of beta, the product domain and non-finite rules, empty rows,
+ * duplicate columns, a column outside [0, n) makes the row NaN unread), and RoundTo is ONE rounding of that exact sum:
+ *   vec_dtype = EXBLAS_DT_F64: the rounding of the fp64 entry, in both modes of exblas_set_round_mode: the result is bit for
+ *     bit exblas_exspmv_csr_dev / exblas_exspmm_csr_dev on the values converted to double;
+ *   vec_dtype = val_dtype: to nearest, ties to even, whatever the mode, straight into the narrow format as
+ *     exblas_round_records_dev does (subnormal results, the carry into the next binade, overflow to +-Inf at the format's
+ *     threshold, -0 for a negative sum that rounds to zero; +-Inf and NaN convert exactly).  The double of the fp64 entry
+ *     cast afterwards would round twice.
+ * ExSpMM: column j of Y is bit for bit the narrow ExSpMV on (A, X[:, j], Y[:, j]); ldx and ldy count elements; the padding
+ * of Y is never written.  The bits depend on the data only (not on the index width, fpe, early_exit, the path, the grid,
+ * k, the column tile, ldx / ldy or the alignment).  Pointers need the alignment of their element only.
+ * (EXBLAS_DT_F64, EXBLAS_DT_F64) forwards to the fp64 entry.  fpe: 0 and 2..8; fpe == 1 returns EXBLAS_UNSUPPORTED (there
+ * is no plain narrow kernel).  hipErrorInvalidValue, before a device is touched: an unknown dtype, float64 values with
+ * narrow vectors, two different narrow types, a pointer that is no multiple of its element size, any other fpe, and
+ * whatever the fp64 entries refuse.  exblas_set_spmv_path / exblas_set_spmm_path and exblas_last_spmv_info /
+ * exblas_last_spmm_info apply with their meanings; workspace and graph capture as for the fp64 entries. */
+int exblas_exspmv_csr_lp_dev(int m, int n, int index_bits, const void *d_row_ptr, const void *d_col_idx, int val_dtype,
+                             const void *d_val, double alpha, int vec_dtype, const void *d_x, double beta, void *d_y, int fpe,
+                             int early_exit, void *stream);
+int exblas_exspmm_csr_lp_dev(int m, int n, int k, int index_bits, const void *d_row_ptr, const void *d_col_idx,
+                             int val_dtype, const void *d_val, double alpha, int vec_dtype, const void *d_x, int64_t ldx,
+                             double beta, void *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
+/* The certificate behind the narrow products' rounding in registers, on the CPU; no device is touched.  Returns 1 and in
+ * *bits the pattern (low 64 / 32 / 16 bits) of the one `dtype` value that EVERY real number of [res - bound, res + bound]
+ * rounds to (to nearest, ties to even), or 0 (and *bits = 0) when the interval reaches a rounding boundary of the format,
+ * so that the value cannot be decided from (res, bound).  bound == 0 declares res exact: ties are then decided, to even.
+ * Sound for every input; it certifies whenever res lies more than 4 * bound from every boundary.  A negative value for
+ * an unknown dtype or a NULL pointer. */
+int exblas_round_interval_host(double res, double bound, int dtype, uint64_t *bits);
+/* The narrow sparse products' rounding of an accumulator, on the CPU; no device is touched.  The same contract as
+ * exblas_round_digits_host (68 normalised digits in, the pattern out), computed the way the kernels do it: from the
+ * leading bit, the 64 bits below it and a sticky for the rest.  It equals exblas_round_digits_host bit for bit for all
+ * four dtypes. */
+int exblas_round_window_host(const int64_t *digits68, int dtype, uint64_t *bits);
 /* ExSpTRSV: exact, reproducible sparse triangular solve A x = b for a square m x m CSR matrix A on device pointers
  * (row_ptr[m+1], col_idx[nnz] int32 or int64, both the same width; val and x contiguous fp64).  d_x holds b on entry and
  * the solution on return, as in exblas_extrsv_dev.  uplo 'L': forward, rows 0 .. m-1,
@@ -920,6 +959,13 @@ int exblas_exsptrsm_csr_ctx(exblas_ctx_t *ctx, char uplo, char diag, int m, int 
 int exblas_exspmm_csr_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
                           const void *d_col_idx, const double *d_val, double alpha, const double *d_x, int64_t ldx,
                           double beta, double *d_y, int64_t ldy, int fpe, int early_exit, void *stream);
+int exblas_exspmv_csr_lp_ctx(exblas_ctx_t *ctx, int m, int n, int index_bits, const void *d_row_ptr,
+                             const void *d_col_idx, int val_dtype, const void *d_val, double alpha, int vec_dtype,
+                             const void *d_x, double beta, void *d_y, int fpe, int early_exit, void *stream);
+int exblas_exspmm_csr_lp_ctx(exblas_ctx_t *ctx, int m, int n, int k, int index_bits, const void *d_row_ptr,
+                             const void *d_col_idx, int val_dtype, const void *d_val, double alpha, int vec_dtype,
+                             const void *d_x, int64_t ldx, double beta, void *d_y, int64_t ldy, int fpe, int early_exit,
+                             void *stream);
 int exblas_exbdot_ctx(exblas_ctx_t *ctx, char mode, int64_t n, int p, int q, const double *d_x, int64_t ldx,
                       const double *d_y, int64_t ldy, double *d_c, int64_t ldc, int fpe, int early_exit, void *stream);
 int exblas_exbgemm_ctx(exblas_ctx_t *ctx, int64_t n, int p, int q, double alpha, const double *d_x, int64_t ldx,
@@ -1076,6 +1122,13 @@ int exblas_exgemm(char transa, char transb, int m, int n, int k, double alpha, c
  * synchronous.  Returns 0 or hipErrorInvalidValue (also for a negative row_ptr entry). */
 int exblas_exspmv_csr(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, const double *val,
                       double alpha, const double *x, double beta, double *y, int fpe, int early_exit);
+/* exblas_exspmv_csr_lp_dev / exblas_exspmm_csr_lp_dev on host arrays, staged through the current device */
+int exblas_exspmv_csr_lp(int m, int n, int index_bits, const void *row_ptr, const void *col_idx, int val_dtype,
+                         const void *val, double alpha, int vec_dtype, const void *x, double beta, void *y, int fpe,
+                         int early_exit);
+int exblas_exspmm_csr_lp(int m, int n, int k, int index_bits, const void *row_ptr, const void *col_idx, int val_dtype,
+                         const void *val, double alpha, int vec_dtype, const void *x, int64_t ldx, double beta, void *y,
+                         int64_t ldy, int fpe, int early_exit);
 /* exblas_exspmm_csr_dev on host arrays (X: n rows of ldx, Y: m rows of ldy, updated in place; the padding of Y keeps
  * its values): staged through the device, synchronous.  Returns 0 or hipErrorInvalidValue (also for a negative row_ptr
  * entry). */
